@@ -7,7 +7,7 @@ set -e -o pipefail
 OUT=gpurun_out/round3
 mkdir -p $OUT/pmc
 export TMPDIR=/tmp
-timeout -k 10 400 python3 bench.py --config C3 --ransac-budget 0 > $OUT/bench_C3_dator.json
+timeout -k 10 400 python3 bench.py --full --config C3 --ransac-budget 0 > $OUT/bench_C3_dator.json
 keep() { f=$(find $1 -name '*counter_collection.csv' | head -1); head -1 $f > $2; grep 'ibl_' $f >> $2; rm -rf $1; }
 for c in FETCH_SIZE WRITE_SIZE; do
     tag=$(echo $c | tr A-Z a-z | cut -d_ -f1)

@@ -10,21 +10,21 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 case "$1" in
 a)
-    timeout -k 10 700 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-    timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python3 bench.py --cpu-frames 0 --ransac-budget 0 --adjacent-spacing 0 --no-h2d --repeats 1 > $OUT/bench_default_under_rocprof.json
+    timeout -k 10 700 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+    timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- python3 bench.py --full --cpu-frames 0 --ransac-budget 0 --adjacent-spacing 0 --no-h2d --repeats 1 > $OUT/bench_default_under_rocprof.json
     python3 tools/step_breakdown.py $OUT/prof 40 > $OUT/bench_default_last_step_breakdown.txt
     cp $(find $OUT/prof -name '*kernel_stats.csv' | head -1) $OUT/bench_default_kernel_stats.csv
     rm -rf $OUT/prof
-    timeout -k 10 300 python3 bench.py --sequential --cpu-frames 0 --ransac-budget 0 --adjacent-spacing 0 --no-h2d --repeats 1 > $OUT/bench_sequential.json
+    timeout -k 10 300 python3 bench.py --full --sequential --cpu-frames 0 --ransac-budget 0 --adjacent-spacing 0 --no-h2d --repeats 1 > $OUT/bench_sequential.json
     ;;
 b|b1)
-    timeout -k 10 300 python3 bench.py --config C1 > $OUT/bench_C1.json
-    timeout -k 10 300 python3 bench.py --config C2 --cpu-frames 0 --ransac-budget 0 > $OUT/bench_C2.json
-    timeout -k 10 500 python3 bench.py --config C3 --ransac-budget 0 > $OUT/bench_C3_dator.json
+    timeout -k 10 300 python3 bench.py --full --config C1 > $OUT/bench_C1.json
+    timeout -k 10 300 python3 bench.py --full --config C2 --cpu-frames 0 --ransac-budget 0 > $OUT/bench_C2.json
+    timeout -k 10 500 python3 bench.py --full --config C3 --ransac-budget 0 > $OUT/bench_C3_dator.json
     ;;&
 b|b2)
-    timeout -k 10 300 python3 bench.py --config C4 --cpu-frames 0 > $OUT/bench_C4_m50000.json
-    timeout -k 10 700 python3 bench.py --config C4 --cpu-frames 0 --layout sharded > $OUT/bench_C4_m50000_shard_rccl_world1.json
+    timeout -k 10 300 python3 bench.py --full --config C4 --cpu-frames 0 > $OUT/bench_C4_m50000.json
+    timeout -k 10 700 python3 bench.py --full --config C4 --cpu-frames 0 --layout sharded > $OUT/bench_C4_m50000_shard_rccl_world1.json
     ;;
 c)
     mkdir -p $OUT/pmc
