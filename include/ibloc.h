@@ -529,6 +529,13 @@ int ibl_evaluate_points(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float* 
                         const int32_t* job_end, const double* T_global, int n_jobs, double threshold, float* d2_out, double* rmse_out,
                         double* fitness_out, void* stream);
 
+/* 1 - IoU of the oriented boxes of n objects, as ObjectMemory._recluster_IoU feeds scikit-learn.
+ * boxes [dev] n x 15 f64 (centre, R row-major, half extents); valid [dev] n int32 (0: no box -> IoU 0 with everything);
+ * dist [dev] n x n f64 row-major, caller-owned; n_overlapping [host, may be NULL]: pairs that passed the separating-axis test
+ * (synchronises the stream when non-NULL).  Scratch from ctx's arena, released on return. */
+int ibl_obb_iou_matrix(ibl_reg_ctx* ctx, const double* boxes, const int32_t* valid, int64_t n, double* dist,
+                       int64_t* n_overlapping, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

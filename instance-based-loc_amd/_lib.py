@@ -94,6 +94,7 @@ _SIGS = {
     "ibl_match_topk_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "ibl_match_topk": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                  C.c_int64, vp]),
+    "ibl_obb_iou_matrix": (C.c_int, [vp, vp, vp, C.c_int64, vp, vp, vp]),
 }
 
 

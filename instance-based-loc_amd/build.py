@@ -75,6 +75,32 @@ def dbscan_batch(ctx: RegContext, groups, eps, min_points, device="cuda"):
     return [h[off[i]:off[i + 1]] for i in range(len(sizes))], n_clusters[:len(sizes)].copy()
 
 
+def obb_iou_matrix(ctx: RegContext, boxes, valid, device="cuda", return_overlapping=False):
+    """1 - IoU of the oriented boxes of n objects (csrc/obb_iou.hip): boxes (n, 15) float64 rows of
+    `utils.IoU_ops.oriented_bounding_boxes` (centre, R row-major, half extents), valid (n,) int (0 = no box: IoU 0 with every
+    object).  Returns the (n, n) float64 device tensor `_recluster_IoU` hands to scikit-learn (diagonal 1, rows and columns of
+    invalid objects 1); with return_overlapping=True also the number of pairs that passed the separating-axis test."""
+    B = torch.as_tensor(boxes, dtype=torch.float64, device=device).contiguous()
+    V = torch.as_tensor(valid, device=device).to(torch.int32).contiguous()
+    if B.dim() != 2 or B.shape[1] != 15 or V.shape != (B.shape[0],):
+        raise ValueError(f"boxes must be (n, 15) and valid (n,): got {tuple(B.shape)} and {tuple(V.shape)}")
+    n = B.shape[0]
+    D = torch.empty((n, n), dtype=torch.float64, device=B.device)
+    n_ov = np.zeros(1, dtype=np.int64)
+    st = _lib.lib.ibl_obb_iou_matrix(ctx.handle, B.data_ptr() if n else None, V.data_ptr() if n else None, n, D.data_ptr() if n else None,
+                                     n_ov.ctypes.data, _stream())
+    _lib.check(st, "ibl_obb_iou_matrix")
+    return (D, int(n_ov[0])) if return_overlapping else D
+
+
+def oriented_box_distance_matrix(clouds, ctx: RegContext, device="cuda", threads=None):
+    """the matrix of ObjectMemory._recluster_IoU's host loop (1 - calculate_obj_aligned_3d_IoU for every pair, 1 on the diagonal)
+    as a host array: one oriented box per cloud on host threads, the N^2 / 2 intersections on the device"""
+    from .utils.IoU_ops import oriented_bounding_boxes
+    boxes, valid = oriented_bounding_boxes(clouds, threads=threads)
+    return obb_iou_matrix(ctx, boxes, valid, device=device).cpu().numpy()
+
+
 # ---- host helpers of the consolidation step ----------------------------------------------------------------------------------
 _default_ctx = None
 

@@ -74,6 +74,7 @@ class ObjectMemory():
         self.object_finder = object_finder
         self.dataset_floor_thickness = dataset_floor_thickness
         self.iou_func = None            # (points_i, points_j) -> IoU for _recluster_IoU; the reference's Objectron IoU is third-party
+        self.iou_backend = "host"       # default measure of _recluster_IoU: "host" pair loop, or "device" (boxes on host threads, pairs on the GPU)
         self.memory = []
         self.floors = None
         self._ctx = RegContext(arena_bytes)
@@ -185,17 +186,26 @@ class ObjectMemory():
 
     def _recluster_IoU(self, IoU_threshold=0.6, iou_func=None):
         """:710-747: average-linkage agglomerative clustering on 1 - IoU.  iou_func(points_i, points_j): the reference uses the
-        object-aligned Objectron IoU (third-party, not in this build, see utils/IoU_ops.py); ObjectMemory.iou_func is the default."""
+        object-aligned Objectron IoU (third-party, not in this build, see utils/IoU_ops.py); ObjectMemory.iou_func is the default.
+        With neither given, the object-aligned IoU of utils/IoU_ops.py is used: pair by pair on the host (iou_backend "host"), or
+        as one device matrix (iou_backend "device", the same values within 1e-9).  A user iou_func always runs in the host loop."""
         from sklearn.cluster import AgglomerativeClustering
+        if self.iou_backend not in ("host", "device"):
+            raise ValueError(f"iou_backend must be 'host' or 'device', not {self.iou_backend!r}")
         iou_func = iou_func or self.iou_func
-        if iou_func is None:
-            from ibloc_amd.utils.IoU_ops import calculate_obj_aligned_3d_IoU as iou_func
-        n = len(self.memory)
-        IoUs = np.zeros((n, n))
-        for i in range(n):
-            for j in range(i, n):
-                IoUs[i][j] = 1 if i == j else 1 - iou_func(np.asarray(self.memory[i].pointcloud.points), np.asarray(self.memory[j].pointcloud.points))
-                IoUs[j][i] = IoUs[i][j]
+        if iou_func is None and self.iou_backend == "device":
+            # the default measure as one matrix: an oriented box per object, every pair's 1 - IoU on the device (ibl_obb_iou_matrix)
+            from ibloc_amd.build import oriented_box_distance_matrix
+            IoUs = oriented_box_distance_matrix([np.asarray(o.pointcloud.points) for o in self.memory], self._ctx, device=self._device())
+        else:
+            if iou_func is None:
+                from ibloc_amd.utils.IoU_ops import calculate_obj_aligned_3d_IoU as iou_func
+            n = len(self.memory)
+            IoUs = np.zeros((n, n))
+            for i in range(n):
+                for j in range(i, n):
+                    IoUs[i][j] = 1 if i == j else 1 - iou_func(np.asarray(self.memory[i].pointcloud.points), np.asarray(self.memory[j].pointcloud.points))
+                    IoUs[j][i] = IoUs[i][j]
         self._log("Clustering agglomeratively")
         labels = AgglomerativeClustering(n_clusters=None, distance_threshold=1 - IoU_threshold, metric='precomputed', linkage='average').fit(IoUs).labels_
         new_memory = [None for _ in set(labels)]

@@ -135,3 +135,36 @@ class SynthWorld:
             clouds.append((pc, col[keep]))
         det = self.base_emb[ids] + rng.normal(0, emb_noise / np.sqrt(self.D), size=(len(ids), self.D))
         return {"ids": ids, "clouds": clouds, "det_emb": det.astype(np.float32), "pose": T_wc}
+
+
+def fragment_scene(n_fragments, seed=0, spacing=1.5):
+    """Clouds of the memory-consolidation step (ObjectMemory._recluster_IoU): objects on a jittered grid, each observed as 3-8
+    overlapping fragments of 1 000-3 000 points (a random half-space cut of the object's box surface, turned by a few degrees).
+    Boxes of U[0.05, 0.5] m half extents at random orientations; a third of the objects are thin (one half extent 2-8 mm) and a
+    sixth near-flat (0.5 mm).  Returns (list of (N_i, 3) float64 arrays, object index per fragment), fragments of one object
+    adjacent in the list."""
+    rng = np.random.default_rng(seed)
+    clouds, owner = [], []
+    side = max(1, int(np.ceil(np.sqrt(n_fragments / 5.5))))
+    k = 0
+    while len(clouds) < n_fragments:
+        centre = np.array([(k % side) * spacing, (k // side) * spacing, 0.0]) + rng.uniform(-0.2, 0.2, size=3)
+        half = rng.uniform(0.05, 0.5, size=3)
+        if k % 3 == 1:
+            half[rng.integers(3)] = rng.uniform(0.002, 0.008)
+        elif k % 6 == 2:
+            half[rng.integers(3)] = 0.0005
+        R = Rotation.random(random_state=rng).as_matrix()
+        for _ in range(min(int(rng.integers(3, 9)), n_fragments - len(clouds))):
+            m = int(rng.integers(1000, 3001))
+            u = rng.uniform(-1, 1, size=(m, 3))
+            ax = rng.integers(0, 3, size=m)
+            u[np.arange(m), ax] = np.sign(u[np.arange(m), ax])              # on the box surface
+            keep = u @ rng.normal(size=3) < rng.uniform(0.0, 0.6)            # the part a view sees
+            u = u[keep] if keep.sum() >= 50 else u
+            Rf = Rotation.from_rotvec(rng.normal(size=3) * 0.04).as_matrix()
+            p = (u * half) @ (R @ Rf).T + centre + rng.normal(size=(len(u), 3)) * 1e-3
+            clouds.append(p)
+            owner.append(k)
+        k += 1
+    return clouds, np.asarray(owner)

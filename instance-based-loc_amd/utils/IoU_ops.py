@@ -67,6 +67,37 @@ def oriented_bounding_box(points):
     return centre, R, (hi - lo) / 2
 
 
+MAX_BOX_THREADS = 16
+
+
+def oriented_bounding_boxes(clouds, threads=None):
+    """`oriented_bounding_box` of every cloud, on a pool of at most 16 threads (Qhull and LAPACK release the GIL).  Returns
+    (boxes (N, 15) float64: centre, R row-major, half extents; valid (N,) int32).  A cloud whose box raises (fewer than 4 points,
+    coplanar points) gets valid = 0 and a zero row: it has IoU 0 with every other object, as in calculate_obj_aligned_3d_IoU."""
+    from concurrent.futures import ThreadPoolExecutor
+    clouds = list(clouds)
+    n = len(clouds)
+    boxes = np.zeros((n, 15), dtype=np.float64)
+    valid = np.zeros(n, dtype=np.int32)
+
+    def one(i):
+        try:
+            c, R, h = oriented_bounding_box(_pts(clouds[i]).T)
+        except Exception:
+            return
+        boxes[i, :3], boxes[i, 3:12], boxes[i, 12:] = c, R.reshape(9), h
+        valid[i] = 1
+
+    workers = max(1, min(MAX_BOX_THREADS if threads is None else int(threads), MAX_BOX_THREADS, n))
+    if workers == 1:
+        for i in range(n):
+            one(i)
+    else:
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            list(pool.map(one, range(n)))
+    return boxes, valid
+
+
 def _box_halfspaces(centre, R, half):
     """six rows [n | -offset] with n . x - offset <= 0 inside the box"""
     rows = []
