@@ -75,9 +75,11 @@ typedef struct {                   /* all [dev]; weights fp16 [N][K] row-major (
     const float* ln1_g; const float* ln1_b;
     const void* w_qkv;  const float* b_qkv;     /* [3*dim][dim] = [Wq; Wk; Wv], [3*dim]              */
     const void* w_o;    const float* b_o;       /* [dim][dim]                                         */
-    const float* ls1;                            /* [dim] or NULL.  NULL (no LayerScale in the model, or ls1 multiplied into the rows of
-                                                  * w_o and into b_o by the host, as ibloc_amd.vit does) selects the faster residual GEMM:
-                                                  * the residual tile is preloaded into the accumulators and the epilogue only stores   */
+    const float* ls1;                            /* [dim] or NULL.  NULL is accepted (no LayerScale in the model, or ls1 multiplied into the
+                                                  * rows of w_o and into b_o by the host, as ibloc_amd.vit can do) and runs the same
+                                                  * read-modify-write residual GEMM with a scale of 1.  The form with the residual tile
+                                                  * preloaded into the accumulators is opt-in ($IBL_GEMM_RESID_PRE=1) and measured ~2 %
+                                                  * slower                                                                 */
     const float* ln2_g; const float* ln2_b;
     const void* w_fc1;  const float* b_fc1;     /* [mlp_dim][dim]                                     */
     const void* w_fc2;  const float* b_fc2;     /* [dim][mlp_dim]                                     */

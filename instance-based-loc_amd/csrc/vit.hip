@@ -69,7 +69,6 @@ struct GemmEpi {
     int accumulate;         // EPI_PATCH: x += alpha * acc instead of x = acc + bias + pos (second weight term of a two-term operand)
     float alpha;
     int algo_k;             // K the in-process timer counts as algorithmic (0: K itself; -1: none -- extra terms of a two-term operand are overhead, not model FLOPs)
-    int stagger;            // persistent grid: workgroup b sleeps (b % 4) * stagger * 64 clocks before its first tile (launch_gemm_cfg)
 };
 
 constexpr int GBK = 64;                 // K granule every caller guarantees (K % 64 == 0)
@@ -80,42 +79,27 @@ constexpr int GBK = 64;                 // K granule every caller guarantees (K 
 __device__ __forceinline__ int key_act(int r) { return r & 7; }
 __device__ __forceinline__ int key_w(int r) { return (((r >> 4) & 3) << 1) | ((r >> 1) & 1); }
 __device__ __forceinline__ int key_pair(int r) { return (((r >> 3) & 3) << 1) | ((r >> 1) & 1); }   // rows 8 a + 4 b + c, a = 0..3, c = 0..3
-// 64-byte tile rows (BK = 32): 4 chunks per row, four rows per 256-byte bank row; the same three fragment-row maps are
-// conflict-free in every 16-lane ds_read_b128 group with a one-bit key (found by enumeration, tools/lds_keys.py)
-template <int BK> __device__ __forceinline__ int keyx_act(int r) { return BK == 64 ? key_act(r) : ((r >> 2) & 1) << 1; }
-template <int BK> __device__ __forceinline__ int keyx_w(int r) { return BK == 64 ? key_w(r) : ((r >> 4) & 1) << 1; }
-template <int BK> __device__ __forceinline__ int keyx_pair(int r) { return BK == 64 ? key_pair(r) : ((r >> 3) & 1) << 1; }
 
-// C[M][N] = A[M][K] * W[N][K]^T.  Block tile (WM * MI * 16) x (WN * 64) x BK, one wave per (MI * 16) x 64 sub-tile, two LDS stages:
-//   <MI = 4, WM = 2, WN = 2, BK = 64>: 128 x 128, 256 threads, 64 KiB LDS (2 blocks / CU)  -- any N % 128 == 0
-//   <MI = 8, WM = 2, WN = 4, BK = 64>: 256 x 256, 512 threads, 128 KiB LDS (1 block / CU) -- N % 256 == 0; halves the operand
-//                             traffic per FLOP (the 128 x 128 form saturates the L2 path at ~7 TB/s)
-//   <MI = 8, WM = 2, WN = 2, BK = 32>: 256 x 128, 256 threads, 48 KiB LDS (2 blocks / CU); measured slower than 256 x 256 on
-//                             every ViT-B shape (launch_gemm, IBL_GEMM_CFG=2)
+// C[M][N] = A[M][K] * W[N][K]^T.  Block tile (2 * MI * 16) x (WN * 64) x 64, one wave per (MI * 16) x 64 sub-tile, two LDS stages.
+// Two shapes (launch_gemm chooses from M and N):
+//   T256 (MI = 8, WN = 4): 256 x 256, 512 threads, 128 KiB LDS, 1 block / CU, software-pipelined K loop, persistent grid
+//                          -- N % 256 == 0; halves the operand traffic per FLOP (the 128 x 128 form saturates the L2 path at ~7 TB/s)
+//   else (MI = 4, WN = 2): 128 x 128, 256 threads,  64 KiB LDS, 2 blocks / CU, plain two-stage loop, one block per tile -- any N % 128 == 0
+// Every other tile shape, K granule and stage count that was built lost on every ViT-B shape: DESIGN.md records them.
 // The MFMA computes the TRANSPOSED tile (W is the A operand, the activations the B operand) and MFMA row 4*fg + r of
 // n-tile j is mapped to weight row 16*fg + 4*j + r, so that every lane ends up with 16 CONSECUTIVE output columns of one
 // output row: the epilogue is 16-byte vector stores.  Operand tiles are staged with direct-to-LDS loads
 // (buffer_load_dwordx4 ... offen lds): one wave instruction writes 1 KiB = 8 tile rows linearly, so the XOR swizzle is applied
 // to the per-lane SOURCE offset.
 // Exact-form GELU, 0.5 v (1 + erf(v / sqrt 2)), with erfc from Abramowitz & Stegun 7.1.26 (|error| < 1.5e-7 in erf, two orders
-// below the fp16 rounding of the stored activation).  libm's erff costs ~35 VALU instructions per element, which made the
-// fc1 epilogue as long as its K loop; this form is 14.
-__device__ __forceinline__ float gelu_erf(float v) {
-    const float z = fabsf(v) * 0.70710678118654752f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
-    float p = fmaf(1.061405429f, t, -1.453152027f);
-    p = fmaf(p, t, 1.421413741f);
-    p = fmaf(p, t, -0.284496736f);
-    p = fmaf(p, t, 0.254829592f);
-    const float c = p * t * __builtin_amdgcn_exp2f(-1.4426950408889634f * z * z);      // erfc(z)
-    return 0.5f * v * (v < 0.f ? c : 2.0f - c);
-}
-
+// below the fp16 rounding of the stored activation; libm's erff costs ~35 VALU instructions per element, which made the
+// fc1 epilogue as long as its K loop).
 // Two elements at a time on the packed fp32 pipe (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32: two lanes of arithmetic per
-// instruction).  Same erfc polynomial; the sign select is folded away with |v| = sqrt(2) z:
+// instruction).  The sign select of erf is folded away with |v| = sqrt(2) z:
 //   0.5 v (1 + erf(v / sqrt 2)) = 0.5 v + 0.5 |v| (1 - erfc(z)) = 0.5 v + (z / sqrt 2) (1 - erfc(z))
 // (for v << 0 the two terms cancel to an absolute error of ~|v| 6e-8, three orders below the fp16 rounding of the row's other
-// activations).  13 packed + 3 scalar operations per pair against 19 scalar per element: the fc1 epilogue was VALU-bound.
+// activations).  13 packed + 3 scalar operations per pair against 19 scalar per element of the one-at-a-time form: the fc1 epilogue
+// was VALU-bound.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 gelu_erf2(f32x2 v) {
     f32x2 z;
@@ -157,29 +141,14 @@ extern "C" int ibl_gemm_stamps_clear() {
 #define GEMM_STAMP(k)
 #endif
 
-#ifdef IBL_GEMM_NOMFMA             // lab: the K loop without its MFMAs -- how fast does a CU stream the operand stages into LDS?
-#define IBL_MFMA(a, b, c, x, y, z) (c)
-#else
 #define IBL_MFMA(a, b, c, x, y, z) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, x, y, z)
-#endif
-#ifndef IBL_GEMM_L2AHEAD
-#define IBL_GEMM_L2AHEAD 0          // lab (-DIBL_GEMM_L2AHEAD=D): every workgroup requests its share of the activation panel's lines of K step
-                                    // kt + D into L2.  Measured per ViT-B layer: 1 034 us off, 1 073 / 1 089 / 1 088 us at D = 2 / 3 / 4 --
-                                    // the operand stream is not slow because it misses L2
-#endif
-#ifndef IBL_GEMM_RMW_PIPE
-#define IBL_GEMM_RMW_PIPE 1         // residual epilogue: the loads of a row group ahead of the previous group's stores (0: round 3's serial rounds)
-#endif
-#ifndef IBL_GEMM_TOUCH
-#define IBL_GEMM_TOUCH 0            // lab (-DIBL_GEMM_TOUCH=1): L2 touches of the next tile's first stages, one tile early.  Measured: the wait
-                                    // at the tile top 6.2 -> 4.9 k clocks, but the K step that carries the touches waits for them (K loop
-                                    // 37.2 -> 37.9 k, fc1 35.6 -> 38.5 k): encoder forward 15.65 -> 16.34 ms.  The first stages are not
-                                    // late because they miss L2: 112 KB at the ~21 B / clock a CU streams into LDS take 5 k clocks
-#endif
-template <int EPI, int MI, int WM, int WN, int BK, int OCC, int NS, bool PIPE = false>
-__global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* __restrict__ A, int64_t lda, const u16* __restrict__ W,
-                                                                  int64_t ldw, int M, int N, int K, GemmEpi epi) {
+
+template <int EPI, bool T256>
+__global__ __launch_bounds__(T256 ? 512 : 256, T256 ? 1 : 2) void ibl_gemm_f16_tn(const u16* __restrict__ A, int64_t lda, const u16* __restrict__ W,
+                                                                                int64_t ldw, int M, int N, int K, GemmEpi epi) {
 #if defined(__HIP_DEVICE_COMPILE__)          // the buffer-resource type and builtins exist in the device pass only
+    constexpr int MI = T256 ? 8 : 4, WM = 2, WN = T256 ? 4 : 2, BK = GBK, NS = 2;      // NS: LDS stages
+    constexpr bool PIPE = T256;              // the 256 x 256 shape is the pipelined, persistent one
     constexpr int BM = WM * MI * 16, BN = WN * 64, NW = WM * WN;
     constexpr int LDS_ROW = BK * 2;          // bytes per tile row, XOR-swizzled 16-byte chunks (no padding)
     constexpr int CPR = BK / 8, RPI = 64 / CPR;             // chunks per row; rows per 1 KiB wave instruction
@@ -202,7 +171,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
     constexpr bool GELU = EPI == EPI_BIAS_GELU_H16 || GT > 1;
     constexpr bool PAIR = EPI == EPI_BIAS_H16 || GELU;
     constexpr int PAIR_STORES = GT * 2 * MI;          // stores per lane of a full tile's fp16 epilogue
-#define KEYW(r) (NAT ? keyx_act<BK>(r) : (PAIR ? keyx_pair<BK>(r) : keyx_w<BK>(r)))
+#define KEYW(r) (NAT ? key_act(r) : (PAIR ? key_pair(r) : key_w(r)))
     const int nbn = N / BN;
     const int nbm = (M + BM - 1) / BM;
     const int nwg = nbn * nbm;
@@ -229,7 +198,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
             const int _rr = (wave + NW * _i) * RPI + lane / CPR, _pch = lane % CPR;                \
             int _ar = _rr;                                                                         \
             if (row0 + _ar >= M) _ar = M - 1 - row0;                                               \
-            a_off[_i] = (unsigned)(((int64_t)_ar * lda + ((_pch ^ keyx_act<BK>(_rr)) << 3)) * 2);  \
+            a_off[_i] = (unsigned)(((int64_t)_ar * lda + ((_pch ^ key_act(_rr)) << 3)) * 2);  \
         }                                                                                          \
         _Pragma("unroll") for (int _i = 0; _i < GW; ++_i) {                                        \
             const int _rr = (wave + NW * _i) * RPI + lane / CPR, _pch = lane % CPR;                \
@@ -237,15 +206,6 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
         }                                                                                          \
     } while (0)
     int tile = blockIdx.x;
-    if constexpr (PIPE) {
-        // Staggered start (residual epilogue only, set by the launcher): the workgroups of a persistent grid run in lockstep -- all K
-        // loops together (HBM nearly idle), then all fp32 read-modify-write epilogues together (HBM saturated at 5.8 TB/s, MFMA idle).
-        // Four phase groups, a quarter of a tile apart, spread the epilogue traffic over the whole launch.
-        if (epi.stagger > 0) {
-            const int ph = ((blockIdx.x >> 3) & 3) * epi.stagger;      // (blockIdx % 8 labels the XCD: every XCD gets all four phases)
-            for (int i = 0; i < ph; ++i) __builtin_amdgcn_s_sleep(64);
-        }
-    }
     GEMM_SET_TILE(tile);
 #define GEMM_GLDS(buf, kt)                                                                                              \
     do {                                                                                                                \
@@ -281,14 +241,11 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
                                                      16, w_off[(pc) >= GA ? (pc) - GA : 0], (unsigned)(_ko * 2), 0, 0);                     \
     } while (0)
 #define FRAG_W(buf, ks, j) (*reinterpret_cast<const h16x8*>(smem + (buf) * STAGE + A_BYTES + wrow[j] * LDS_ROW + (((4 * (ks) + fg) ^ KEYW(wrow[j])) << 4)))
-#define FRAG_A(buf, ks, i) (*reinterpret_cast<const h16x8*>(smem + (buf) * STAGE + arow[i] * LDS_ROW + (((4 * (ks) + fg) ^ keyx_act<BK>(arow[i])) << 4)))
+#define FRAG_A(buf, ks, i) (*reinterpret_cast<const h16x8*>(smem + (buf) * STAGE + arow[i] * LDS_ROW + (((4 * (ks) + fg) ^ key_act(arow[i])) << 4)))
     // The pipelined form is launched as a persistent grid (one workgroup per CU walks the tiles t, t + grid, ...): the next tile's
     // first stage is requested before the epilogue of the current one, so its latency hides under the stores.
-    static_assert(!PIPE || (BK == 64 && NS == 2 && MI % 2 == 0), "pipelined loop: BK 64, two stages");
-#ifndef IBL_GEMM_HA_DIV
-#define IBL_GEMM_HA_DIV 4
-#endif
-    constexpr int HA = MI / IBL_GEMM_HA_DIV, N2B = MI - HA;       // groups before / after the barrier in the second K half
+    static_assert(MI % 2 == 0, "pipelined loop: groups in halves");
+    constexpr int HA = MI / 4, N2B = MI - HA;                     // groups before / after the barrier in the second K half
     constexpr int NL = MI + 4;                                    // fragment reads per K half
     constexpr int LB = (NL + MI - 2) / (MI - 1);                  // set-B reads per phase-1 group (none after the last group)
     constexpr int LA = (NL + N2B - 2) / (N2B - 1);                // set-A reads per phase-2b group (none before the last group)
@@ -388,7 +345,8 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
         if (first_tile) GEMM_PROLOGUE();
         // fp16 epilogues: the 2 * MI stores of the previous (full) tile were issued AFTER this tile's first pieces, so "at most 2 * MI
         // operations outstanding" already means the pieces have landed (vmcnt retires in issue order): the stores drain under the first K
-        // step instead of in front of it (a raw barrier: __syncthreads() would add its own vmcnt(0) while LDS-DMA is pending)
+        // step instead of in front of it (a raw barrier: __syncthreads() would add its own vmcnt(0) while LDS-DMA is pending).  The count
+        // holds only while the compiler adds no scratch access of its own: the build fails if this kernel spills (csrc/Makefile)
         if (PAIR && stores_pending) {
             asm volatile("s_waitcnt vmcnt(%0)" ::"i"(PAIR_STORES) : "memory");
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -398,43 +356,8 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
             __syncthreads();
         }
         GEMM_STAMP(1);
-        if (IBL_GEMM_TOUCH && tile + (int)gridDim.x < nwg) {     // issued here, behind the tile-top wait and before the fragments exist:
-                                                                 // the K loop has no register to spare (two more live VGPRs spill its LDS addresses)
-            int _bid = tile + (int)gridDim.x;
-            const int _q = nwg / 8, _r = nwg % 8, _xcd = _bid % 8;
-            _bid = (_xcd < _r ? _xcd * (_q + 1) : _r * (_q + 1) + (_xcd - _r) * _q) + _bid / 8;
-            const int prow0 = (_bid / nbn) * BM, pcol0 = (_bid % nbn) * BN;
-            // (32-bit arithmetic on a freshly formed lane id: the K loop has no register to spare -- two more live VGPRs spill its
-            // LDS fragment addresses)
-            const int wv = __builtin_amdgcn_readfirstlane(wave);
-            const bool act = wv < NW / 2;
-            const unsigned ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-            unsigned r = (unsigned)((act ? prow0 : pcol0) + (wv % (NW / 2)) * 64) + ln;
-            if (act) r = r < (unsigned)M ? r : (unsigned)(M - 1);
-            const unsigned touch_off = r * (unsigned)((act ? lda : ldw) * 2);
-            const __amdgpu_buffer_rsrc_t t_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(act ? A : W), 0, -1, 0x00020000);
-            unsigned char* const tdst = smem + NS * STAGE + wave * 512;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(t_rsrc, (__attribute__((address_space(3))) void*)tdst, 4, touch_off, 0, 0, 0);
-            if (nk > 1)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(t_rsrc, (__attribute__((address_space(3))) void*)(tdst + 256), 4, touch_off, BK * 2, 0, 0);
-        }
         __builtin_amdgcn_sched_barrier(0);
-#if IBL_GEMM_L2AHEAD > 0
-        // (wave-uniform: SGPRs) which quarter(s) of the row panel this workgroup requests ahead; not on the last row of tiles (rows beyond M)
-        const bool l2ahead = row0 + BM <= M && nk > IBL_GEMM_L2AHEAD;
-        const int tcol = col0 / BN;
-        const bool l2two = nbn < 4;
-        const unsigned touch_row0 = (unsigned)((tcol & 3) * 64 * lda * 2);
-        const unsigned touch_row1 = (unsigned)(((tcol + nbn) & 3) * 64 * lda * 2);
-#endif
         h16x8 afA[MI], wfA[4], afB[MI], wfB[4];
-        // L2 touches for the NEXT tile of this block (round 4).  Per-tile stamps: from the request of a tile's first two operand stages to the
-        // start of its K loop pass ~14 k clocks whatever the epilogue in between does (shortening the fp16 epilogue by 1.5 k lengthened the
-        // wait at the tile top by 1.5 k; 32 instead of 256 active CUs change nothing): the 112 KB are first touches of a new row panel,
-        // L2 misses, and a CU sustains ~8.5 B / clock of those.  So the lines of those two stages are requested one tile EARLY, as 4-byte
-        // direct-to-LDS loads into a scratch area (no VGPR, no use of the data): one per lane and stage, waves 0 .. NW / 2 - 1 the rows of
-        // the activation tile, the others the rows of the weight tile; the pieces issued at the end of this tile then hit L2.
-        // (the offsets are formed where the touches are issued: nothing of this lives across the K loop)
 #pragma unroll
         for (int j = 0; j < 4; ++j) wfA[j] = FRAG_W(0, 0, j);
 #pragma unroll
@@ -463,33 +386,8 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
                 for (int j = 0; j < 4; ++j) acc[g][j] = IBL_MFMA(wfB[j], afB[g], acc[g][j], 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-#if IBL_GEMM_L2AHEAD > 0
-            // Cooperative L2 prefetch of the activation panel (round 4).  The K loop takes the same ~3 000 clocks per step WITHOUT its MFMAs
-            // (lab build -DIBL_GEMM_NOMFMA): it is bound by how fast a CU streams its 64 KB of operands into LDS, and the tiles that find
-            // their panel in L2 run at 1 300 clocks per step.  The nbn column tiles of a row panel run side by side on one XCD and all miss
-            // on the same activation lines at the same time.  So every workgroup requests a QUARTER of its row panel's lines of K step
-            // kt + IBL_GEMM_L2AHEAD now (4-byte direct-to-LDS loads into a scratch area: the offsets of piece 0 cover 64 rows, the quarter is
-            // chosen by the tile's column), as the LAST memory operation of the step: the wait below then lets exactly that one stay in
-            // flight (vmcnt retires in order), and it is the oldest operation when the next step waits.
-            if (l2ahead && kt + IBL_GEMM_L2AHEAD < nk) {
-                const unsigned ko2 = (unsigned)((kt + IBL_GEMM_L2AHEAD) * BK * 2);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(smem + NS * STAGE + wave * 512), 4, a_off[0],
-                                                         touch_row0 + ko2, 0, 0);
-                if (l2two) {
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(smem + NS * STAGE + wave * 512 + 256), 4,
-                                                             a_off[0], touch_row1 + ko2, 0, 0);
-                    asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-                } else {
-                    asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
-                }
-            } else {
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            }
-            __builtin_amdgcn_s_barrier();
-#else
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // this wave's pieces have landed, its set-B reads have returned
             __syncthreads();
-#endif
             // ---- phase 2b
             const int nb = buf ^ 1;
 #pragma unroll
@@ -508,23 +406,19 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
             }
         }
     } else {
-    // NS LDS stages: the loads of K steps 0 .. NS - 2 are in flight before the loop, step kt issues those of step kt + NS - 1, and the
-    // wait that closes a step lets the (NS - 2) youngest stages stay in flight (vmcnt counts LDS-DMA pieces in issue order)
+    // NS LDS stages: the loads of K steps 0 .. NS - 2 are in flight before the loop, step kt issues those of step kt + NS - 1
+    static_assert(NS == 2, "the vmcnt(0) that closes a step leaves no later stage in flight");
 #pragma unroll
     for (int st = 0; st < NS - 1; ++st)
         if (st < nk) GEMM_GLDS(st, st);
-    if (NS == 2 || nk < NS - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"i"((NS - 2) * NP) : "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     GEMM_STAMP(1);
     // One K step = 2 * MI groups of 4 MFMAs.  The GA + GW direct-to-LDS pieces of the NEXT tile are issued one at a time
     // between those groups: a piece blocks its wave's issue port for ~100 cycles, and eight of them back to back at the top
     // of the step (right after the barrier, in every wave at once) left the MFMA pipe idle for a third of the step.
-    constexpr int KS = BK / 32, NG = KS * MI;
-#ifndef IBL_GEMM_NGI_DIV
-#define IBL_GEMM_NGI_DIV 2
-#endif
-    constexpr int NGI = NG / IBL_GEMM_NGI_DIV;
+    constexpr int KS = BK / 32, NG = KS * MI;                      // K halves (one MFMA deep each), MFMA groups per step
+    constexpr int NGI = NG / 2;
     for (int kt = 0; kt < nk; ++kt) {
         const int buf = kt % NS;
         const bool more = kt + NS - 1 < nk;
@@ -539,7 +433,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
 #pragma unroll
             for (int j = 0; j < 4; ++j) wf[j] = *reinterpret_cast<const h16x8*>(pw + wrow[j] * LDS_ROW + ((ch ^ KEYW(wrow[j])) << 4));
 #pragma unroll
-            for (int i = 0; i < MI; ++i) af[i] = *reinterpret_cast<const h16x8*>(pa + arow[i] * LDS_ROW + ((ch ^ keyx_act<BK>(arow[i])) << 4));
+            for (int i = 0; i < MI; ++i) af[i] = *reinterpret_cast<const h16x8*>(pa + arow[i] * LDS_ROW + ((ch ^ key_act(arow[i])) << 4));
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
 #pragma unroll
@@ -561,16 +455,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
                 }
             }
         }
-        // stage kt + 1 has landed; the pieces of later steps (issued during this step and the ones before) may still be in flight
-        if (NS == 2) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
-            const int later = nk - 2 - kt;               // K steps after kt + 1 ...
-            if (later >= NS - 2) asm volatile("s_waitcnt vmcnt(%0)" ::"i"((NS - 2) * NP) : "memory");
-            else if (NS >= 4 && later == NS - 3) asm volatile("s_waitcnt vmcnt(%0)" ::"i"((NS >= 4 ? NS - 3 : 0) * NP) : "memory");
-            else if (NS >= 5 && later == NS - 4) asm volatile("s_waitcnt vmcnt(%0)" ::"i"((NS >= 5 ? NS - 4 : 0) * NP) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // stage kt + NS - 1 has landed
         __syncthreads();
     }
     }
@@ -605,11 +490,9 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
             b4[j] = epi.bias ? *reinterpret_cast<const float4*>(epi.bias + nbq + 16 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
             s4[j] = epi.scale ? *reinterpret_cast<const float4*>(epi.scale + nbq + 16 * j) : make_float4(1.f, 1.f, 1.f, 1.f);
         }
-#ifndef IBL_GEMM_EPI_BATCHED
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             asm volatile("" ::"v"(b4[j].x), "v"(b4[j].y), "v"(b4[j].z), "v"(b4[j].w), "v"(s4[j].x), "v"(s4[j].y), "v"(s4[j].z), "v"(s4[j].w));
-#endif
     }
     tile += gridDim.x;
     const bool has_next = PIPE && tile < nwg;
@@ -649,74 +532,6 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
     } else if (NAT) {
         // x[row][n] += scale[n] * (acc + bias[n]); lane (fr, fg) owns columns 16 j + 4 fg + 0..3 of n-tile j
         const int nb = ecol0 + wn * 64 + 4 * fg;
-#ifdef IBL_GEMM_EPI_BATCHED
-        // Round 4 (lab switch, measured SLOWER: proj 131 -> 147 us, fc2 298 -> 313 us -- the compiler folds the additions into the
-        // accumulators and keeps three loads in flight whatever the source order; 16 + 16 spills).  The read-modify-write used to run as eight dependent rounds (4 loads, wait, 4 stores per 16-row group -- and vmcnt counts
-        // stores too on gfx9, so every round also waited for the previous round's stores): ~16 exposed memory latencies, 34 k clocks per tile
-        // at K = 768 where the whole K loop is 35 k.  Now: the increments are formed in place in the accumulators (bias / scale registers
-        // die), then the 32 float4 of the residual tile are requested in three batches (12 + 12 + 8) with two batches always in flight,
-        // and a batch's stores are issued after the NEXT batch's loads: three exposed latencies.  (16 + 16 spilled: the K loop's
-        // 254 registers leave 96 beside the accumulators.)  The last row of tiles keeps the masked serial form.
-        {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float4 b4 = epi.bias ? *reinterpret_cast<const float4*>(epi.bias + nb + 16 * j) : make_float4(0.f, 0.f, 0.f, 0.f);
-                const float4 s4 = epi.scale ? *reinterpret_cast<const float4*>(epi.scale + nb + 16 * j) : make_float4(1.f, 1.f, 1.f, 1.f);
-#pragma unroll
-                for (int i = 0; i < MI; ++i) {
-                    acc[i][j][0] = (acc[i][j][0] + b4.x) * s4.x; acc[i][j][1] = (acc[i][j][1] + b4.y) * s4.y;
-                    acc[i][j][2] = (acc[i][j][2] + b4.z) * s4.z; acc[i][j][3] = (acc[i][j][3] + b4.w) * s4.w;
-                }
-            }
-        }
-        if (erow0 + BM <= M) {                                     // full tile (all but the last row of tiles): no row is clamped or masked
-            constexpr int B0 = MI == 8 ? 3 : 2, B1 = MI == 8 ? 3 : 2;  // 16-row groups of batch A, batch B; the rest is batch C (in A's registers)
-            float* const obase = reinterpret_cast<float*>(epi.out) + (int64_t)(erow0 + wm * (MI * 16) + fr) * epi.ldo + nb;
-            const int64_t gstride = 16 * epi.ldo;
-            float4 xa[B0][4], xb[B1][4];
-#pragma unroll
-            for (int i = 0; i < B0; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) xa[i][j] = *reinterpret_cast<const float4*>(obase + i * gstride + 16 * j);
-#pragma unroll
-            for (int i = 0; i < B1; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) xb[i][j] = *reinterpret_cast<const float4*>(obase + (B0 + i) * gstride + 16 * j);
-            __builtin_amdgcn_sched_barrier(0);
-#define RESID_STORE(X, I)                                                                                                           \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                                           \
-                *reinterpret_cast<float4*>(obase + (I) * gstride + 16 * j) = make_float4(X[j].x + acc[I][j][0], X[j].y + acc[I][j][1], \
-                                                                                         X[j].z + acc[I][j][2], X[j].w + acc[I][j][3]);
-#pragma unroll
-            for (int i = 0; i < B0; ++i) { RESID_STORE(xa[i], i) }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < MI - B0 - B1; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) xa[i][j] = *reinterpret_cast<const float4*>(obase + (B0 + B1 + i) * gstride + 16 * j);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < B1; ++i) { RESID_STORE(xb[i], B0 + i) }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < MI - B0 - B1; ++i) { RESID_STORE(xa[i], B0 + B1 + i) }
-        } else {
-#pragma unroll
-            for (int i = 0; i < MI; ++i) {
-                const int row = erow0 + wm * (MI * 16) + i * 16 + fr;
-                if (row >= M) continue;
-                float* orow = reinterpret_cast<float*>(epi.out) + (int64_t)row * epi.ldo + nb;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float4* o = reinterpret_cast<float4*>(orow + 16 * j);
-                    float4 x = *o;
-                    x.x += acc[i][j][0]; x.y += acc[i][j][1]; x.z += acc[i][j][2]; x.w += acc[i][j][3];
-                    *o = x;
-                }
-            }
-        }
-#undef RESID_STORE
-#else
         // (b4 / s4 were fetched before the next tile's pieces went out, above)
 #define RESID_RMW(X, I, PTR)                                                                                                        \
         _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                                             \
@@ -725,7 +540,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
             x.z += (acc[I][j][2] + b4[j].z) * s4[j].z; x.w += (acc[I][j][3] + b4[j].w) * s4[j].w;                                   \
             *reinterpret_cast<float4*>((PTR) + 16 * j) = x;                                                                         \
         }
-        if (IBL_GEMM_RMW_PIPE && erow0 + BM <= M) {
+        if (erow0 + BM <= M) {
             // Full tile: the read-modify-write of a 16-row group used to be 4 loads, wait, 4 stores -- and since vmcnt retires in order
             // and counts stores, the wait of group i + 1 also waited for the stores of group i: eight rounds of (store latency + load
             // latency), 38 k clocks of a proj tile's 85 k.  Now the loads of group i + 1 are issued BEFORE the stores of group i (two
@@ -733,7 +548,8 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
             //     L0 L1 | wait(4) S0 L2 | wait(8) S1 L3 | ... | wait(8) S6 | wait(4) S7
             // The memory operations and their waits are inline assembly: with loads AND stores pending the compiler treats vmcnt as
             // unordered and waits vmcnt(0) at every use (LLVM SIInsertWaitcnts: mixed pending events), which is the serial form again.
-            // No compiler-issued memory operation may sit between them (the kernel has no spills; bias / scale were consumed above).
+            // No compiler-issued memory operation may sit between them: bias / scale were consumed above, and the build fails if this
+            // kernel has a private segment, i.e. spills (csrc/Makefile, spill guard).
             float* const obase = reinterpret_cast<float*>(epi.out) + (int64_t)(erow0 + wm * (MI * 16) + fr) * epi.ldo + nb;
             const int64_t gstride = 16 * epi.ldo;
             f32x4 xa[4], xb[4];
@@ -790,7 +606,6 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
             }
         }
 #undef RESID_RMW
-#endif
     } else if (PAIR) {
         const int nb = ecol0 + wn * 64 + 8 * fg;
 #define PAIR_STORE(I, OROW)                                                                                                         \
@@ -833,16 +648,14 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
             }
         }
 #undef PAIR_STORE
-    } else {
+    } else {                                           // EPI_PATCH_F32, EPI_BIAS_F32
     const int n0 = ecol0 + wn * 64 + 16 * fg;          // first of this lane's 16 consecutive columns
-    float bias[16], scale[16];
+    float bias[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f), s4 = make_float4(1.f, 1.f, 1.f, 1.f);
+        float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (epi.bias) b4 = *reinterpret_cast<const float4*>(epi.bias + n0 + 4 * q);
-        if (EPI == EPI_RESID_F32 && epi.scale) s4 = *reinterpret_cast<const float4*>(epi.scale + n0 + 4 * q);
         bias[4 * q] = b4.x; bias[4 * q + 1] = b4.y; bias[4 * q + 2] = b4.z; bias[4 * q + 3] = b4.w;
-        scale[4 * q] = s4.x; scale[4 * q + 1] = s4.y; scale[4 * q + 2] = s4.z; scale[4 * q + 3] = s4.w;
     }
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
@@ -853,42 +666,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[4 * j + r] = acc[i][j][r] + bias[4 * j + r];
-        if (PAIR) {
-            if (GELU) {
-#pragma unroll
-                for (int t = 0; t < 16; ++t) v[t] = gelu_erf(v[t]);
-            }
-            unsigned int pk[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) pk[t] = (unsigned int)f2h(v[2 * t]) | ((unsigned int)f2h(v[2 * t + 1]) << 16);
-            uint4* o = reinterpret_cast<uint4*>(reinterpret_cast<u16*>(epi.out) + (int64_t)row * epi.ldo + n0);
-            o[0] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-            o[1] = make_uint4(pk[4], pk[5], pk[6], pk[7]);
-            if (GT > 1) {
-                unsigned int lk[8], sk[8];
-#pragma unroll
-                for (int t = 0; t < 8; ++t) {
-                    const float h0 = h2f((u16)(pk[t] & 0xFFFFu)), h1 = h2f((u16)(pk[t] >> 16));
-                    sk[t] = (unsigned int)f2h(h0 * (1.0f / IBL_VIT_SPLIT_SCALE)) | ((unsigned int)f2h(h1 * (1.0f / IBL_VIT_SPLIT_SCALE)) << 16);
-                    lk[t] = (unsigned int)f2h((v[2 * t] - h0) * IBL_VIT_SPLIT_SCALE) | ((unsigned int)f2h((v[2 * t + 1] - h1) * IBL_VIT_SPLIT_SCALE) << 16);
-                }
-                if (GT == 3) {
-                    o[N / 8] = make_uint4(lk[0], lk[1], lk[2], lk[3]);
-                    o[N / 8 + 1] = make_uint4(lk[4], lk[5], lk[6], lk[7]);
-                }
-                o[(GT - 1) * (N / 8)] = make_uint4(sk[0], sk[1], sk[2], sk[3]);
-                o[(GT - 1) * (N / 8) + 1] = make_uint4(sk[4], sk[5], sk[6], sk[7]);
-            }
-        } else if (EPI == EPI_RESID_F32) {
-            float4* o = reinterpret_cast<float4*>(reinterpret_cast<float*>(epi.out) + (int64_t)row * epi.ldo + n0);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float4 x = o[q];
-                x.x += v[4 * q] * scale[4 * q]; x.y += v[4 * q + 1] * scale[4 * q + 1];
-                x.z += v[4 * q + 2] * scale[4 * q + 2]; x.w += v[4 * q + 3] * scale[4 * q + 3];
-                o[q] = x;
-            }
-        } else if (EPI == EPI_PATCH_F32) {
+        if (EPI == EPI_PATCH_F32) {
             const int b = row / epi.patches_per_crop, p = row - b * epi.patches_per_crop;
             const int64_t orow = (int64_t)b * epi.tokens_per_crop + 1 + p;
             float4* o = reinterpret_cast<float4*>(reinterpret_cast<float*>(epi.out) + orow * epi.ldo + n0);
@@ -932,11 +710,11 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void ibl_gemm_f16_tn(const u16* 
 #endif
 }
 
-template <int EPI, int MI, int WM, int WN, int BK, int OCC, int NS, bool PIPE = false>
+template <int EPI, bool T256>
 static int launch_gemm_cfg(const u16* A, int64_t lda, const u16* W, int64_t ldw, int M, int N, int K, const GemmEpi& epi, hipStream_t s) {
-    constexpr int BM = WM * MI * 16, BN = WN * 64;
+    constexpr int BM = T256 ? 256 : 128, BN = BM;
     const int nwg = (N / BN) * ((M + BM - 1) / BM);
-    const size_t lds = NS * (size_t)(BM + BN) * BK * 2 + (PIPE ? (size_t)WM * WN * 512 : 0);     // (+ the landing area of the L2 touches, 512 B per wave)
+    const size_t lds = 2 * (size_t)(BM + BN) * GBK * 2;          // two stages (NS) of fp16 operand tiles
     // the dynamic-LDS limit is a per-device property of the function: set once per device of this process.  The bit mask is only
     // a cache -- two threads racing here both set the same value (localise_concurrent lanes launch from several host threads)
     static std::atomic<unsigned long long> attr_set{0};
@@ -944,15 +722,12 @@ static int launch_gemm_cfg(const u16* A, int64_t lda, const u16* W, int64_t ldw,
     IBL_HIP_CHECK(hipGetDevice(&dev));
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        IBL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ibl_gemm_f16_tn<EPI, MI, WM, WN, BK, OCC, NS, PIPE>),
+        IBL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ibl_gemm_f16_tn<EPI, T256>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set.fetch_or(bit, std::memory_order_release);
     }
     int grid = nwg;
-#ifndef IBL_GEMM_PERSIST
-#define IBL_GEMM_PERSIST 1
-#endif
-    if (PIPE && IBL_GEMM_PERSIST) {          // persistent: one workgroup per CU (a multiple of 8, see GEMM_SET_TILE)
+    if (T256) {                              // persistent: one workgroup per CU (a multiple of 8, see GEMM_SET_TILE)
         static std::atomic<int> n_cu{0};
         int cus = n_cu.load(std::memory_order_relaxed);
         if (cus == 0) {
@@ -960,43 +735,14 @@ static int launch_gemm_cfg(const u16* A, int64_t lda, const u16* W, int64_t ldw,
             cus = cus >= 8 ? cus / 8 * 8 : 8;
             n_cu.store(cus, std::memory_order_relaxed);
         }
-        if (grid > cus * OCC) grid = cus * OCC;
-        static int cap = -2;                 // lab: IBL_GEMM_MAXGRID caps the persistent grid (is a per-tile phase bound by the chip or by the CU?)
-        if (cap == -2) { const char* e = getenv("IBL_GEMM_MAXGRID"); cap = e ? atoi(e) : 0; }
-        if (cap > 0 && grid > cap) grid = cap;
-    }
-    GemmEpi e2 = epi;
-    if (PIPE && grid < nwg) {
-        // lab only (IBL_GEMM_STAGGER = s_sleep(64) units per phase group): measured and rejected in round 3 -- proj 125 / 142 / 155 / 171 us
-        // and fc2 304 / 311 / 322 / 341 us at 0 / 3 / 6 / 10: the epilogue is not slowed by the other workgroups' epilogues, the delay is
-        // pure tail
-        static int stag = -2;
-        if (stag == -2) { const char* e = getenv("IBL_GEMM_STAGGER"); stag = e ? atoi(e) : 0; }
-        e2.stagger = stag;
+        if (grid > cus) grid = cus;
     }
     void* tok;
     ibl_prof_begin(IBL_PROF_GEMM, 2.0 * (double)M * (double)N * (double)(epi.algo_k < 0 ? 0 : (epi.algo_k ? epi.algo_k : K)), s, &tok);
-    hipLaunchKernelGGL((ibl_gemm_f16_tn<EPI, MI, WM, WN, BK, OCC, NS, PIPE>), dim3(grid), dim3(WM * WN * 64), lds, s, A, lda, W, ldw, M, N, K, e2);
+    hipLaunchKernelGGL((ibl_gemm_f16_tn<EPI, T256>), dim3(grid), dim3(T256 ? 512 : 256), lds, s, A, lda, W, ldw, M, N, K, epi);
     ibl_prof_end(tok, s);
     IBL_LAUNCH_CHECK();
     return IBL_OK;
-}
-
-// Tile configurations (IBL_GEMM_CFG overrides the choice; the lab build -DIBL_GEMM_LAB adds the variants measured and rejected):
-//   8  256 x 256, BK 64, 8 waves, 128 KiB LDS, software-pipelined K loop, persistent grid      (default for N % 256 == 0, M >= 4096)
-//   0  256 x 256, BK 64, 8 waves, 128 KiB LDS, plain K loop, one block per tile
-//   1  128 x 128, BK 64, 4 waves,  64 KiB LDS, 2 blocks / CU  (any N % 128 == 0, small M)
-//   2  256 x 128, BK 32, 4 waves,  48 KiB LDS, 2 blocks / CU  (the epilogue of one block overlaps the K loop of the other)
-//   3  256 x 256, BK 32, 8 waves, 4 LDS stages = 128 KiB      (loads two K steps ahead, no full drain at the step boundary)
-// Measured on the four ViT-B/14 layer shapes (57 568 rows), TFLOP/s per layer, one process: 8: 783, 8 without the persistent
-// grid: 775, 0: 745, 3: 649, 2: 632, 1: 629; lab: 256 x 128 BK 32 three stages 643, 128 x 256 BK 32 639, 128 x 128 pipelined 620.
-static int gemm_cfg_override() {
-    static int v = -2;
-    if (v == -2) {
-        const char* e = getenv("IBL_GEMM_CFG");
-        v = e ? atoi(e) : -1;
-    }
-    return v;
 }
 
 // EPI_RESID_PRE_F32 (residual tile preloaded into the accumulators, store-only epilogue) is a lab switch: measured per tile with
@@ -1016,25 +762,9 @@ static int launch_gemm(const u16* A, int64_t lda, const u16* W, int64_t ldw, int
     if (M <= 0) return IBL_OK;
     if (N % 128 != 0 || K % GBK != 0)
         return ibl_set_error(IBL_ERR_ARG, "gemm: N (%d) must be a multiple of 128 and K (%d) of 64", N, K);
-    int cfg = (N % 256 == 0 && M >= 4096) ? 8 : 1;
-    const int ov = gemm_cfg_override();
-    if (ov == 1 || ov == 2 || ((ov == 0 || ov == 3 || ov == 8) && N % 256 == 0)) cfg = ov;
-#ifdef IBL_GEMM_LAB
-    if (ov == 4 || ov == 6 || ov == 7 || ov == 9 || (ov == 5 && N % 256 == 0)) cfg = ov;
-    if (cfg == 9) return launch_gemm_cfg<EPI, 4, 2, 2, 64, 2, 2, true>(A, lda, W, ldw, M, N, K, epi, s);
-    if (cfg == 4) return launch_gemm_cfg<EPI, 8, 2, 2, 32, 2, 3>(A, lda, W, ldw, M, N, K, epi, s);
-    if (cfg == 5) return launch_gemm_cfg<EPI, 4, 2, 4, 32, 4, 3>(A, lda, W, ldw, M, N, K, epi, s);
-    if (cfg == 6) return launch_gemm_cfg<EPI, 4, 2, 2, 32, 2, 4>(A, lda, W, ldw, M, N, K, epi, s);
-    if (cfg == 7) return launch_gemm_cfg<EPI, 4, 2, 2, 32, 3, 3>(A, lda, W, ldw, M, N, K, epi, s);
-#endif
-#ifdef IBL_GEMM_FORCE128
-    cfg = 1;
-#endif
-    if (cfg == 8) return launch_gemm_cfg<EPI, 8, 2, 4, 64, 1, 2, true>(A, lda, W, ldw, M, N, K, epi, s);
-    if (cfg == 0) return launch_gemm_cfg<EPI, 8, 2, 4, 64, 1, 2>(A, lda, W, ldw, M, N, K, epi, s);
-    if (cfg == 2) return launch_gemm_cfg<EPI, 8, 2, 2, 32, 2, 2>(A, lda, W, ldw, M, N, K, epi, s);
-    if (cfg == 3) return launch_gemm_cfg<EPI, 8, 2, 4, 32, 1, 4>(A, lda, W, ldw, M, N, K, epi, s);
-    return launch_gemm_cfg<EPI, 4, 2, 2, 64, 2, 2>(A, lda, W, ldw, M, N, K, epi, s);
+    // the 256 x 256 shape where it divides N and M is large, else 128 x 128
+    if (N % 256 == 0 && M >= 4096) return launch_gemm_cfg<EPI, true>(A, lda, W, ldw, M, N, K, epi, s);
+    return launch_gemm_cfg<EPI, false>(A, lda, W, ldw, M, N, K, epi, s);
 }
 
 // ------------------------------------------------------------------------------------------------
