@@ -1,6 +1,6 @@
 // reg_api.hip -- C-ABI entry points of the registration path: context (device arena), batched
-// radius-outlier removal and normals + FPFH.  The fused register / evaluate drivers live in
-// reg_register.hip.
+// radius-outlier removal and normals + FPFH.  The fused register driver lives in reg_register.hip (its stages in
+// reg_match.hip, reg_ransac.hip, reg_icp.hip), the evaluation against the whole memory in reg_eval.hip.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 

@@ -130,6 +130,12 @@ int ibl_feat_search_mfma(ibl_reg_ctx* ctx, const FeatPair* d_pairs, int n_pairs,
                          float* pair_d2, const int* need_pos, const int* need_list, int out0, int64_t out_count, bool* overflow,
                          hipStream_t s);
 
+// reg_api.hip: normals (radius 2 voxel, 30 nn) and FPFH (5 voxel, 100 nn) of every cloud of a batch, colour gradients (grad_radius,
+// 30 nn) of the points [gq0, gq1)
+int ibl_features_on_batch(ibl_reg_ctx* ctx, const float4* P, const int* seg_off_dev, const int* seg_off_host, int n_seg, const float* bbox_host, double voxel_size,
+                          double grad_radius, int gq0, int gq1, float4* normals, float* fpfh, unsigned short* fpfh_split, float* fpfh_norm,
+                          float4* grad, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------------
 // device helpers
 // ------------------------------------------------------------------------------------------------

@@ -1,0 +1,284 @@
+// reg_eval.hip -- scoring of registration results against the whole memory: a hash grid over the concatenation of all memory
+// clouds (ibl_memgrid) and the fitness / rmse of every job's transformed detected points against it.
+//
+// Replaces, for a whole batch of (frame, assignment) jobs at once,
+//   utils/fpfh_register.py:145-150            evaluate_transform against the concatenation of all memory clouds
+#pragma clang fp contract(off)
+#include <hip/hip_runtime.h>
+
+#include <memory>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "ibloc.h"
+#include "reg_common.h"
+#include "reg_stages.h"
+
+// ------------------------------------------------------------------------------------------------
+// whole-memory hash grid + evaluate_registration
+// ------------------------------------------------------------------------------------------------
+struct ibl_memgrid {
+    float cell, inv;
+    int64_t n;
+    int n_cells;
+    unsigned long long hmask;
+    float4* sorted;                 // points in cell order
+    unsigned long long* ukeys;      // unique cell keys
+    int* ustart;                    // [n_cells + 1]
+    unsigned long long* tkeys;      // hash table keys (EMPTY = ~0)
+    int* tvals;                     // cell index
+};
+
+#define MG_EMPTY 0xFFFFFFFFFFFFFFFFull
+__device__ __forceinline__ unsigned long long mg_key(int ix, int iy, int iz) {
+    return ((unsigned long long)(unsigned)(ix + (1 << 20)) << 42) | ((unsigned long long)(unsigned)(iy + (1 << 20)) << 21) |
+           (unsigned long long)(unsigned)(iz + (1 << 20));
+}
+__device__ __forceinline__ unsigned long long mg_hash(unsigned long long k) {
+    k ^= k >> 33; k *= 0xFF51AFD7ED558CCDull; k ^= k >> 33; k *= 0xC4CEB9FE1A85EC53ull; k ^= k >> 33;
+    return k;
+}
+
+__global__ __launch_bounds__(256) void ibl_mg_key_kernel(const float4* __restrict__ pts, int64_t n, float inv, unsigned long long* __restrict__ keys,
+                                                         int* __restrict__ vals) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = pts[i];
+    keys[i] = mg_key((int)floorf(p.x * inv), (int)floorf(p.y * inv), (int)floorf(p.z * inv));
+    vals[i] = (int)i;
+}
+
+__global__ __launch_bounds__(256) void ibl_mg_heads_kernel(const unsigned long long* __restrict__ skeys, int64_t n, int* __restrict__ head) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    head[i] = (i == 0 || skeys[i] != skeys[i - 1]) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void ibl_mg_cells_kernel(const unsigned long long* __restrict__ skeys, const int* __restrict__ head,
+                                                           const int* __restrict__ head_scan, const int* __restrict__ order,
+                                                           const float4* __restrict__ pts, int64_t n, unsigned long long* __restrict__ ukeys,
+                                                           int* __restrict__ ustart, float4* __restrict__ sorted) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    sorted[i] = pts[order[i]];
+    if (head[i]) { const int c = head_scan[i]; ukeys[c] = skeys[i]; ustart[c] = (int)i; }
+}
+
+__global__ __launch_bounds__(256) void ibl_mg_insert_kernel(const unsigned long long* __restrict__ ukeys, int n_cells, unsigned long long hmask,
+                                                            unsigned long long* __restrict__ tkeys, int* __restrict__ tvals) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n_cells) return;
+    const unsigned long long k = ukeys[c];
+    unsigned long long h = mg_hash(k) & hmask;
+    while (true) {
+        const unsigned long long prev = atomicCAS(&tkeys[h], MG_EMPTY, k);
+        if (prev == MG_EMPTY) { tvals[h] = c; return; }
+        h = (h + 1) & hmask;
+    }
+}
+
+extern "C" int ibl_memgrid_build(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, ibl_memgrid** out, void* stream) {
+    if (!ctx || !mem_pts4 || !out || n <= 0 || n > 0x7FFFFFF0ll || cell <= 0) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_build: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    std::unique_ptr<ibl_memgrid> owner(new ibl_memgrid());      // freed on every error return below
+    ibl_memgrid* g = owner.get();
+    g->cell = (float)cell; g->inv = 1.0f / (float)cell; g->n = n;
+    const float4* P = reinterpret_cast<const float4*>(mem_pts4);
+    // persistent part (stays allocated in the arena until the context is destroyed)
+    IBL_ARENA(g->sorted, float4, n + 1);
+    IBL_ARENA(g->ukeys, unsigned long long, n + 1);
+    IBL_ARENA(g->ustart, int, n + 2);
+    {
+        ArenaMark scratch(ctx);
+        unsigned long long *keys, *skeys; int *vals, *order, *head, *hscan; unsigned char* tmp;
+        IBL_ARENA(keys, unsigned long long, n);
+        IBL_ARENA(skeys, unsigned long long, n);
+        IBL_ARENA(vals, int, n);
+        IBL_ARENA(order, int, n);
+        IBL_ARENA(head, int, n + 1);
+        IBL_ARENA(hscan, int, n + 1);
+        const unsigned nb = (unsigned)((n + 255) / 256);
+        hipLaunchKernelGGL(ibl_mg_key_kernel, dim3(nb), dim3(256), 0, s, P, n, g->inv, keys, vals);
+        IBL_LAUNCH_CHECK();
+        size_t t1 = 0, t2 = 0;
+        IBL_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, keys, skeys, vals, order, (int)n, 0, 63, s));
+        IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, head, hscan, (int)n, s));
+        IBL_ARENA(tmp, unsigned char, (int64_t)std::max(t1, t2) + 256);
+        IBL_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, t1, keys, skeys, vals, order, (int)n, 0, 63, s));
+        hipLaunchKernelGGL(ibl_mg_heads_kernel, dim3(nb), dim3(256), 0, s, skeys, n, head);
+        IBL_LAUNCH_CHECK();
+        IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, t2, head, hscan, (int)n, s));
+        hipLaunchKernelGGL(ibl_mg_cells_kernel, dim3(nb), dim3(256), 0, s, skeys, head, hscan, order, P, n, g->ukeys, g->ustart, g->sorted);
+        IBL_LAUNCH_CHECK();
+        int last_scan = 0, last_head = 0;
+        IBL_HIP_CHECK(hipMemcpyAsync(&last_scan, hscan + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+        IBL_HIP_CHECK(hipMemcpyAsync(&last_head, head + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+        IBL_HIP_CHECK(hipStreamSynchronize(s));
+        g->n_cells = last_scan + last_head;
+        const int nn = (int)n;
+        IBL_HIP_CHECK(hipMemcpyAsync(g->ustart + g->n_cells, &nn, sizeof(int), hipMemcpyHostToDevice, s));
+        IBL_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    // The table is dimensioned from the OCCUPIED CELLS, now that they are counted (round 4): it used to hold 2 n slots -- 128 M slots = 1.5 GB
+    // for a 10 000-instance memory whose 50 M surface points occupy a few million 4 cm cells -- so that every probe of the evaluation was
+    // a first touch of HBM (1.9 GB moved per launch for 158 MB of points).  At <= 1 / 3 load the table of the same memory is ~100 MB: it stays
+    // in the Infinity Cache, and a miss walks 1.5 slots on average.  Same cells, same points, same minima.
+    unsigned long long H = 1024;
+    while (H < (unsigned long long)g->n_cells * 3) H <<= 1;
+    g->hmask = H - 1;
+    IBL_ARENA(g->tkeys, unsigned long long, (int64_t)H);
+    IBL_ARENA(g->tvals, int, (int64_t)H);
+    IBL_HIP_CHECK(hipMemsetAsync(g->tkeys, 0xFF, sizeof(unsigned long long) * H, s));
+    hipLaunchKernelGGL(ibl_mg_insert_kernel, dim3((g->n_cells + 255) / 256), dim3(256), 0, s, g->ukeys, g->n_cells, g->hmask, g->tkeys, g->tvals);
+    IBL_LAUNCH_CHECK();
+    IBL_HIP_CHECK(hipStreamSynchronize(s));
+    *out = owner.release();
+    return IBL_OK;
+}
+
+extern "C" int ibl_memgrid_destroy(ibl_memgrid* g) {
+    delete g;       // device memory belongs to the context arena
+    return IBL_OK;
+}
+
+struct EvalJob {
+    double T[12];
+    int begin, end;      // detected point range (all cleaned detected clouds of the job's frame)
+    long long out;       // offset of this job's per-point distances (ibl_evaluate_points)
+};
+
+// grid (ICP_BPJ, J): fitness / rmse partials of evaluate_registration against the whole memory
+__global__ __launch_bounds__(256) void ibl_evaluate_kernel(ibl_memgrid g, const float4* __restrict__ det, const EvalJob* __restrict__ jobs,
+                                                           float thr, float thr2, double* __restrict__ partial /* [J][BPJ][2] */,
+                                                           float* __restrict__ d2_out /* per (job, point) or null */, int prune) {
+    const int j = blockIdx.y;
+    const EvalJob job = jobs[j];
+    double cnt = 0, err2 = 0;
+    for (int i = job.begin + blockIdx.x * 256 + threadIdx.x; i < job.end; i += ICP_BPJ * 256) {
+        const float4 s4 = det[i];
+        double p[3];
+        xform_d(job.T, s4.x, s4.y, s4.z, p);
+        const float qx = (float)p[0], qy = (float)p[1], qz = (float)p[2];
+        float best = thr2;
+        bool found = false;
+        const int x0 = (int)floorf((qx - thr) * g.inv), x1 = (int)floorf((qx + thr) * g.inv);
+        const int y0 = (int)floorf((qy - thr) * g.inv), y1 = (int)floorf((qy + thr) * g.inv);
+        const int z0 = (int)floorf((qz - thr) * g.inv), z1 = (int)floorf((qz + thr) * g.inv);
+        // The query's own cell first, then the (up to seven) others of its +-thr box only while they can still hold a closer point:
+        // a neighbouring cell lies behind the face it shares with the own cell, so the distance to that face (per axis that differs) bounds
+        // every point of it from below.  Round 4: an inlier's nearest point is millimetres away and the faces are centimetres away, so ~1.5
+        // instead of 8 cells are looked up and read (1.6 of the 1.9 GB a launch moved were the points of those cells).  The bound is
+        // conservative -- the slack covers the rounding of floorf(x * inv) against the geometric face, which grows with the coordinate -- and
+        // a cell is skipped only when its bound already reaches the best: the minimum is that of the full scan.
+        const int hx = (int)floorf(qx * g.inv), hy = (int)floorf(qy * g.inv), hz = (int)floorf(qz * g.inv);
+        auto scan_cell = [&](int ix, int iy, int iz) {
+            const unsigned long long k = mg_key(ix, iy, iz);
+            unsigned long long h = mg_hash(k) & g.hmask;
+            int c = -1;
+            while (true) {
+                const unsigned long long tk = g.tkeys[h];
+                if (tk == k) { c = g.tvals[h]; break; }
+                if (tk == MG_EMPTY) break;
+                h = (h + 1) & g.hmask;
+            }
+            if (c < 0) return;
+            const int b = g.ustart[c], e = g.ustart[c + 1];
+            for (int t = b; t < e; t += 4) {           // four points in flight (past the end: the last point again -- a repeat changes no minimum)
+                float4 m[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) m[u] = g.sorted[min(t + u, e - 1)];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float d2 = dist2f(qx, qy, qz, m[u].x, m[u].y, m[u].z);
+                    if (d2 < best) { best = d2; found = true; }
+                }
+            }
+        };
+        auto face_gap = [&](int i, int hcell, float q) {   // distance from q to the face between its own cell and cell i on this axis (0: same cell)
+            if (i == hcell) return 0.0f;
+            const float face = (float)(i < hcell ? hcell : hcell + 1) * g.cell;
+            return fmaxf(fabsf(q - face) - (1e-3f * g.cell + 5e-7f * fabsf(face)), 0.0f);
+        };
+        scan_cell(hx, hy, hz);
+        for (int ix = x0; ix <= x1; ++ix) {
+            const float gx = face_gap(ix, hx, qx);
+            for (int iy = y0; iy <= y1; ++iy) {
+                const float gy = face_gap(iy, hy, qy);
+                for (int iz = z0; iz <= z1; ++iz) {
+                    if (ix == hx && iy == hy && iz == hz) continue;
+                    const float gz = face_gap(iz, hz, qz);
+                    if (prune && gx * gx + gy * gy + gz * gz >= best) continue;
+                    scan_cell(ix, iy, iz);
+                }
+            }
+        }
+        if (found) { cnt += 1.0; err2 += (double)best; }
+        if (d2_out) d2_out[job.out + (i - job.begin)] = found ? best : INFINITY;
+    }
+    __shared__ double sh[2][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    cnt = wave_sum_d(cnt); err2 = wave_sum_d(err2);
+    if (lane == 0) { sh[0][wave] = cnt; sh[1][wave] = err2; }
+    __syncthreads();
+    if (threadIdx.x < 2)
+        partial[((int64_t)j * ICP_BPJ + blockIdx.x) * 2 + threadIdx.x] =
+            ((sh[threadIdx.x][0] + sh[threadIdx.x][1]) + sh[threadIdx.x][2]) + sh[threadIdx.x][3];
+}
+
+static int evaluate_impl(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float* det_pts4, const int32_t* job_begin, const int32_t* job_end,
+                         const double* T_global, int n_jobs, double threshold, double* rmse_out, double* fitness_out, float* d2_out, void* stream);
+
+extern "C" int ibl_evaluate_batch(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float* det_pts4, const int32_t* job_begin,
+                                  const int32_t* job_end, const double* T_global, int n_jobs, double threshold, double* rmse_out,
+                                  double* fitness_out, void* stream) {
+    return evaluate_impl(ctx, grid, det_pts4, job_begin, job_end, T_global, n_jobs, threshold, rmse_out, fitness_out, nullptr, stream);
+}
+
+extern "C" int ibl_evaluate_points(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float* det_pts4, const int32_t* job_begin,
+                                   const int32_t* job_end, const double* T_global, int n_jobs, double threshold, float* d2_out,
+                                   double* rmse_out, double* fitness_out, void* stream) {
+    if (!d2_out) return ibl_set_error(IBL_ERR_ARG, "ibl_evaluate_points: d2_out is null");
+    return evaluate_impl(ctx, grid, det_pts4, job_begin, job_end, T_global, n_jobs, threshold, rmse_out, fitness_out, d2_out, stream);
+}
+
+static int evaluate_impl(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float* det_pts4, const int32_t* job_begin, const int32_t* job_end,
+                         const double* T_global, int n_jobs, double threshold, double* rmse_out, double* fitness_out, float* d2_out, void* stream) {
+    if (!ctx || !grid || !det_pts4 || !job_begin || !job_end || !T_global || !rmse_out || !fitness_out || n_jobs <= 0 || threshold <= 0)
+        return ibl_set_error(IBL_ERR_ARG, "ibl_evaluate_batch: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    ArenaMark mark(ctx);
+    const int J = n_jobs;
+    std::vector<EvalJob> jobs(J);
+    for (int j = 0; j < J; ++j) {
+        for (int t = 0; t < 12; ++t) jobs[j].T[t] = T_global[16 * j + t];
+        jobs[j].begin = job_begin[j]; jobs[j].end = job_end[j];
+        if (job_end[j] < job_begin[j]) return ibl_set_error(IBL_ERR_ARG, "ibl_evaluate_batch: bad point range");
+        jobs[j].out = j == 0 ? 0 : jobs[j - 1].out + (jobs[j - 1].end - jobs[j - 1].begin);
+    }
+    EvalJob* d_jobs; double* partial;
+    IBL_ARENA(d_jobs, EvalJob, J);
+    IBL_ARENA(partial, double, (int64_t)J * ICP_BPJ * 2);
+    IBL_HIP_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(EvalJob) * J, hipMemcpyHostToDevice, s));
+    const char* efs = getenv("IBL_EVAL_FULLSCAN");          // diagnostics: 1 = every cell of the query's box (the tests compare both)
+    const int prune = !(efs && atoi(efs));
+    void* tok;
+    ibl_prof_begin(IBL_PROF_ST_EVAL, 24.0 * (double)(jobs[J - 1].out + (jobs[J - 1].end - jobs[J - 1].begin)), s, &tok);
+    hipLaunchKernelGGL(ibl_evaluate_kernel, dim3(ICP_BPJ, J), dim3(256), 0, s, *grid, reinterpret_cast<const float4*>(det_pts4), d_jobs,
+                       (float)threshold, (float)(threshold * threshold), partial, d2_out, prune);
+    ibl_prof_end(tok, s);
+    IBL_LAUNCH_CHECK();
+    std::vector<double> h((size_t)J * ICP_BPJ * 2);
+    IBL_HIP_CHECK(hipMemcpyAsync(h.data(), partial, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
+    IBL_HIP_CHECK(hipStreamSynchronize(s));
+    for (int j = 0; j < J; ++j) {
+        double cnt = 0, err2 = 0;
+        for (int b = 0; b < ICP_BPJ; ++b) { cnt += h[((size_t)j * ICP_BPJ + b) * 2]; err2 += h[((size_t)j * ICP_BPJ + b) * 2 + 1]; }
+        const int ns = job_end[j] - job_begin[j];
+        fitness_out[j] = ns > 0 ? cnt / (double)ns : 0.0;
+        rmse_out[j] = cnt > 0 ? std::sqrt(err2 / cnt) : 0.0;
+    }
+    return IBL_OK;
+}

@@ -1704,7 +1704,7 @@ __global__ __launch_bounds__(256) void ibl_knn_query_kernel(BatchGrid g, const f
     hybrid_select(g, g.seg[s], q, qi, radius, r2, max_nn, &lds[threadIdx.x >> 6], cons, status);
 }
 
-// Position of histogram bin b in the "matching order" of the feature search (reg_register.hip, oracle_reg.c FEAT_ORDER: the
+// Position of histogram bin b in the "matching order" of the feature search (reg_match.hip, oracle_reg.c FEAT_ORDER: the
 // three histograms from their centre bins outwards, interleaved).  Instance features are stored in that order so that the
 // search reads the terms of its early-abandon chain contiguously.
 __constant__ int FEAT_POS[33] = {29, 23, 17, 11, 5, 2, 8, 14, 20, 26, 32, 27, 21, 15, 9, 3, 0, 6, 12, 18, 24, 30, 28, 22, 16, 10, 4, 1, 7, 13, 19, 25, 31};
