@@ -177,6 +177,30 @@ enum { IBL_LINEAR_F16 = 0, IBL_LINEAR_GELU_F16 = 1, IBL_LINEAR_RESID_F32 = 2, IB
 int ibl_linear_f16(const void* x, int64_t ldx, const void* W, int64_t ldw, const float* bias, const float* scale,
                     int64_t rows, int n_out, int n_in, int epilogue, void* out, int64_t ldo, void* stream);
 
+/* The encoder's attention on its own: out = softmax(q k^T / 8) v per (crop, head), head_dim 64 -- what transformers'
+ * ViTSelfAttention / Dinov2SelfAttention and open_clip's nn.MultiheadAttention compute inside the encoders of
+ * utils/embeddings.py:46,69,93.  The kernel and the key-tile tier (4 / 9 / 13 / 17 tiles of 16 keys) are those ibl_vit_forward runs.
+ *   qkv [dev] fp16 [batch*n_tokens][3*dim] = [q | k | v], each [heads][64]; 16-byte aligned
+ *   out [dev] fp16 [batch*n_tokens][terms*dim]; 8-byte aligned.  terms 1: the row a; 2: [a | a / S]; 3: [a | (value - a) * S | a / S]
+ *       (S = IBL_VIT_SPLIT_SCALE, value = the fp32 result a was rounded from: the K-extended operand rows of the output projection)
+ *   cls_only 1: only token 0 of every crop is a query (the encoder's last block); the other rows of out are not written
+ *   dim == 64 * heads, 0 <= n_tokens <= 272, terms 1..3; batch or n_tokens 0 returns IBL_OK without a launch.  Everything else is
+ *   refused with a status before anything is launched. */
+int ibl_attention_f16(const void* qkv, void* out, int batch, int n_tokens, int dim, int heads, int cls_only, int terms, void* stream);
+
+/* The encoder's LayerNorm on its own: out[r] = (x[r] - mean) / sqrt(var + eps) * gamma + beta over `dim` columns, biased variance
+ * from a second pass over the centred row (torch.nn.LayerNorm as the reference's encoders call it).  The kernel and the launch are
+ * those of ibl_vit_forward.
+ *   x [dev] fp32 [n_rows][ld_x], gamma / beta [dev] fp32 [dim]; all 16-byte aligned
+ *   out_kind IBL_LN_OUT_F32: out fp32 [n_rows][ld_out], 16-byte aligned; out == x (with ld_out == ld_x) normalises in place
+ *            IBL_LN_OUT_F16 / _X2 / _X3: out fp16 [n_rows][ld_out] of 1 / 2 / 3 terms per row -- [a], [a | a / S],
+ *            [a | (value - a) * S | a / S] as for ibl_attention_f16; 8-byte aligned, ld_out >= terms * dim
+ *   dim a multiple of 4, <= 1024; ld_x >= dim; ld_x, ld_out multiples of 4 elements; eps >= 0; n_rows 0 returns IBL_OK without a
+ *   launch.  Rows between the strides are neither read nor written.  x and out must not overlap except in the in-place form. */
+enum { IBL_LN_OUT_F32 = 0, IBL_LN_OUT_F16 = 1, IBL_LN_OUT_F16_X2 = 2, IBL_LN_OUT_F16_X3 = 3 };
+int ibl_layernorm_f32(const float* x, int64_t ld_x, int64_t n_rows, int dim, const float* gamma, const float* beta, float eps,
+                      void* out, int64_t ld_out, int out_kind, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* DATOR RGB-D encoder                                                       */
 /* ------------------------------------------------------------------------------------------ */

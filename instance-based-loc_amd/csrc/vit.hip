@@ -858,6 +858,19 @@ __global__ __launch_bounds__(256) void ibl_layernorm_kernel(const float* x, int6
     }
 }
 
+// Every LayerNorm launch of this file: one wave per row, four rows per block.  terms 0 = fp32 rows (in place allowed), 1 / 2 / 3 = fp16
+// rows of that many terms.  No argument checks here: ibl_vit_forward and ibl_layernorm_f32 validate what they pass.
+static int launch_layernorm(const float* x, int64_t ld_x, int64_t n_rows, int dim, const float* g, const float* b, float eps, void* out,
+                            int64_t ld_out, int terms, hipStream_t s) {
+    const dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
+    if (terms == 0) hipLaunchKernelGGL((ibl_layernorm_kernel<true>), grid, block, 0, s, x, ld_x, n_rows, dim, g, b, eps, out, ld_out);
+    else if (terms == 1) hipLaunchKernelGGL((ibl_layernorm_kernel<false, 1>), grid, block, 0, s, x, ld_x, n_rows, dim, g, b, eps, out, ld_out);
+    else if (terms == 2) hipLaunchKernelGGL((ibl_layernorm_kernel<false, 2>), grid, block, 0, s, x, ld_x, n_rows, dim, g, b, eps, out, ld_out);
+    else hipLaunchKernelGGL((ibl_layernorm_kernel<false, 3>), grid, block, 0, s, x, ld_x, n_rows, dim, g, b, eps, out, ld_out);
+    IBL_LAUNCH_CHECK();
+    return IBL_OK;
+}
+
 // x[b*T + 0][:] = cls_pos[:]   (cls token + its position embedding)
 __global__ void ibl_set_cls_kernel(float* __restrict__ x, const float* __restrict__ cls_pos, int B, int T, int dim) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1104,6 +1117,45 @@ static int run_attention(const u16* qkv, u16* out, int B, int T, int D, int head
     return IBL_OK;
 }
 
+extern "C" int ibl_attention_f16(const void* qkv, void* out, int batch, int n_tokens, int dim, int heads, int cls_only, int terms,
+                                 void* stream) {
+    if (batch < 0 || n_tokens < 0) return ibl_set_error(IBL_ERR_ARG, "ibl_attention_f16: negative batch (%d) or n_tokens (%d)", batch, n_tokens);
+    if (terms < 1 || terms > 3) return ibl_set_error(IBL_ERR_ARG, "ibl_attention_f16: terms %d outside 1..3", terms);
+    if (cls_only != 0 && cls_only != 1) return ibl_set_error(IBL_ERR_ARG, "ibl_attention_f16: cls_only must be 0 or 1");
+    if (heads <= 0 || dim != heads * 64)
+        return ibl_set_error(IBL_ERR_UNSUPPORTED, "ibl_attention_f16: dim (%d) must be 64 * heads (%d): head_dim is 64", dim, heads);
+    if (n_tokens > 272) return ibl_set_error(IBL_ERR_UNSUPPORTED, "ibl_attention_f16: n_tokens %d > 272 not supported", n_tokens);
+    if ((int64_t)batch * heads > 0x7fffffff) return ibl_set_error(IBL_ERR_ARG, "ibl_attention_f16: batch * heads exceeds the grid");
+    if (batch == 0 || n_tokens == 0) return IBL_OK;
+    if (!qkv || !out) return ibl_set_error(IBL_ERR_ARG, "ibl_attention_f16: null pointer");
+    if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 7))
+        return ibl_set_error(IBL_ERR_ARG, "ibl_attention_f16: qkv must be 16-byte and out 8-byte aligned");
+    return run_attention(reinterpret_cast<const u16*>(qkv), reinterpret_cast<u16*>(out), batch, n_tokens, dim, heads, cls_only,
+                         reinterpret_cast<hipStream_t>(stream), terms);
+}
+
+extern "C" int ibl_layernorm_f32(const float* x, int64_t ld_x, int64_t n_rows, int dim, const float* gamma, const float* beta, float eps,
+                                 void* out, int64_t ld_out, int out_kind, void* stream) {
+    if (n_rows < 0 || n_rows > 0x7fffffff) return ibl_set_error(IBL_ERR_ARG, "ibl_layernorm_f32: n_rows out of range");
+    if (out_kind < IBL_LN_OUT_F32 || out_kind > IBL_LN_OUT_F16_X3) return ibl_set_error(IBL_ERR_ARG, "ibl_layernorm_f32: unknown out_kind %d", out_kind);
+    // the kernel keeps a row in 4 float4 per lane (+ a tail of up to 255 elements): beyond 1024 columns would be dropped, not refused
+    if (dim <= 0 || dim > 1024 || (dim & 3))
+        return ibl_set_error(IBL_ERR_UNSUPPORTED, "ibl_layernorm_f32: dim %d must be a multiple of 4 in 4..1024", dim);
+    if (!(eps >= 0.f)) return ibl_set_error(IBL_ERR_ARG, "ibl_layernorm_f32: eps must be >= 0");
+    const int terms = out_kind == IBL_LN_OUT_F32 ? 1 : out_kind;          // column blocks of an output row
+    if (ld_x < dim || ld_out < (int64_t)terms * dim || (ld_x & 3) || (ld_out & 3))
+        return ibl_set_error(IBL_ERR_ARG, "ibl_layernorm_f32: row strides must be >= the row length (%d in, %d out) and multiples of 4 elements",
+                             dim, terms * dim);
+    if (n_rows == 0) return IBL_OK;
+    if (!x || !gamma || !beta || !out) return ibl_set_error(IBL_ERR_ARG, "ibl_layernorm_f32: null pointer");
+    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(gamma) & 15) || (reinterpret_cast<uintptr_t>(beta) & 15) ||
+        (reinterpret_cast<uintptr_t>(out) & (out_kind == IBL_LN_OUT_F32 ? 15 : 7)))
+        return ibl_set_error(IBL_ERR_ARG, "ibl_layernorm_f32: x / gamma / beta / fp32 out must be 16-byte aligned, fp16 out 8-byte");
+    if (out == (const void*)x && (out_kind != IBL_LN_OUT_F32 || ld_out != ld_x))
+        return ibl_set_error(IBL_ERR_ARG, "ibl_layernorm_f32: in place needs fp32 output with the input's row stride");
+    return launch_layernorm(x, ld_x, n_rows, dim, gamma, beta, eps, out, ld_out, out_kind, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, const void* patches, int batch,
                                float* out, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!d || !w || !patches || !out || !workspace) return ibl_set_error(IBL_ERR_ARG, "ibl_vit_forward: null pointer");
@@ -1156,12 +1208,10 @@ extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, 
                            T, D);
         IBL_LAUNCH_CHECK();
     }
-    const dim3 ln_grid((unsigned)((Rn + 3) / 4));
     if (d->flags & IBL_VIT_PRE_LN) {
         // CLIP ln_pre: normalise the residual stream in place (through the fp16-free f32 path)
-        hipLaunchKernelGGL(ibl_layernorm_kernel<true>, ln_grid, dim3(256), 0, s, x, (int64_t)D, Rn, D, w->ln_pre_g,
-                           w->ln_pre_b, d->ln_eps, (void*)x, (int64_t)D);
-        IBL_LAUNCH_CHECK();
+        st = launch_layernorm(x, D, Rn, D, w->ln_pre_g, w->ln_pre_b, d->ln_eps, x, D, 0, s);
+        if (st) return st;
     }
     for (int l = 0; l < d->n_blocks_run; ++l) {
         const ibl_vit_layer* L = &w->layers[l];
@@ -1175,14 +1225,8 @@ extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, 
         const int qt = (!cls_only && L->w_qkv_x && L->qkv_terms > 1) ? L->qkv_terms : 1;
         const int ft = (!cls_only && L->w_fc1_x && L->fc1_terms > 1) ? L->fc1_terms : 1;
         if (qt > 3 || ft > 3) return ibl_set_error(IBL_ERR_ARG, "ibl_vit_forward: layer %d: at most three operand terms", l);
-#define IBL_LN_TERMS(terms, g_, b_)                                                                                                 \
-        do {                                                                                                                            \
-            if ((terms) == 1) hipLaunchKernelGGL((ibl_layernorm_kernel<false, 1>), ln_grid, dim3(256), 0, s, x, (int64_t)D, Rn, D, g_, b_, d->ln_eps, (void*)xn, (int64_t)D);            \
-            else if ((terms) == 2) hipLaunchKernelGGL((ibl_layernorm_kernel<false, 2>), ln_grid, dim3(256), 0, s, x, (int64_t)D, Rn, D, g_, b_, d->ln_eps, (void*)xn, (int64_t)2 * D);   \
-            else hipLaunchKernelGGL((ibl_layernorm_kernel<false, 3>), ln_grid, dim3(256), 0, s, x, (int64_t)D, Rn, D, g_, b_, d->ln_eps, (void*)xn, (int64_t)3 * D);                      \
-        } while (0)
-        IBL_LN_TERMS(qt, L->ln1_g, L->ln1_b);
-        IBL_LAUNCH_CHECK();
+        st = launch_layernorm(x, D, Rn, D, L->ln1_g, L->ln1_b, d->ln_eps, xn, (int64_t)qt * D, qt, s);
+        if (st) return st;
         if (!cls_only) {
             GemmEpi e{};
             e.bias = L->b_qkv; e.out = qkv; e.ldo = 3 * D; e.algo_k = D;
@@ -1224,13 +1268,9 @@ extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, 
                 if (st) return st;
             }
         }
-        if (!cls_only) {
-            IBL_LN_TERMS(ft, L->ln2_g, L->ln2_b);
-        } else {
-            hipLaunchKernelGGL(ibl_layernorm_kernel<false>, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, s, x, TD, (int64_t)batch, D,
-                               L->ln2_g, L->ln2_b, d->ln_eps, (void*)fin_bf, (int64_t)D);
-        }
-        IBL_LAUNCH_CHECK();
+        st = cls_only ? launch_layernorm(x, TD, batch, D, L->ln2_g, L->ln2_b, d->ln_eps, fin_bf, D, 1, s)
+                      : launch_layernorm(x, D, Rn, D, L->ln2_g, L->ln2_b, d->ln_eps, xn, (int64_t)ft * D, ft, s);
+        if (st) return st;
         const u16* mlp_in = cls_only ? fin_bf : xn;
         const int mlp_rows = cls_only ? batch : (int)Rn;
         {
@@ -1260,41 +1300,35 @@ extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, 
             }
         }
     }
-#undef IBL_LN_TERMS
     if (d->flags & IBL_VIT_OUT_ALL_TOKENS) {
         // DATOR streams: all tokens, optionally through the final LayerNorm
         if (d->flags & IBL_VIT_FINAL_LN) {
-            hipLaunchKernelGGL(ibl_layernorm_kernel<true>, ln_grid, dim3(256), 0, s, x, (int64_t)D, Rn, D, w->ln_f_g,
-                               w->ln_f_b, d->ln_eps, (void*)out, (int64_t)D);
-            IBL_LAUNCH_CHECK();
+            st = launch_layernorm(x, D, Rn, D, w->ln_f_g, w->ln_f_b, d->ln_eps, out, D, 0, s);
+            if (st) return st;
         } else {
             IBL_HIP_CHECK(hipMemcpyAsync(out, x, Rn * D * 4, hipMemcpyDeviceToDevice, s));
         }
         return IBL_OK;
     }
     // CLS rows -> (final LN) -> (projection) -> out fp32 [batch][out_dim]
-    const dim3 cls_grid((unsigned)((batch + 3) / 4));
     if (d->flags & IBL_VIT_PROJ) {
         if (!(d->flags & IBL_VIT_FINAL_LN)) return ibl_set_error(IBL_ERR_UNSUPPORTED, "projection needs final LN");
         GemmEpi e{};
         e.bias = nullptr; e.out = out; e.ldo = d->out_dim;
         if (w->w_proj_x) {           // three-term operands: K' = 3 D, one accumulation (xn is free by now: batch <= R rows of 3 D)
-            hipLaunchKernelGGL((ibl_layernorm_kernel<false, 3>), cls_grid, dim3(256), 0, s, x, (int64_t)T * D, (int64_t)batch, D,
-                               w->ln_f_g, w->ln_f_b, d->ln_eps, (void*)xn, (int64_t)3 * D);
-            IBL_LAUNCH_CHECK();
+            st = launch_layernorm(x, (int64_t)T * D, batch, D, w->ln_f_g, w->ln_f_b, d->ln_eps, xn, (int64_t)3 * D, 3, s);
+            if (st) return st;
             e.algo_k = D;
             return launch_gemm<EPI_BIAS_F32>(xn, (int64_t)3 * D, reinterpret_cast<const u16*>(w->w_proj_x), (int64_t)3 * D, batch, d->out_dim,
                                              3 * D, e, s);
         }
-        hipLaunchKernelGGL(ibl_layernorm_kernel<false>, cls_grid, dim3(256), 0, s, x, (int64_t)T * D, (int64_t)batch, D,
-                           w->ln_f_g, w->ln_f_b, d->ln_eps, (void*)fin_bf, (int64_t)D);
-        IBL_LAUNCH_CHECK();
+        st = launch_layernorm(x, (int64_t)T * D, batch, D, w->ln_f_g, w->ln_f_b, d->ln_eps, fin_bf, D, 1, s);
+        if (st) return st;
         return launch_gemm<EPI_BIAS_F32>(fin_bf, D, reinterpret_cast<const u16*>(w->w_proj), D, batch, d->out_dim, D, e, s);
     }
     if (d->flags & IBL_VIT_FINAL_LN) {
-        hipLaunchKernelGGL(ibl_layernorm_kernel<true>, cls_grid, dim3(256), 0, s, x, (int64_t)T * D, (int64_t)batch, D,
-                           w->ln_f_g, w->ln_f_b, d->ln_eps, (void*)out, (int64_t)D);
-        IBL_LAUNCH_CHECK();
+        st = launch_layernorm(x, (int64_t)T * D, batch, D, w->ln_f_g, w->ln_f_b, d->ln_eps, out, D, 0, s);
+        if (st) return st;
     } else {
         IBL_HIP_CHECK(hipMemcpy2DAsync(out, (size_t)D * 4, x, (size_t)T * D * 4, (size_t)D * 4, batch,
                                        hipMemcpyDeviceToDevice, s));

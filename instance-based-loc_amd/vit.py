@@ -491,3 +491,42 @@ def linear_f16(x: torch.Tensor, W: torch.Tensor, bias=None, epilogue=LINEAR_F16,
                                   out.stride(0), torch.cuda.current_stream().cuda_stream)
     _lib.check(st, "ibl_linear_f16")
     return out
+
+
+def attention_f16(qkv: torch.Tensor, heads: int, cls_only: bool = False, terms: int = 1, out=None) -> torch.Tensor:
+    """softmax(q k^T / 8) v per (crop, head) through `ibl_attention_f16` (the encoder's attention kernel on its own).
+    qkv (batch, n_tokens, 3 * dim) fp16 = [q | k | v]; returns (batch, n_tokens, terms * dim) fp16.  With `cls_only` only row 0 of
+    every crop is written, so pass `out` unless the other rows may stay uninitialised.  Shapes the kernel cannot run
+    (dim != 64 * heads, n_tokens > 272, terms outside 1..3) are refused by the library: IblError."""
+    assert qkv.dtype == torch.float16 and qkv.is_cuda and qkv.dim() == 3 and qkv.is_contiguous() and qkv.shape[2] % 3 == 0
+    batch, n_tokens, dim = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
+    if out is None:
+        out = torch.empty((batch, n_tokens, max(int(terms), 0) * dim), device=qkv.device, dtype=torch.float16)
+    assert out.dtype == torch.float16 and out.is_cuda and out.is_contiguous() and out.shape == (batch, n_tokens, terms * dim)
+    st = _lib.lib.ibl_attention_f16(qkv.data_ptr(), out.data_ptr(), batch, n_tokens, dim, heads, int(cls_only), terms,
+                                     torch.cuda.current_stream().cuda_stream)
+    _lib.check(st, "ibl_attention_f16")
+    return out
+
+
+LN_F32, LN_F16, LN_F16_X2, LN_F16_X3 = 0, 1, 2, 3
+
+
+def layernorm_f32(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, out_kind=LN_F32, out=None) -> torch.Tensor:
+    """LayerNorm over the last axis of x (n_rows, dim) fp32 through `ibl_layernorm_f32` (the encoder's kernel on its own).  x and
+    `out` may be row-strided views (only the last axis must be contiguous); `out=x` normalises in place (LN_F32).  LN_F16 /
+    LN_F16_X2 / LN_F16_X3 give fp16 rows of 1 / 2 / 3 terms, (n_rows, terms * dim).  dim > 1024 or dim % 4 != 0 is refused
+    by the library: IblError."""
+    assert x.dtype == torch.float32 and x.is_cuda and x.dim() == 2 and x.stride(1) == 1
+    n_rows, dim = x.shape
+    width = dim * (1 if out_kind == LN_F32 else int(out_kind))
+    if out is None:
+        out = torch.empty((n_rows, width), device=x.device, dtype=torch.float32 if out_kind == LN_F32 else torch.float16)
+    assert out.dtype == (torch.float32 if out_kind == LN_F32 else torch.float16) and out.is_cuda
+    assert out.dim() == 2 and out.shape == (n_rows, width) and out.stride(1) == 1
+    for t in (gamma, beta):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == dim
+    st = _lib.lib.ibl_layernorm_f32(x.data_ptr(), x.stride(0), n_rows, dim, gamma.data_ptr(), beta.data_ptr(), eps, out.data_ptr(),
+                                     out.stride(0), out_kind, torch.cuda.current_stream().cuda_stream)
+    _lib.check(st, "ibl_layernorm_f32")
+    return out
