@@ -355,6 +355,31 @@ int64_t ibl_reg_ctx_high_water(const ibl_reg_ctx* ctx);
  * search / with a full-size RANSAC survivor list after the fast path's list overflowed -- same results, more time); synchronises the
  * device */
 int ibl_reg_ctx_status(ibl_reg_ctx* ctx, int clear);
+/* Diagnostic switches of a context, by name.  All are numbers; a flag is on when it is not 0.
+ *   name            default  meaning
+ *   knn_safety      1.1      tile k-NN grids: a ball of knn_rho cells holds knn_safety x max_nn points at the cloud's mean density
+ *   knn_rho         3        tile k-NN grids: cells a tile's staging cube reaches past the tile (clamped to 1..4)
+ *   knn_noguess     0        flag: the two-pass histogram selection for every k-NN query instead of the guessed threshold
+ *   knn_debug       0        flag: print how many queries of each tile search fell back to the grid walk (synchronises)
+ *   feat_unfused    0        flag: normals and FPFH from two neighbour searches instead of one
+ *   feat_valu       0        flag: the VALU feature search of the registration instead of the matrix-core one
+ *   feat_cand_cap   0        entries of the matrix-core search's candidate list (>= 1), 0 = sized by the call; a small one forces the
+ *                            overflow fallback
+ *   feat_p1_stride  2        pass 1 of the matrix-core search visits one database chunk in feat_p1_stride (>= 1)
+ *   spfh_f64        0        flag: every SPFH pair in fp64 instead of fp32 bins + fp64 for the undecided pairs
+ *   spfh_qcap       0        entries per queue of undecided SPFH pairs (>= 1), 0 = sized by the call; a small one forces the overflow path
+ *   spfh_stats      0        flag: print the undecided SPFH pairs of every batch (synchronises)
+ *   eval_fullscan   0        flag: the evaluation reads every cell of a query's box instead of pruning by the best distance so far
+ *   timing          0        level: 1 prints the host-synchronised phase times of a registration call, 2 also synchronises and checks
+ *                            for errors after every launch group of its feature search
+ * Every switch except knn_safety, knn_rho and feat_p1_stride must leave every output bit unchanged: each selects another path to the
+ * same result, or only prints.  Those three dimension work and leave the results unchanged as well, but are for measurements, not
+ * for comparisons.  ibl_reg_ctx_create sets every switch whose environment variable IBL_<NAME IN UPPER CASE> exists (IBL_TIMING=1,
+ * IBL_KNN_RHO=2, ...) to its value; the environment is not read again.  After that the switches of a context are set by the thread
+ * that owns the context, between calls.  Both functions return the argument error (-1) and change nothing for an unknown name, a null argument
+ * or a value that is not finite; the setter clamps as listed. */
+int ibl_reg_ctx_set_diag(ibl_reg_ctx* ctx, const char* name, double value);
+int ibl_reg_ctx_get_diag(const ibl_reg_ctx* ctx, const char* name, double* value);
 
 /* Clouds are passed as batches of segments: pts4 [dev] N x float4 (x, y, z, intensity =
  * (r+g+b)/3), seg_off [dev] and [host] copies of the (n_seg + 1) int32 segment boundaries. */
@@ -392,7 +417,7 @@ int ibl_radius_outlier_batch(ibl_reg_ctx* ctx, const float* pts4, const int32_t*
  * downsample_and_compute_fpfh (utils/fpfh_register.py:86-98).  normals4: [dev] N x float4,
  * fpfh: [dev] N x 33 fp32 (point-major) or NULL to skip the features.  When radius_normal <= radius_feature and max_nn_normal <=
  * min(max_nn_feature, 32) -- the reference's 2 / 5 voxel, 30 / 100 neighbours -- ONE neighbour search serves both (the normal's
- * neighbours are among the feature neighbours); the results are those of the two searches bit for bit (IBL_FEAT_UNFUSED=1 runs them). */
+ * neighbours are among the feature neighbours); the results are those of the two searches bit for bit (switch feat_unfused runs them). */
 int ibl_normals_fpfh_batch(ibl_reg_ctx* ctx, const float* pts4, const int32_t* seg_off_dev, const int32_t* seg_off_host,
                            int n_seg, double radius_normal, int max_nn_normal, double radius_feature, int max_nn_feature,
                            float* normals4, float* fpfh, void* stream);

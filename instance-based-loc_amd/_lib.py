@@ -54,6 +54,8 @@ _SIGS = {
     "ibl_reg_ctx_reset": (C.c_int, [vp]),
     "ibl_reg_ctx_high_water": (C.c_int64, [vp]),
     "ibl_reg_ctx_status": (C.c_int, [vp, C.c_int]),
+    "ibl_reg_ctx_set_diag": (C.c_int, [vp, C.c_char_p, C.c_double]),
+    "ibl_reg_ctx_get_diag": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_double)]),
     "ibl_unproject_masks": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp, C.c_int64,
                                       vp, vp, vp]),
     "ibl_voxel_downsample_batch": (C.c_int, [vp, vp, vp, vp, C.c_int32, C.c_double, vp, vp, vp, vp, vp]),

@@ -6,6 +6,12 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include <cctype>
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <string>
 #include <vector>
 
 #include "ibloc.h"
@@ -36,7 +42,7 @@ int ibl_launch_fpfh(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* pts, con
 int ibl_launch_radius_count(const BatchGrid& g, const float4* pts, const int* seg_off, int n, double radius, int nb_points,
                             unsigned char* keep, hipStream_t s);
 
-bool ibl_normals_fpfh_fusable(double radius_normal, int max_nn_normal, double radius_feature, int max_nn_feature);
+bool ibl_normals_fpfh_fusable(const ibl_reg_ctx* ctx, double radius_normal, int max_nn_normal, double radius_feature, int max_nn_feature);
 int ibl_launch_normals_fpfh(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* pts, const int* seg_off, int n, double radius_normal,
                             int max_nn_normal, double radius_feature, int max_nn_feature, float4* normals, unsigned char* spfh, int* nbr_idx,
                             float* nbr_d2, int* nbr_cnt, float* fpfh, int matching_order, int* status, hipStream_t s);
@@ -53,6 +59,52 @@ static int ibl_bbox_to_host(ibl_reg_ctx* ctx, const float4* P, const int* seg_of
     if (st) return st;
     IBL_HIP_CHECK(hipMemcpyAsync(bbox_host, bbox, sizeof(float) * 6 * (size_t)n_seg, hipMemcpyDeviceToHost, s));
     IBL_HIP_CHECK(hipStreamSynchronize(s));
+    return IBL_OK;
+}
+
+// The diagnostic switches by name (include/ibloc.h documents them at ibl_reg_ctx_set_diag).  Values are clamped to [lo, hi]; auto0:
+// 0 is kept and means "sized by the call".  The environment variable of a switch is IBL_ + its name in upper case.
+struct DiagSwitch {
+    const char* name;
+    int RegDiag::*field;          // null: knn_safety, the one double
+    int lo = INT_MIN, hi = INT_MAX;
+    bool auto0 = false;
+};
+static const DiagSwitch DIAG_SWITCHES[] = {
+    {"knn_safety", nullptr},
+    {"knn_rho", &RegDiag::knn_rho, 1, 4},
+    {"knn_noguess", &RegDiag::knn_noguess},
+    {"knn_debug", &RegDiag::knn_debug},
+    {"feat_unfused", &RegDiag::feat_unfused},
+    {"feat_valu", &RegDiag::feat_valu},
+    {"feat_cand_cap", &RegDiag::feat_cand_cap, 1, INT_MAX, true},
+    {"feat_p1_stride", &RegDiag::feat_p1_stride, 1},
+    {"spfh_f64", &RegDiag::spfh_f64},
+    {"spfh_qcap", &RegDiag::spfh_qcap, 1, INT_MAX, true},
+    {"spfh_stats", &RegDiag::spfh_stats},
+    {"eval_fullscan", &RegDiag::eval_fullscan},
+    {"timing", &RegDiag::timing},
+};
+
+static const DiagSwitch* find_diag(const char* name) {
+    for (const DiagSwitch& d : DIAG_SWITCHES)
+        if (name && strcmp(name, d.name) == 0) return &d;
+    return nullptr;
+}
+
+extern "C" int ibl_reg_ctx_set_diag(ibl_reg_ctx* ctx, const char* name, double value) {
+    const DiagSwitch* d = find_diag(name);
+    if (!ctx || !d || !std::isfinite(value)) return ibl_set_error(IBL_ERR_ARG, "ibl_reg_ctx_set_diag: null context, unknown switch or non-finite value");
+    if (!d->field) ctx->diag.knn_safety = value;
+    else if (d->auto0 && value == 0) ctx->diag.*d->field = 0;
+    else ctx->diag.*d->field = (int)std::min(std::max(value, (double)d->lo), (double)d->hi);
+    return IBL_OK;
+}
+
+extern "C" int ibl_reg_ctx_get_diag(const ibl_reg_ctx* ctx, const char* name, double* value) {
+    const DiagSwitch* d = find_diag(name);
+    if (!ctx || !d || !value) return ibl_set_error(IBL_ERR_ARG, "ibl_reg_ctx_get_diag: null argument or unknown switch");
+    *value = d->field ? (double)(ctx->diag.*d->field) : ctx->diag.knn_safety;
     return IBL_OK;
 }
 
@@ -73,6 +125,11 @@ extern "C" int ibl_reg_ctx_create(ibl_reg_ctx** out, int64_t arena_bytes) {
     if (e != hipSuccess) { (void)hipFree(c->base); delete c; return ibl_set_error(IBL_ERR_HIP, "ibl_reg_ctx_create: memset failed"); }
     c->pin_size = 32 << 20;            // pinned staging of the plan tables (job / pair / grid descriptors of one call)
     if (hipHostMalloc(reinterpret_cast<void**>(&c->pin), (size_t)c->pin_size, hipHostMallocDefault) != hipSuccess) { c->pin = nullptr; c->pin_size = 0; }
+    for (const DiagSwitch& d : DIAG_SWITCHES) {          // the one getenv of the registration path: later changes of the environment do not reach the context
+        std::string var = "IBL_";
+        for (const char* p = d.name; *p; ++p) var += (char)toupper((unsigned char)*p);
+        if (const char* v = getenv(var.c_str())) (void)ibl_reg_ctx_set_diag(c, d.name, atof(v));
+    }
     *out = c;
     return IBL_OK;
 }
@@ -141,7 +198,7 @@ extern "C" int ibl_normals_fpfh_batch(ibl_reg_ctx* ctx, const float* pts4, const
     std::vector<float> bbox_host((size_t)n_seg * 6 + 6);
     st = ibl_bbox_to_host(ctx, P, seg_off_dev, n_seg, bbox_host.data(), s);
     if (st) return st;
-    const bool fused = fpfh && radius_feature > 0 && max_nn_feature > 0 && ibl_normals_fpfh_fusable(radius_normal, max_nn_normal, radius_feature, max_nn_feature);
+    const bool fused = fpfh && radius_feature > 0 && max_nn_feature > 0 && ibl_normals_fpfh_fusable(ctx, radius_normal, max_nn_normal, radius_feature, max_nn_feature);
     if (!fused) {
         ArenaMark m2(ctx);
         BatchGrid g;
@@ -218,7 +275,7 @@ int ibl_features_on_batch(ibl_reg_ctx* ctx, const float4* P, const int* seg_off_
         if (st) return st;
         bbox_host = own_bbox.data();
     }
-    const bool fused = fpfh && ibl_normals_fpfh_fusable(voxel_size * 2, 30, voxel_size * 5, 100);
+    const bool fused = fpfh && ibl_normals_fpfh_fusable(ctx, voxel_size * 2, 30, voxel_size * 5, 100);
     if (!fused) {
         ArenaMark mA(ctx);
         BatchGrid gA;

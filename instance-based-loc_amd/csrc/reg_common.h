@@ -32,7 +32,23 @@ struct BatchGrid {
 // ------------------------------------------------------------------------------------------------
 // context: explicit device arena (bump allocator), created / destroyed through the C-ABI
 // ------------------------------------------------------------------------------------------------
+#define FM_P1_STRIDE 2           // reg_featnn.hip: pass 1 visits one database chunk in FM_P1_STRIDE (ibl_feat_search_mfma)
+
+// Diagnostic switches of a context (names, meanings and rules: include/ibloc.h at ibl_reg_ctx_set_diag; the table that names the
+// fields is next to the setter in reg_api.hip).  Read at the point of use, written only through the setter.
+struct RegDiag {
+    double knn_safety = 1.1;                // tile grids (reg_grid.hip: the sweeps behind the two defaults)
+    int knn_rho = 3;
+    int knn_noguess = 0, knn_debug = 0;
+    int feat_unfused = 0, feat_valu = 0, feat_cand_cap = 0;
+    int feat_p1_stride = FM_P1_STRIDE;
+    int spfh_f64 = 0, spfh_qcap = 0, spfh_stats = 0;
+    int eval_fullscan = 0;
+    int timing = 0;                         // 1: a "[reg]" line per phase of a registration pass; 2: also a synchronisation + error check per launch group
+};
+
 struct ibl_reg_ctx {
+    RegDiag diag;
     unsigned char* base = nullptr;
     int64_t size = 0;
     int64_t used = 0;
@@ -104,11 +120,9 @@ int ibl_build_batch_grid_bounded(ibl_reg_ctx* ctx, const float4* pts, const int*
 // Grid for the hybrid k-NN kernels, sized on the HOST from the segments' bounding boxes (bbox_host [S][6], the values
 // ibl_launch_bbox produced): no read-back, no dims kernel.  The cell of a segment follows its point density (about max_nn points
 // inside a ball of two cells, clamped to [radius / 12, radius]), tiles are cubes of ts^3 cells.
-// Tile-grid tuning: the staging cube of a tile reaches ibl_knn_rho() cells past it, and the cell of a segment is sized so that the
-// ball of that many cells holds ibl_knn_safety() x max_nn points at the segment's mean surface density (clouds are uneven: edges,
-// corners and seams see half-empty balls).  Environment overrides IBL_KNN_RHO / IBL_KNN_SAFETY are for measurements.
-double ibl_knn_safety();
-int ibl_knn_rho();
+// Tile-grid tuning: the staging cube of a tile reaches diag.knn_rho cells past it, and the cell of a segment is sized so that the
+// ball of that many cells holds diag.knn_safety x max_nn points at the segment's mean surface density (clouds are uneven: edges,
+// corners and seams see half-empty balls).  Values other than the defaults are for measurements.
 int ibl_build_tile_grid(ibl_reg_ctx* ctx, const float4* pts, const int* seg_off_dev, const int* seg_off_host, int n_seg,
                         const float* bbox_host, double radius, int max_nn, int ts, int64_t max_cells, BatchGrid* out, hipStream_t s);
 

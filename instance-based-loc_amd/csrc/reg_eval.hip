@@ -262,8 +262,7 @@ static int evaluate_impl(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float*
     IBL_ARENA(d_jobs, EvalJob, J);
     IBL_ARENA(partial, double, (int64_t)J * ICP_BPJ * 2);
     IBL_HIP_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(EvalJob) * J, hipMemcpyHostToDevice, s));
-    const char* efs = getenv("IBL_EVAL_FULLSCAN");          // diagnostics: 1 = every cell of the query's box (the tests compare both)
-    const int prune = !(efs && atoi(efs));
+    const int prune = !ctx->diag.eval_fullscan;          // diagnostics: full scan = every cell of the query's box (the tests compare both)
     void* tok;
     ibl_prof_begin(IBL_PROF_ST_EVAL, 24.0 * (double)(jobs[J - 1].out + (jobs[J - 1].end - jobs[J - 1].begin)), s, &tok);
     hipLaunchKernelGGL(ibl_evaluate_kernel, dim3(ICP_BPJ, J), dim3(256), 0, s, *grid, reinterpret_cast<const float4*>(det_pts4), d_jobs,

@@ -52,7 +52,6 @@ typedef __attribute__((ext_vector_type(16))) float fm_f32x16;
 #ifndef FM_NQ
 #define FM_NQ 2                  // 32-query tiles per wave (they share every database fragment read)
 #endif
-#define FM_P1_STRIDE 2           // pass 1 visits one database chunk in FM_P1_STRIDE (ibl_feat_search_mfma)
 #define FM_QUEUE 256             // per-wave candidate queue, flushed when fewer than 64 slots (one append step) are left
 
 struct FmCand { int pair, qi, t, pad; };
@@ -320,7 +319,7 @@ int ibl_feat_search_mfma(ibl_reg_ctx* ctx, const FeatPair* d_pairs, int n_pairs,
     if (n_pairs > 32768) { *overflow = true; return IBL_OK; }      // candidates carry the pair id as blockIdx.y: one launch only
     ArenaMark mark(ctx);
     int cand_cap = (int)std::min<int64_t>(out_count * 8 + 65536, (int64_t)1 << 27);
-    if (const char* e = getenv("IBL_FEAT_CAND_CAP")) cand_cap = std::max(1, atoi(e));      // tests: force the overflow fallback
+    if (ctx->diag.feat_cand_cap) cand_cap = ctx->diag.feat_cand_cap;      // tests: force the overflow fallback
     float* up; FmCand* cand; unsigned long long* n_cand; unsigned long long* best;
     IBL_ARENA(up, float, out_count + 64);
     IBL_ARENA(cand, FmCand, cand_cap);
@@ -332,8 +331,7 @@ int ibl_feat_search_mfma(ibl_reg_ctx* ctx, const FeatPair* d_pairs, int n_pairs,
     IBL_HIP_CHECK(hipMemsetAsync(best, 0xFF, sizeof(unsigned long long) * (size_t)out_count, s));
     const bool indexed = need_pos != nullptr;
     // pass 1 on every FM_P1_STRIDE-th chunk of the database: 1 / stride of a pass for a bound that is the stride-th smallest distance or so
-    static int p1s = -1;
-    if (p1s < 0) { const char* e = getenv("IBL_FEAT_P1_STRIDE"); p1s = e ? std::max(1, atoi(e)) : FM_P1_STRIDE; }
+    const int p1s = ctx->diag.feat_p1_stride;
     bool conv = false;                  // a feature set without resident operand rows takes part
     for (int k = 0; k < 3; ++k) conv = conv || (src.fpfh[k] && !src.split[k]);
     for (int p0 = 0; p0 < n_pairs; p0 += 32768) {
@@ -353,7 +351,7 @@ int ibl_feat_search_mfma(ibl_reg_ctx* ctx, const FeatPair* d_pairs, int n_pairs,
         else passes(std::false_type{});
         IBL_LAUNCH_CHECK();
     }
-    if (getenv("IBL_TIMING") && atoi(getenv("IBL_TIMING")) >= 2) {
+    if (ctx->diag.timing >= 2) {
         unsigned long long h = 0;
         const hipError_t e = hipMemcpy(&h, n_cand, sizeof(h), hipMemcpyDeviceToHost);
         fprintf(stderr, "[reg-dbg] mfma passes done: %s; candidates %llu of cap %d, out_count %lld, pairs %d, max_q %d\n", hipGetErrorString(e), h, cand_cap,

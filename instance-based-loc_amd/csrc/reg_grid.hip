@@ -224,21 +224,6 @@ int ibl_build_batch_grid_bounded(ibl_reg_ctx* ctx, const float4* pts, const int*
     return grid_fill(ctx, pts, seg_off_dev, n_seg, n, seg, (int)cells_bound, out, s);
 }
 
-// Defaults from sweeps on the detections of a bench step (tools/lab_knn_grid.sh, 1.04 M points in 210 clouds, ms per feature call;
-// the results do not depend on the knobs -- a tile proves its queries or hands them to the grid walk).  With the 100-neighbour search
-// on 1 600-candidate packed tiles, three workgroups per CU (reg_knn.hip):
-//   rho 2: safety 0.6 7.64 | 0.7 7.41 | 0.8 7.44 | 1.0 7.80 (9.7 % of the queries overflow their cube)
-//   rho 3: safety 0.7 7.89 | 0.8 7.33 | 0.9 7.16 | 1.0 7.14 | 1.1 7.02 | 1.25 7.06 | 1.5 7.30      rho 4: 1.25 7.43
-// (on the 2 560-candidate tiles, two workgroups per CU, the best was rho 2 / 0.8: 8.53 against 9.05 at 3 / 1.0.)
-double ibl_knn_safety() {
-    static const double v = [] { const char* e = getenv("IBL_KNN_SAFETY"); return e ? atof(e) : 1.1; }();
-    return v;
-}
-int ibl_knn_rho() {
-    static const int v = [] { const char* e = getenv("IBL_KNN_RHO"); const int r = e ? atoi(e) : 3; return r < 1 ? 1 : (r > 4 ? 4 : r); }();
-    return v;
-}
-
 int ibl_stage_upload(ibl_reg_ctx* ctx, void* dst_dev, const void* src_host, int64_t bytes, hipStream_t s) {
     if (bytes <= 0) return IBL_OK;
     const int64_t need = ibl_align_up(bytes, 64);
@@ -261,6 +246,12 @@ __global__ __launch_bounds__(256) void ibl_tile_seg_kernel(const int* __restrict
     for (int t = tile_base[sgi] + threadIdx.x; t < tile_base[sgi + 1]; t += 256) tile_seg[t] = sgi;
 }
 
+// The defaults of diag.knn_safety / diag.knn_rho come from sweeps on the detections of a bench step (tools/lab_knn_grid.sh, 1.04 M
+// points in 210 clouds, ms per feature call; the results do not depend on the knobs -- a tile proves its queries or hands them to the grid walk).  With the 100-neighbour search
+// on 1 600-candidate packed tiles, three workgroups per CU (reg_knn.hip):
+//   rho 2: safety 0.6 7.64 | 0.7 7.41 | 0.8 7.44 | 1.0 7.80 (9.7 % of the queries overflow their cube)
+//   rho 3: safety 0.7 7.89 | 0.8 7.33 | 0.9 7.16 | 1.0 7.14 | 1.1 7.02 | 1.25 7.06 | 1.5 7.30      rho 4: 1.25 7.43
+// (on the 2 560-candidate tiles, two workgroups per CU, the best was rho 2 / 0.8: 8.53 against 9.05 at 3 / 1.0.)
 int ibl_build_tile_grid(ibl_reg_ctx* ctx, const float4* pts, const int* seg_off_dev, const int* seg_off_host, int n_seg,
                         const float* bbox_host, double radius, int max_nn, int ts, int64_t max_cells, BatchGrid* out, hipStream_t s) {
     const int n = seg_off_host[n_seg];
@@ -272,7 +263,7 @@ int ibl_build_tile_grid(ibl_reg_ctx* ctx, const float4* pts, const int* seg_off_
     if (n_seg == 0) return IBL_OK;
     std::vector<SegGrid> h(n_seg);
     std::vector<int> tb(n_seg + 1, 0);
-    const double safety = ibl_knn_safety(), rho_t = (double)ibl_knn_rho();
+    const double safety = ctx->diag.knn_safety, rho_t = (double)ctx->diag.knn_rho;
     long long cells = 0, tiles = 0;
     for (int sgi = 0; sgi < n_seg; ++sgi) {
         const float* b = bbox_host + 6 * (size_t)sgi;

@@ -1824,14 +1824,13 @@ __global__ __launch_bounds__(256) void ibl_radius_count_kernel(BatchGrid g, cons
 // ------------------------------------------------------------------------------------------------
 // host launchers (used by reg_api.hip)
 // ------------------------------------------------------------------------------------------------
-static NeedPop need_pop_table(int max_nn, int ts) {
+static NeedPop need_pop_table(const RegDiag& diag, int max_nn, int ts) {
     NeedPop np;
     np.v[0] = 0.f;
     for (int rho = 1; rho < 8; ++rho)
-        np.v[rho] = (float)(ibl_knn_safety() * max_nn * (ts + 2.0 * rho) * (ts + 2.0 * rho) / (3.14159265358979 * rho * rho));
-    np.rho_start = ibl_knn_rho();
-    const char* e = getenv("IBL_KNN_NOGUESS");          // diagnostics, read per call: the tests compare both selections bit for bit
-    np.guess = (e && atoi(e)) ? 0 : 1;
+        np.v[rho] = (float)(diag.knn_safety * max_nn * (ts + 2.0 * rho) * (ts + 2.0 * rho) / (3.14159265358979 * rho * rho));
+    np.rho_start = diag.knn_rho;
+    np.guess = diag.knn_noguess ? 0 : 1;          // diagnostics: the tests compare both selections bit for bit
     return np;
 }
 
@@ -1846,7 +1845,7 @@ static int launch_knn(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* pts, c
         IBL_ARENA(fb_list, int, (int64_t)n + 64);
         IBL_ARENA(fb_count, int, 64);
         IBL_HIP_CHECK(hipMemsetAsync(fb_count, 0, sizeof(int), s));
-        const NeedPop np = need_pop_table(max_nn, g.ts);
+        const NeedPop np = need_pop_table(ctx->diag, max_nn, g.ts);
         // LDS budget of the staged cube.  The kernel is bound by its resident workgroups: padded to ONE workgroup per CU it ran the
         // 100-neighbour search in 10.6 ms against 5.4 ms with two (lab: -DKNN_LAB_PAD_LDS).  Round 3, final form for the consumers that read
         // geometry only (Factory::WIDE): a PACKED tile (the original index rides in the staged point's w: 16 instead of 20 B per candidate)
@@ -1888,7 +1887,7 @@ static int launch_knn(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* pts, c
 #endif
         const int blocks = std::max(1, std::min(2048, (q1 - q0 + 3) / 4));
         hipLaunchKernelGGL((ibl_knn_list_kernel<Factory>), dim3(blocks), dim3(256), 0, s, g, seg_off, r, r2, max_nn, fac, fb_list, fb_count, status);
-        if (getenv("IBL_KNN_DEBUG")) {                      // diagnostics: how many queries the staged cubes could not answer
+        if (ctx->diag.knn_debug) {                      // diagnostics: how many queries the staged cubes could not answer
             int h = 0;
             (void)hipMemcpyAsync(&h, fb_count, sizeof(int), hipMemcpyDeviceToHost, s);
             (void)hipStreamSynchronize(s);
@@ -2062,10 +2061,9 @@ __global__ __launch_bounds__(256) void ibl_spfh_queue_kernel(const float4* __res
 }
 
 // normals + FPFH from ONE neighbour search (requires radius_normal <= radius_feature, max_nn_normal <= max_nn_feature and <= NP_MAXK)
-bool ibl_normals_fpfh_fusable(double radius_normal, int max_nn_normal, double radius_feature, int max_nn_feature) {
-    const char* e = getenv("IBL_FEAT_UNFUSED");          // diagnostics: 1 = the two separate searches (read per call: the tests compare both)
-    const bool off = e && atoi(e);
-    return !off && radius_normal <= radius_feature && max_nn_normal <= max_nn_feature && max_nn_normal <= NP_MAXK && max_nn_feature <= 128;   // (128-slot mask)
+// (diag.feat_unfused keeps the two separate searches: the tests compare both)
+bool ibl_normals_fpfh_fusable(const ibl_reg_ctx* ctx, double radius_normal, int max_nn_normal, double radius_feature, int max_nn_feature) {
+    return !ctx->diag.feat_unfused && radius_normal <= radius_feature && max_nn_normal <= max_nn_feature && max_nn_normal <= NP_MAXK && max_nn_feature <= 128;   // (128-slot mask)
 }
 int ibl_launch_normals_fpfh(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* pts, const int* seg_off, int n, double radius_normal,
                             int max_nn_normal, double radius_feature, int max_nn_feature, float4* normals, unsigned char* spfh, int* nbr_idx,
@@ -2085,13 +2083,11 @@ int ibl_launch_normals_fpfh(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* 
     IBL_LAUNCH_CHECK();
     {
         // fp32 bins + fp64 for the pairs next to a bin boundary (pair_bins_f32); the SPFH_NQ queues together hold 1 / 16 of all pairs
-        // (measured: 0.8 % are undecided) -- a batch that overflows one is redone in fp64 by the gated third launch; IBL_SPFH_F64=1 runs
-        // every pair in fp64 (the tests compare both), IBL_SPFH_QCAP=<entries per queue> shrinks the queues (the overflow test)
-        const char* e64 = getenv("IBL_SPFH_F64");
-        bool fast = !(e64 && atoi(e64));
-        if (fast) {
+        // (measured: 0.8 % are undecided) -- a batch that overflows one is redone in fp64 by the gated third launch; diag.spfh_f64 runs
+        // every pair in fp64 (the tests compare both), diag.spfh_qcap = <entries per queue> shrinks the queues (the overflow test)
+        if (!ctx->diag.spfh_f64) {
             int64_t cap64 = std::min<int64_t>((int64_t)n * max_nn_feature / (16 * SPFH_NQ) + 256, (int64_t)1 << 20);
-            if (const char* ec = getenv("IBL_SPFH_QCAP")) cap64 = std::max<int64_t>(1, atoll(ec));
+            if (ctx->diag.spfh_qcap) cap64 = ctx->diag.spfh_qcap;
             int2* queue; int* q_count;
             IBL_ARENA(queue, int2, cap64 * SPFH_NQ);
             IBL_ARENA(q_count, int, SPFH_NQ * SPFH_QSTRIDE + 64);
@@ -2104,7 +2100,7 @@ int ibl_launch_normals_fpfh(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* 
             hipLaunchKernelGGL(ibl_spfh_lists_kernel<false>, dim3(2048), dim3(256), 0, s, pts, normals, nbr_idx, nbr_cnt, max_nn_feature, n, spfh,
                                (int2*)nullptr, q_count, (int)cap64);
             IBL_LAUNCH_CHECK();
-            if (const char* es = getenv("IBL_SPFH_STATS"); es && atoi(es)) {              // diagnostics: undecided pairs of this batch (synchronises)
+            if (ctx->diag.spfh_stats) {              // diagnostics: undecided pairs of this batch (synchronises)
                 std::vector<int> cnt(SPFH_NQ * SPFH_QSTRIDE + 1);
                 IBL_HIP_CHECK(hipMemcpyAsync(cnt.data(), q_count, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost, s));
                 IBL_HIP_CHECK(hipStreamSynchronize(s));

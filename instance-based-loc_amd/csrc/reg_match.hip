@@ -611,7 +611,7 @@ static int search_features(ibl_reg_ctx* ctx, RegPass& ps, const FeatSources& src
     if (st) return st;
     // (1) every source point's nearest target: source-query pairs, folded per job
     // matrix-core filter + exact recheck (reg_featnn.hip); the VALU search only if its candidate list overflowed
-    const bool use_mfma = getenv("IBL_FEAT_VALU") == nullptr && !ps.opt.force_valu;      // read per call: the tests compare both searches
+    const bool use_mfma = !ctx->diag.feat_valu && !ps.opt.force_valu;      // (diagnostics: the tests compare both searches)
     bool over = !use_mfma;
     ps.dbg("plan uploads");
     if (use_mfma) {

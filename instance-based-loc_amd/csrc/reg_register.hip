@@ -88,7 +88,7 @@ __global__ void ibl_status_set_kernel(int* __restrict__ status, int mask) { atom
 static double now_ms() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
 
 void RegPass::phase(const char* what) {
-    if (!timing) return;
+    if (timing < 1) return;
     (void)hipStreamSynchronize(s);
     const double t = now_ms();
     fprintf(stderr, "[reg] %-28s %7.3f ms\n", what, t - t_prev);
@@ -96,8 +96,7 @@ void RegPass::phase(const char* what) {
 }
 
 void RegPass::dbg(const char* what) const {
-    static const bool on = getenv("IBL_TIMING") && atoi(getenv("IBL_TIMING")) >= 2;
-    if (!on) return;
+    if (timing < 2) return;
     const hipError_t e = hipStreamSynchronize(s);
     fprintf(stderr, "[reg-dbg] %-36s %s\n", what, hipGetErrorString(e));
 }
@@ -268,7 +267,7 @@ static int register_pass(ibl_reg_ctx* ctx, const RegCall& c, RegPassOpts opt, in
     ArenaMark mark(ctx);
     hipLaunchKernelGGL(ibl_status_clear_kernel, dim3(1), dim3(1), 0, s, ctx->d_status, IBL_ST_FEAT_OVERFLOW | IBL_ST_RANSAC_OVERFLOW);
     IBL_LAUNCH_CHECK();
-    ps.timing = getenv("IBL_TIMING") != nullptr;
+    ps.timing = ctx->diag.timing;
     ps.t_prev = now_ms();
 
     int st = assemble_jobs(ctx, ps);

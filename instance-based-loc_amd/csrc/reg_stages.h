@@ -113,10 +113,10 @@ struct RegPass {
     RansacState* rs;                       // null: no RANSAC (point-to-point ICP from the identity)
     IcpState* is;
     void *tok_match, *tok_ransac, *tok_icp;       // stage brackets of the in-process timer (bench.py)
-    bool timing;                           // IBL_TIMING: a "[reg]" line per phase
+    int timing;                            // diag.timing: 1 = a "[reg]" line per phase
     double t_prev;
     void phase(const char* what);
-    void dbg(const char* what) const;      // IBL_TIMING=2: synchronise after every launch group of the search phase
+    void dbg(const char* what) const;      // timing 2: synchronise after every launch group of the search phase
 };
 
 int ibl_reg_match_stage(ibl_reg_ctx* ctx, RegPass& ps);        // features of the job clouds, matching -> corr, n_corr

@@ -2,6 +2,7 @@
 
 Cloud batches are `(pts4, seg_off)`: pts4 a float32 CUDA tensor (N, 4) = (x, y, z, intensity) and
 seg_off an int32 tensor (S + 1,) of segment boundaries (host copy kept alongside)."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -44,6 +45,29 @@ class RegContext:
 
     def high_water(self):
         return _lib.lib.ibl_reg_ctx_high_water(self._h)
+
+    def diag_get(self, name):
+        """value of a diagnostic switch (include/ibloc.h lists them at ibl_reg_ctx_set_diag)"""
+        v = C.c_double()
+        _lib.check(_lib.lib.ibl_reg_ctx_get_diag(self._h, None if name is None else name.encode(), C.byref(v)), "ibl_reg_ctx_get_diag")
+        return v.value
+
+    def diag_set(self, name, value):
+        """sets one switch for good (the library clamps the value); `diag()` is the form that puts the old value back"""
+        _lib.check(_lib.lib.ibl_reg_ctx_set_diag(self._h, None if name is None else name.encode(), float(value)), "ibl_reg_ctx_set_diag")
+
+    @contextlib.contextmanager
+    def diag(self, **switches):
+        """`with ctx.diag(feat_valu=1, spfh_qcap=8):` sets diagnostic switches of this context for the body and puts the former
+        values back afterwards, also when the body raises.  For the thread that owns the context, between calls."""
+        old = {name: self.diag_get(name) for name in switches}          # (an unknown name raises before anything is set)
+        try:
+            for name, value in switches.items():
+                self.diag_set(name, value)
+            yield self
+        finally:
+            for name, value in old.items():
+                self.diag_set(name, value)
 
 
 class CloudBatch:

@@ -82,9 +82,9 @@ def test_knn_slow_path_matches_fast_path(ctx):
     assert np.mean(np.abs(fpfh.cpu().numpy() - ef).max(1) < 2e-3) > 0.99
 
 
-def test_fused_normals_and_feature_search_equals_the_two_searches(ctx, monkeypatch):
+def test_fused_normals_and_feature_search_equals_the_two_searches(ctx):
     """instance features take the normals' <= 30 neighbours from the 100-neighbour list of the feature search (one search instead of two);
-    IBL_FEAT_UNFUSED=1 runs the two stand-alone searches: normals and FPFH must agree bit for bit, dense and sparse clouds alike"""
+    the switch feat_unfused runs the two stand-alone searches: normals and FPFH must agree bit for bit, dense and sparse clouds alike"""
     from ibloc_amd.registration import CloudBatch, instance_features_batch, normals_fpfh_batch
     rng = np.random.default_rng(77)
     cs = clouds([5000, 1200, 40, 3, 0], 9)
@@ -92,18 +92,18 @@ def test_fused_normals_and_feature_search_equals_the_two_searches(ctx, monkeypat
     b = CloudBatch.from_numpy(cs)
     got = instance_features_batch(ctx, b, 0.05)
     n1, f1 = normals_fpfh_batch(ctx, b, 0.1, 30, 0.25, 100)
-    monkeypatch.setenv("IBL_FEAT_UNFUSED", "1")
-    ref = instance_features_batch(ctx, b, 0.05)
-    n2, f2 = normals_fpfh_batch(ctx, b, 0.1, 30, 0.25, 100)
+    with ctx.diag(feat_unfused=1):
+        ref = instance_features_batch(ctx, b, 0.05)
+        n2, f2 = normals_fpfh_batch(ctx, b, 0.1, 30, 0.25, 100)
     torch.cuda.synchronize()
     assert ctx.status() == 0
     assert torch.equal(got.normals[:b.n], ref.normals[:b.n]) and torch.equal(got.fpfh[:b.n], ref.fpfh[:b.n])
     assert torch.equal(n1, n2) and torch.equal(f1, f2)
 
 
-def test_spfh_fp32_bins_with_fp64_for_undecided_pairs_equal_the_fp64_bins(ctx, monkeypatch):
+def test_spfh_fp32_bins_with_fp64_for_undecided_pairs_equal_the_fp64_bins(ctx):
     """round 4: the SPFH bins of a pair come from fp32 arithmetic when every decision clears a guard band (pair_bins_f32, csrc/reg_knn.hip)
-    and from the fp64 pair features otherwise (queue + second kernel).  IBL_SPFH_F64=1 evaluates every pair in fp64; IBL_SPFH_QCAP=8
+    and from the fp64 pair features otherwise (queue + second kernel).  the switch spfh_f64 evaluates every pair in fp64; spfh_qcap=8
     overflows the queue, which the gated fp64 launch repairs: all three must give the same bytes -- noisy surfaces, exact planes (equal
     normals, theta on a bin boundary for every pair), a cloud 200 m from the origin, tiny and empty clouds"""
     from ibloc_amd.registration import CloudBatch, instance_features_batch
@@ -118,11 +118,10 @@ def test_spfh_fp32_bins_with_fp64_for_undecided_pairs_equal_the_fp64_bins(ctx, m
     cs.append(box.astype(np.float32))
     b = CloudBatch.from_numpy(cs)
     got = instance_features_batch(ctx, b, 0.05)
-    monkeypatch.setenv("IBL_SPFH_F64", "1")
-    ref = instance_features_batch(ctx, b, 0.05)
-    monkeypatch.delenv("IBL_SPFH_F64")
-    monkeypatch.setenv("IBL_SPFH_QCAP", "8")
-    over = instance_features_batch(ctx, b, 0.05)
+    with ctx.diag(spfh_f64=1):
+        ref = instance_features_batch(ctx, b, 0.05)
+    with ctx.diag(spfh_qcap=8):
+        over = instance_features_batch(ctx, b, 0.05)
     torch.cuda.synchronize()
     assert ctx.status() == 0
     assert float(ref.fpfh[:b.n].abs().sum()) > 0
@@ -130,9 +129,9 @@ def test_spfh_fp32_bins_with_fp64_for_undecided_pairs_equal_the_fp64_bins(ctx, m
     assert torch.equal(over.fpfh[:b.n], ref.fpfh[:b.n])
 
 
-def test_guess_threshold_selection_equals_the_two_pass_selection(ctx, monkeypatch):
+def test_guess_threshold_selection_equals_the_two_pass_selection(ctx):
     """round 3: the tile search collects the candidates below a GUESS of the k-th neighbour's distance in one pass and selects from that
-    list (tile_select_guess); IBL_KNN_NOGUESS=1 runs the two-pass histogram selection for every query: neighbour sets, normals, FPFH
+    list (tile_select_guess); the switch knn_noguess runs the two-pass histogram selection for every query: neighbour sets, normals, FPFH
     and colour gradients must agree bit for bit -- dense, sparse, tiny and two-object clouds alike"""
     from ibloc_amd.registration import CloudBatch, instance_features_batch, normals_fpfh_batch
     rng = np.random.default_rng(78)
@@ -143,9 +142,9 @@ def test_guess_threshold_selection_equals_the_two_pass_selection(ctx, monkeypatc
     b = CloudBatch.from_numpy(cs, ints)
     got = instance_features_batch(ctx, b, 0.05, grad_radius=0.15)
     n1, f1 = normals_fpfh_batch(ctx, b, 0.1, 30, 0.25, 100)
-    monkeypatch.setenv("IBL_KNN_NOGUESS", "1")
-    ref = instance_features_batch(ctx, b, 0.05, grad_radius=0.15)
-    n2, f2 = normals_fpfh_batch(ctx, b, 0.1, 30, 0.25, 100)
+    with ctx.diag(knn_noguess=1):
+        ref = instance_features_batch(ctx, b, 0.05, grad_radius=0.15)
+        n2, f2 = normals_fpfh_batch(ctx, b, 0.1, 30, 0.25, 100)
     torch.cuda.synchronize()
     assert ctx.status() == 0
     assert torch.equal(got.normals[:b.n], ref.normals[:b.n]) and torch.equal(got.fpfh[:b.n], ref.fpfh[:b.n])

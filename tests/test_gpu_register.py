@@ -114,9 +114,9 @@ def test_evaluate_batch_vs_oracle(ctx, scene):
     grid.close()
 
 
-def test_evaluate_pruned_scan_equals_the_full_scan_far_from_the_origin(ctx, monkeypatch):
+def test_evaluate_pruned_scan_equals_the_full_scan_far_from_the_origin(ctx):
     """round 4: the evaluation reads the query's own cell first and another cell of its +-threshold box only while the face it shares with
-    the own cell is nearer than the best distance so far (IBL_EVAL_FULLSCAN=1: every cell).  The bound must hold where floorf(x / cell)
+    the own cell is nearer than the best distance so far (switch eval_fullscan: every cell).  The bound must hold where floorf(x / cell)
     and the geometric cell faces disagree by rounding: points 240 m from the origin, queries on cell faces, outliers, an empty job"""
     from ibloc_amd.registration import MemGrid, evaluate_points
     rng = np.random.default_rng(91)
@@ -134,8 +134,8 @@ def test_evaluate_pruned_scan_equals_the_full_scan_far_from_the_origin(ctx, monk
     T[1][:3, 3] = [0.013, -0.007, 0.004]
     jb, je = [0, 0, 5], [len(det), len(det), 5]
     d_p, rmse_p, fit_p = evaluate_points(ctx, grid, det4, jb, je, T, 0.02)
-    monkeypatch.setenv("IBL_EVAL_FULLSCAN", "1")
-    d_f, rmse_f, fit_f = evaluate_points(ctx, grid, det4, jb, je, T, 0.02)
+    with ctx.diag(eval_fullscan=1):
+        d_f, rmse_f, fit_f = evaluate_points(ctx, grid, det4, jb, je, T, 0.02)
     torch.cuda.synchronize()
     assert torch.equal(d_p, d_f) and np.array_equal(rmse_p, rmse_f) and np.array_equal(fit_p, fit_f)
     assert 0.5 < fit_p[0] < 0.99 and fit_p[2] == 0
@@ -225,9 +225,10 @@ def test_instance_features_chunked_equals_single_pass(ctx):
 
 def test_matrix_core_feature_search_equals_valu_search(ctx):
     """the MFMA-filtered nearest-feature search (fp16 products with the norms folded in + exact recheck) against the full VALU scan it replaces
-    (IBL_FEAT_VALU=1): every output of the registration must be bit-identical -- the filter may only drop rows that cannot be
-    the exact minimum.  Includes a degenerate job (a cloud registered onto itself: every distance 0 is an exact tie)."""
-    import os
+    (switch feat_valu): every output of the registration must be bit-identical -- the filter may only drop rows that cannot be
+    the exact minimum.  Includes a degenerate job (a cloud registered onto itself: every distance 0 is an exact tie).
+    The forced overflow (feat_cand_cap=100) must really take the fallback: status bit 4 (IBL_ST_FEAT_REDONE, a call was redone with the
+    VALU search) is set after that call and clear after the default one."""
     from ibloc_amd.registration import CloudBatch, instance_features_batch, register_batch
     w = SynthWorld(9, pts_per_object=3000, E=1, D=8, seed=91, spacing=1.4)
     rng = np.random.default_rng(92)
@@ -252,14 +253,13 @@ def test_matrix_core_feature_search_equals_valu_search(ctx):
     assert (op[:, 33] == 8).all() and (op[:, 34] == 8).all() and torch.count_nonzero(op[:, 38:]).item() == 0
     assert ((op[:, 35] + op[:, 36]) * 8 - nrm).abs().max().item() <= 2.0 ** -20 * nrm.max().item()
     assert (op[:, 37] >= (1.0e-3 * nrm + 4.0e-3) * (1 - 1e-6)).all() and (op[:, 37] <= (1.0e-3 * nrm + 4.0e-3) * (1 + 2.0 ** -9) + 1e-6).all()
-    outs = []
-    for env in ({}, {"IBL_FEAT_VALU": "1"}, {"IBL_FEAT_CAND_CAP": "100"}):        # matrix cores | VALU scan | overflow -> fallback
-        os.environ.update(env)
-        try:
+    outs, redone = [], []
+    ctx.status()                                            # (clears the sticky bits of earlier tests)
+    for switches in ({}, {"feat_valu": 1}, {"feat_cand_cap": 100}):        # matrix cores | VALU scan | overflow -> fallback
+        with ctx.diag(**switches):
             outs.append(register_batch(ctx, det, mem, js, jt, 0.05, 1.5, 1.5, seed=3, job_id_base=40, det_features=fd, mem_features=fm))
-        finally:
-            for k in env:
-                os.environ.pop(k, None)
+        redone.append(ctx.status() & 16)
+    assert redone[0] == 0 and redone[2] == 16, redone
     # compact memory features (no resident fp16 operand rows: the search builds them from the fp32 rows as it stages them) -- the same
     # bits in the operands, so the same candidates and the same results
     fc = instance_features_batch(ctx, mem, 0.05, grad_radius=0.15, compact=True)

@@ -45,11 +45,8 @@ for seed in range(n_scenes):
     fd = instance_features_batch(ctx, det, 0.05)
     fm = instance_features_batch(ctx, mem, 0.05, grad_radius=0.15)
     fast = register_batch(ctx, det, mem, js, jt, 0.05, 1.5, 1.5, seed=seed, job_id_base=3, det_features=fd, mem_features=fm)
-    os.environ["IBL_FEAT_VALU"] = "1"
-    try:
+    with ctx.diag(feat_valu=1):
         slow = register_batch(ctx, det, mem, js, jt, 0.05, 1.5, 1.5, seed=seed, job_id_base=3)
-    finally:
-        os.environ.pop("IBL_FEAT_VALU", None)
     same = all(np.array_equal(fast[k], slow[k]) for k in ("T", "rmse", "fitness", "T_ransac", "ransac_stats", "means"))
     print(f"scene {seed}: spacing {spacing} pts {pts} jobs {len(js)} reuse {fast['reuse'].tolist()} -> {'identical' if same else 'DIFFERENT'}")
     bad += 0 if same else 1

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU: randomised cross-check of the fp32-guard-band SPFH path (pair_bins_f32 + fp64 queue, csrc/reg_knn.hip) against the all-fp64 evaluation
-(IBL_SPFH_F64=1) on clouds of many shapes: the FPFH rows (and normals) must be identical, bit for bit.  python tools/stress_spfh.py [rounds]"""
+(switch spfh_f64) on clouds of many shapes: the FPFH rows (and normals) must be identical, bit for bit.  python tools/stress_spfh.py [rounds]"""
 import os
 import sys
 
@@ -44,10 +44,9 @@ def main():
     for r in range(rounds):
         rng = np.random.default_rng(5000 + r)
         b = CloudBatch.from_numpy([shapes(rng) for _ in range(24)])
-        os.environ.pop("IBL_SPFH_F64", None)
         a = instance_features_batch(ctx, b, 0.05)
-        os.environ["IBL_SPFH_F64"] = "1"
-        c = instance_features_batch(ctx, b, 0.05)
+        with ctx.diag(spfh_f64=1):
+            c = instance_features_batch(ctx, b, 0.05)
         torch.cuda.synchronize()
         same = torch.equal(a.fpfh[:b.n], c.fpfh[:b.n]) and torch.equal(a.normals[:b.n], c.normals[:b.n])
         pts += b.n
@@ -55,7 +54,6 @@ def main():
             bad += 1
             d = (a.fpfh[:b.n] != c.fpfh[:b.n]).any(1).sum().item()
             print(f"round {r}: {d} of {b.n} FPFH rows differ")
-    os.environ.pop("IBL_SPFH_F64", None)
     print(f"{rounds} rounds, {pts} points: {'all identical' if not bad else str(bad) + ' rounds differ'} (status {ctx.status()})")
     sys.exit(1 if bad else 0)
 
