@@ -539,6 +539,29 @@ typedef struct ibl_memgrid ibl_memgrid;
 int ibl_memgrid_build(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, ibl_memgrid** out, void* stream);
 int ibl_memgrid_destroy(ibl_memgrid* grid);
 
+/* The same grid for a memory that GROWS while it is resident (live memory): same keys, same hash, same arrays as ibl_memgrid_build
+ * gives for the same points -- every evaluation entry point below takes either kind.
+ *   Ownership: the device arrays belong to the grid (hipMalloc), not to the context arena; they are sized for n + reserve_points
+ *   points and freed by ibl_memgrid_destroy, so such a grid survives ibl_reg_ctx_reset and must be destroyed before the process
+ *   gives the device up.  The arena is used as scratch only (the size of an arena build, released on return).
+ *   ibl_memgrid_append merges n_new further points (new_pts4 [dev] n_new x 4 floats; they count as the points n .. n + n_new - 1)
+ *   into the grid: afterwards it holds what ibl_memgrid_build returns for the old points followed by the new ones, array for array
+ *   (the sort is stable and a cell keeps its points in index order, so the merge "old before new" is that sort).  One pass over
+ *   the resident points into the second buffer of a ping-pong pair (allocated by the first append), cell arrays and table
+ *   rebuilt; buffers that no longer fit grow by a factor of 1.5, the table keeps the rule of the build (smallest power of two
+ *   >= 3 x cells, >= 1024).  Scratch: 16 bytes per resident point + 24 per new point from ctx's arena, released on return.
+ *   n_new == 0 is a no-op (IBL_OK); n + n_new <= 0x7FFFFFF0; a grid of ibl_memgrid_build is refused with IBL_ERR_ARG and nothing
+ *   is launched.  A failed append that returns IBL_ERR_ARG, the arena error or an allocation error leaves the grid as it was.
+ *   Synchronisation: both calls synchronise `stream` before they return.  An append frees and replaces arrays of the grid: no
+ *   evaluation that uses the grid may be in flight on ANY other stream during the call, and none may be issued until it returns.
+ * ibl_memgrid_info: n, occupied cells, table slots, point capacity of the current buffer and ustart[n_cells] (any pointer may be
+ * NULL; asking for ustart_end reads it from the device and synchronises `stream`). */
+int ibl_memgrid_build_owned(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, int64_t reserve_points, ibl_memgrid** out,
+                            void* stream);
+int ibl_memgrid_append(ibl_reg_ctx* ctx, ibl_memgrid* grid, const float* new_pts4, int64_t n_new, void* stream);
+int ibl_memgrid_info(const ibl_memgrid* grid, int64_t* n, int32_t* n_cells, int64_t* table_slots, int64_t* point_capacity,
+                     int32_t* ustart_end, void* stream);
+
 /* evaluate_transform(all_detected_pcd, all_memory_pcd, T) for n_jobs candidates: job j transforms the detected
  * points [job_begin[j], job_end[j]) of det_pts4 [dev] by T_global[j] (host, 16 doubles row-major) and looks for
  * the nearest memory point within `threshold`.  rmse_out / fitness_out: HOST arrays (the call synchronises). */

@@ -74,6 +74,9 @@ _SIGS = {
                                          C.c_double, C.c_uint64, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ibl_memgrid_build": (C.c_int, [vp, vp, C.c_int64, C.c_double, C.POINTER(vp), vp]),
     "ibl_memgrid_destroy": (C.c_int, [vp]),
+    "ibl_memgrid_build_owned": (C.c_int, [vp, vp, C.c_int64, C.c_double, C.c_int64, C.POINTER(vp), vp]),
+    "ibl_memgrid_append": (C.c_int, [vp, vp, vp, C.c_int64, vp]),
+    "ibl_memgrid_info": (C.c_int, [vp, C.POINTER(C.c_int64), c_i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_i32p, vp]),
     "ibl_evaluate_batch": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp]),
     "ibl_register_evaluate_batch": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp,
                                               C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_uint64, C.c_uint32,

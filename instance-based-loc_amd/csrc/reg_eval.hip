@@ -24,6 +24,7 @@ struct ibl_memgrid {
     float cell, inv;
     int64_t n;
     int n_cells;
+    int owned;                      // 0: arrays in the context arena; 1: an ibl_memgrid_live (below) that owns its device memory
     unsigned long long hmask;
     float4* sorted;                 // points in cell order
     unsigned long long* ukeys;      // unique cell keys
@@ -139,8 +140,243 @@ extern "C" int ibl_memgrid_build(ibl_reg_ctx* ctx, const float* mem_pts4, int64_
     return IBL_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// live grid: the same structure in device memory of its own, with room to grow (ibl_memgrid_build_owned / ibl_memgrid_append)
+// ------------------------------------------------------------------------------------------------
+// An owned grid is the arena grid's struct (what the evaluation kernels take by value) plus the book-keeping of its buffers: a
+// ping-pong pair for the points (an append merges buf[cur] and the new points into buf[1 - cur]), cell arrays and a table with their
+// own capacities.  buf[1 - cur] is allocated by the first append that needs it.
+struct ibl_memgrid_live : ibl_memgrid {
+    float4* buf[2] = {nullptr, nullptr};
+    int64_t buf_cap[2] = {0, 0};        // points
+    int cur = 0;
+    int64_t cell_cap = 0;               // ukeys holds cell_cap, ustart cell_cap + 1 entries
+    unsigned long long tab_cap = 0;     // slots of tkeys / tvals
+};
+
+static void mg_live_free(ibl_memgrid_live* g) {
+    (void)hipFree(g->buf[0]); (void)hipFree(g->buf[1]); (void)hipFree(g->ukeys); (void)hipFree(g->ustart);
+    (void)hipFree(g->tkeys); (void)hipFree(g->tvals);
+    delete g;
+}
+
+extern "C" int ibl_memgrid_build_owned(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, int64_t reserve_points,
+                                       ibl_memgrid** out, void* stream) {
+    if (!ctx || !mem_pts4 || !out || n <= 0 || n > 0x7FFFFFF0ll || cell <= 0 || reserve_points < 0 || reserve_points > 0x7FFFFFF0ll - n)
+        return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_build_owned: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    // the arena build, under a mark: its arrays are copied out and its arena space is released on return -- one build, one set of values
+    ArenaMark scratch(ctx);
+    ibl_memgrid* a = nullptr;
+    const int st = ibl_memgrid_build(ctx, mem_pts4, n, cell, &a, stream);
+    if (st != IBL_OK) return st;
+    std::unique_ptr<ibl_memgrid> arena_grid(a);
+    ibl_memgrid_live* g = new ibl_memgrid_live();
+    static_cast<ibl_memgrid&>(*g) = *a;
+    g->owned = 1;
+    g->sorted = nullptr; g->ukeys = nullptr; g->ustart = nullptr; g->tkeys = nullptr; g->tvals = nullptr;
+    const unsigned long long H = a->hmask + 1;
+    g->buf_cap[0] = n + reserve_points;
+    g->cell_cap = a->n_cells + std::min<int64_t>(reserve_points, a->n_cells / 2);
+    g->tab_cap = H;
+    hipError_t e = hipMalloc(&g->buf[0], sizeof(float4) * (size_t)g->buf_cap[0]);
+    if (e == hipSuccess) e = hipMalloc(&g->ukeys, sizeof(unsigned long long) * (size_t)g->cell_cap);
+    if (e == hipSuccess) e = hipMalloc(&g->ustart, sizeof(int) * (size_t)(g->cell_cap + 1));
+    if (e == hipSuccess) e = hipMalloc(&g->tkeys, sizeof(unsigned long long) * H);
+    if (e == hipSuccess) e = hipMalloc(&g->tvals, sizeof(int) * H);
+    if (e == hipSuccess) e = hipMemcpyAsync(g->buf[0], a->sorted, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(g->ukeys, a->ukeys, sizeof(unsigned long long) * (size_t)a->n_cells, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(g->ustart, a->ustart, sizeof(int) * (size_t)(a->n_cells + 1), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(g->tkeys, a->tkeys, sizeof(unsigned long long) * H, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(g->tvals, a->tvals, sizeof(int) * H, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        mg_live_free(g);
+        return ibl_set_error(IBL_ERR_HIP, "ibl_memgrid_build_owned: %s", hipGetErrorString(e));
+    }
+    g->sorted = g->buf[0];
+    *out = g;
+    return IBL_OK;
+}
+
 extern "C" int ibl_memgrid_destroy(ibl_memgrid* g) {
+    if (g && g->owned) { mg_live_free(static_cast<ibl_memgrid_live*>(g)); return IBL_OK; }
     delete g;       // device memory belongs to the context arena
+    return IBL_OK;
+}
+
+extern "C" int ibl_memgrid_info(const ibl_memgrid* g, int64_t* n, int32_t* n_cells, int64_t* table_slots, int64_t* point_capacity,
+                                int32_t* ustart_end, void* stream) {
+    if (!g) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_info: grid is null");
+    if (n) *n = g->n;
+    if (n_cells) *n_cells = g->n_cells;
+    if (table_slots) *table_slots = (int64_t)(g->hmask + 1);
+    if (point_capacity) {
+        const ibl_memgrid_live* l = g->owned ? static_cast<const ibl_memgrid_live*>(g) : nullptr;
+        *point_capacity = l ? l->buf_cap[l->cur] : g->n;
+    }
+    if (ustart_end) {
+        IBL_HIP_CHECK(hipMemcpyAsync(ustart_end, g->ustart + g->n_cells, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+        IBL_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    }
+    return IBL_OK;
+}
+
+// first index of the sorted keys[0, n) whose key is not below k (strict = 0) / is above k (strict = 1)
+__device__ __forceinline__ int mg_bound(const unsigned long long* __restrict__ keys, int n, unsigned long long k, int strict) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        const unsigned long long v = keys[mid];
+        if (strict ? v <= k : v < k) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// Stable merge, old side: point i of the cell-ordered old points moves up by the number of new points in cells before its own (new
+// points of its own cell follow it: they have the higher original indices).  One thread per point, 16-byte load and store; the new
+// keys are a few thousand and stay in cache.  The merged keys go along for the cell boundaries.
+__global__ __launch_bounds__(256) void ibl_mg_merge_old_kernel(const float4* __restrict__ src, int64_t n_old, float inv,
+                                                               const unsigned long long* __restrict__ nkeys, int n_new,
+                                                               float4* __restrict__ dst, unsigned long long* __restrict__ mkeys) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_old) return;
+    const float4 p = src[i];
+    const unsigned long long k = mg_key((int)floorf(p.x * inv), (int)floorf(p.y * inv), (int)floorf(p.z * inv));
+    const int64_t d = i + mg_bound(nkeys, n_new, k, 0);
+    dst[d] = p;
+    mkeys[d] = k;
+}
+
+// new side: sorted new point j moves up by the number of old points in cells up to and including its own, read from the old cell arrays
+__global__ __launch_bounds__(256) void ibl_mg_merge_new_kernel(const float4* __restrict__ pts, const int* __restrict__ order,
+                                                               const unsigned long long* __restrict__ nkeys, int n_new,
+                                                               const unsigned long long* __restrict__ ukeys, const int* __restrict__ ustart,
+                                                               int n_cells, float4* __restrict__ dst, unsigned long long* __restrict__ mkeys) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n_new) return;
+    const unsigned long long k = nkeys[j];
+    const int64_t d = (int64_t)j + ustart[mg_bound(ukeys, n_cells, k, 1)];
+    dst[d] = pts[order[j]];
+    mkeys[d] = k;
+}
+
+__global__ __launch_bounds__(256) void ibl_mg_merged_cells_kernel(const unsigned long long* __restrict__ mkeys, const int* __restrict__ head,
+                                                                  const int* __restrict__ head_scan, int64_t n,
+                                                                  unsigned long long* __restrict__ ukeys, int* __restrict__ ustart) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (head[i]) { const int c = head_scan[i]; ukeys[c] = mkeys[i]; ustart[c] = (int)i; }
+}
+
+// as ibl_mg_insert_kernel, with the probe walk bounded by the table: a key that found no slot (cannot happen at <= 1 / 3 load) is reported
+__global__ __launch_bounds__(256) void ibl_mg_insert_bounded_kernel(const unsigned long long* __restrict__ ukeys, int n_cells,
+                                                                    unsigned long long hmask, unsigned long long* __restrict__ tkeys,
+                                                                    int* __restrict__ tvals, int* __restrict__ failed) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n_cells) return;
+    const unsigned long long k = ukeys[c];
+    unsigned long long h = mg_hash(k) & hmask;
+    for (unsigned long long probe = 0; probe <= hmask; ++probe) {
+        const unsigned long long prev = atomicCAS(&tkeys[h], MG_EMPTY, k);
+        if (prev == MG_EMPTY) { tvals[h] = c; return; }
+        h = (h + 1) & hmask;
+    }
+    atomicExch(failed, 1);
+}
+
+extern "C" int ibl_memgrid_append(ibl_reg_ctx* ctx, ibl_memgrid* grid, const float* new_pts4, int64_t n_new, void* stream) {
+    if (!ctx || !grid || n_new < 0 || (n_new > 0 && !new_pts4)) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_append: bad argument");
+    if (!grid->owned) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_append: the grid lives in the context arena (build it with ibl_memgrid_build_owned)");
+    if (n_new == 0) return IBL_OK;
+    ibl_memgrid_live* g = static_cast<ibl_memgrid_live*>(grid);
+    const int64_t n_old = g->n, n = n_old + n_new;
+    if (n > 0x7FFFFFF0ll) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_append: more than 0x7FFFFFF0 points");
+    hipStream_t s = (hipStream_t)stream;
+    const float4* P = reinterpret_cast<const float4*>(new_pts4);
+    ArenaMark scratch(ctx);
+    unsigned long long *keys, *nkeys, *mkeys; int *vals, *order, *head, *hscan, *failed; unsigned char* tmp;
+    IBL_ARENA(keys, unsigned long long, n_new);
+    IBL_ARENA(nkeys, unsigned long long, n_new);
+    IBL_ARENA(vals, int, n_new);
+    IBL_ARENA(order, int, n_new);
+    IBL_ARENA(mkeys, unsigned long long, n);
+    IBL_ARENA(head, int, n + 1);
+    IBL_ARENA(hscan, int, n + 1);
+    IBL_ARENA(failed, int, 1);
+    size_t t1 = 0, t2 = 0;
+    IBL_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, keys, nkeys, vals, order, (int)n_new, 0, 63, s));
+    IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, head, hscan, (int)n, s));
+    IBL_ARENA(tmp, unsigned char, (int64_t)std::max(t1, t2) + 256);
+    // the other half of the ping-pong pair: grown by 1.5 when the merged points no longer fit
+    const int o = 1 - g->cur;
+    if (g->buf_cap[o] < n) {
+        const int64_t cap = std::min<int64_t>(0x7FFFFFF0ll, std::max<int64_t>(n, g->buf_cap[g->cur] + g->buf_cap[g->cur] / 2));
+        IBL_HIP_CHECK(hipStreamSynchronize(s));
+        (void)hipFree(g->buf[o]);
+        g->buf[o] = nullptr; g->buf_cap[o] = 0;
+        IBL_HIP_CHECK(hipMalloc(&g->buf[o], sizeof(float4) * (size_t)cap));
+        g->buf_cap[o] = cap;
+    }
+    float4* dst = g->buf[o];
+    // key and sort the new points (stable: equal keys keep their index order), merge both sides into dst
+    const unsigned nb_new = (unsigned)((n_new + 255) / 256), nb_old = (unsigned)((n_old + 255) / 256), nb = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(ibl_mg_key_kernel, dim3(nb_new), dim3(256), 0, s, P, n_new, g->inv, keys, vals);
+    IBL_LAUNCH_CHECK();
+    IBL_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, t1, keys, nkeys, vals, order, (int)n_new, 0, 63, s));
+    hipLaunchKernelGGL(ibl_mg_merge_old_kernel, dim3(nb_old), dim3(256), 0, s, g->sorted, n_old, g->inv, nkeys, (int)n_new, dst, mkeys);
+    IBL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ibl_mg_merge_new_kernel, dim3(nb_new), dim3(256), 0, s, P, order, nkeys, (int)n_new, g->ukeys, g->ustart, g->n_cells,
+                       dst, mkeys);
+    IBL_LAUNCH_CHECK();
+    // cells of the merged order
+    hipLaunchKernelGGL(ibl_mg_heads_kernel, dim3(nb), dim3(256), 0, s, mkeys, n, head);
+    IBL_LAUNCH_CHECK();
+    IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, t2, head, hscan, (int)n, s));
+    int last_scan = 0, last_head = 0;
+    IBL_HIP_CHECK(hipMemcpyAsync(&last_scan, hscan + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+    IBL_HIP_CHECK(hipMemcpyAsync(&last_head, head + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+    IBL_HIP_CHECK(hipStreamSynchronize(s));         // (the merge has read the old cell arrays: they may be replaced now)
+    const int n_cells = last_scan + last_head;
+    // every allocation the new state needs before any of the old state is overwritten: a failure here leaves the grid as it was
+    unsigned long long H = 1024;
+    while (H < (unsigned long long)n_cells * 3) H <<= 1;
+    unsigned long long* ukeys = g->ukeys; int* ustart = g->ustart; int64_t cell_cap = g->cell_cap;
+    unsigned long long* tkeys = g->tkeys; int* tvals = g->tvals;
+    if (n_cells > cell_cap) {
+        cell_cap = std::max<int64_t>(n_cells, cell_cap + cell_cap / 2);
+        ukeys = nullptr; ustart = nullptr;
+        hipError_t e = hipMalloc(&ukeys, sizeof(unsigned long long) * (size_t)cell_cap);
+        if (e == hipSuccess) e = hipMalloc(&ustart, sizeof(int) * (size_t)(cell_cap + 1));
+        if (e != hipSuccess) { (void)hipFree(ukeys); return ibl_set_error(IBL_ERR_HIP, "ibl_memgrid_append: %s", hipGetErrorString(e)); }
+    }
+    if (H > g->tab_cap) {
+        tkeys = nullptr; tvals = nullptr;
+        hipError_t e = hipMalloc(&tkeys, sizeof(unsigned long long) * H);
+        if (e == hipSuccess) e = hipMalloc(&tvals, sizeof(int) * H);
+        if (e != hipSuccess) {
+            (void)hipFree(tkeys);
+            if (ukeys != g->ukeys) { (void)hipFree(ukeys); (void)hipFree(ustart); }
+            return ibl_set_error(IBL_ERR_HIP, "ibl_memgrid_append: %s", hipGetErrorString(e));
+        }
+    }
+    if (ukeys != g->ukeys) { (void)hipFree(g->ukeys); (void)hipFree(g->ustart); g->ukeys = ukeys; g->ustart = ustart; g->cell_cap = cell_cap; }
+    if (tkeys != g->tkeys) { (void)hipFree(g->tkeys); (void)hipFree(g->tvals); g->tkeys = tkeys; g->tvals = tvals; g->tab_cap = H; }
+    g->sorted = dst; g->cur = o; g->n = n; g->n_cells = n_cells; g->hmask = H - 1;
+    hipLaunchKernelGGL(ibl_mg_merged_cells_kernel, dim3(nb), dim3(256), 0, s, mkeys, head, hscan, n, g->ukeys, g->ustart);
+    IBL_LAUNCH_CHECK();
+    const int nn = (int)n;
+    IBL_HIP_CHECK(hipMemcpyAsync(g->ustart + n_cells, &nn, sizeof(int), hipMemcpyHostToDevice, s));
+    // the table by the build's rule (smallest power of two >= 3 n_cells, >= 1024), refilled: the cell indices have shifted
+    IBL_HIP_CHECK(hipMemsetAsync(g->tkeys, 0xFF, sizeof(unsigned long long) * H, s));
+    IBL_HIP_CHECK(hipMemsetAsync(failed, 0, sizeof(int), s));
+    hipLaunchKernelGGL(ibl_mg_insert_bounded_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, s, g->ukeys, n_cells, g->hmask, g->tkeys,
+                       g->tvals, failed);
+    IBL_LAUNCH_CHECK();
+    int h_failed = 0;
+    IBL_HIP_CHECK(hipMemcpyAsync(&h_failed, failed, sizeof(int), hipMemcpyDeviceToHost, s));
+    IBL_HIP_CHECK(hipStreamSynchronize(s));
+    if (h_failed) return ibl_set_error(IBL_ERR_OVERFLOW, "ibl_memgrid_append: the cell table is full");
     return IBL_OK;
 }
 

@@ -29,7 +29,7 @@ from scipy.spatial.transform import Rotation
 from . import match
 from .assign import K_HI, K_LO, assign_batch, assign_candidates
 from .parallel import ShardExchange, shard_range, sharded_candidates
-from .registration import (CloudBatch, InstanceFeatures, MemGrid, RegContext, evaluate_batch, evaluate_points,
+from .registration import (CloudBatch, InstanceFeatures, MemGrid, RegContext, evaluate_batch, evaluate_points, grow_rows,
                            instance_features_batch, radius_outlier_batch, register_batch, register_evaluate_batch)
 
 IBL_ST_GRID_OVERFLOW = 1          # ibl_reg_ctx_status bits (include/ibloc.h)
@@ -49,11 +49,18 @@ class MemoryShard:
     shard=(rank, world): this rank keeps the embeddings of the instances [lo, hi) = parallel.shard_range(M, rank, world) only;
     instance indices everywhere else remain global.  The clouds stay replicated unless shard_clouds=True: then this rank also keeps
     only the clouds, cached features and evaluation grid of [lo, hi) (`clouds` / `colors` / `intensities` may be the full lists or just
-    that range), registration jobs are routed between the ranks and the evaluation is reduced over them (routing.py)."""
+    that range), registration jobs are routed between the ranks and the evaluation is reduced over them (routing.py).
+    live=True (unsharded memories): the memory can grow while it is resident -- `append` adds instances without rebuilding anything.
+    The embeddings, clouds and instance features then sit in buffers with room for reserve_points further points (default: an
+    eighth of the memory + 65 536) and reserve_rows further embedding rows, and the spatial hash owns its device memory
+    (ibl_memgrid_build_owned) instead of living in the arena.  Everything computed is the same as with live=False."""
 
     def __init__(self, ctx: RegContext, embeddings, clouds=None, colors=None, intensities=None, eval_threshold=0.02, device="cuda",
-                 shard=None, shard_clouds=False, compact_features=False):
+                 shard=None, shard_clouds=False, compact_features=False, live=False, reserve_points=None, reserve_rows=None):
         self.ctx = ctx
+        self.live = bool(live)
+        if self.live and shard is not None:
+            raise ValueError("a live memory cannot be sharded")
         self.compact_features = bool(compact_features)     # resident instance features without their fp16 operand rows (168 B / point)
         self.device = torch.device(device)
         self.M = len(embeddings)
@@ -69,6 +76,13 @@ class MemoryShard:
         else:
             self.mem_emb = torch.zeros((0, dim), dtype=torch.float32, device=self.device)
         self.emb_offsets = torch.from_numpy(self.emb_offsets_host).to(self.device)
+        self._emb_buf = self.mem_emb
+        if self.live:
+            rows = len(raw) // 8 + 1024 if reserve_rows is None else int(reserve_rows)
+            self._emb_buf = torch.empty((len(raw) + rows, dim), dtype=torch.float32, device=self.device)
+            self._emb_buf[:len(raw)].copy_(self.mem_emb)
+            self.mem_emb = self._emb_buf[:len(raw)]
+        self.reserve_points = 0
         self.eval_threshold = eval_threshold
         self._features = {}
         self.clouds = self.grid = None
@@ -83,20 +97,80 @@ class MemoryShard:
         if clouds is not None:
             if intensities is None:
                 intensities = [intensity_from_colors(c) for c in colors] if colors is not None else None
-            self.clouds = CloudBatch.from_numpy(clouds, intensities, device=device)
-            self.grid = MemGrid(ctx, self.clouds.pts4, cell=2 * eval_threshold)
+            if not self.live:
+                self.clouds = CloudBatch.from_numpy(clouds, intensities, device=device)
+                self.grid = MemGrid(ctx, self.clouds.pts4, cell=2 * eval_threshold)
+            else:
+                n_pts = sum(len(c) for c in clouds)
+                self.reserve_points = n_pts // 8 + 65536 if reserve_points is None else int(reserve_points)
+                self.clouds = CloudBatch.from_numpy(clouds, intensities, device=device, reserve_points=self.reserve_points)
+                self.grid = MemGrid(ctx, self.clouds.pts4, cell=2 * eval_threshold, live=True, reserve_points=self.reserve_points)
 
     def features(self, voxel_size, local_dist_factor):
         """Normals, FPFH and colour gradients of every memory instance for these registration parameters: computed on first
         use, then resident in HBM (1.3 GB per 1 000 instances of 5 000 points; 0.84 GB with compact_features) for every later query."""
         key = (float(voxel_size), float(local_dist_factor))
         if key not in self._features:
-            self._features[key] = instance_features_batch(self.ctx, self.clouds, voxel_size, 2.0 * (voxel_size * local_dist_factor),
-                                                          compact=self.compact_features)
+            if not self.live:
+                self._features[key] = instance_features_batch(self.ctx, self.clouds, voxel_size, 2.0 * (voxel_size * local_dist_factor),
+                                                              compact=self.compact_features)
+            else:       # room behind the rows for what is left of the clouds' own headroom
+                room = max(self.clouds._buf.shape[0] - self.clouds.n, 0)
+                self._features[key] = instance_features_batch(self.ctx, self.clouds, voxel_size, 2.0 * (voxel_size * local_dist_factor),
+                                                              compact=self.compact_features, reserve_points=room)
         return self._features[key]
 
+    def append(self, embeddings, clouds=None, colors=None, intensities=None):
+        """Adds the instances M .. M + k - 1 to a live memory: `embeddings` a list of k (E_i, D) arrays, `clouds` / `colors` /
+        `intensities` lists of k arrays as the constructor takes them.  Their embeddings are normalised and attached, their clouds are
+        attached and merged into the spatial hash, and their instance features are computed -- on the new clouds alone -- and attached
+        to every feature set already resident (each with its own voxel size and local distance factor).  The state afterwards is, array
+        for array, that of a MemoryShard constructed from all instances; nothing resident is recomputed, and only the new rows are
+        copied unless a buffer has run out of headroom (it then grows by 1.5).  Synchronises the device first: no localisation may
+        be in flight.  Raises ValueError, before anything is touched, for a sharded or non-live memory, clouds given to an embedding-only
+        memory (or withheld from one with clouds), a count mismatch or another embedding dimension."""
+        if self.shard is not None:
+            raise ValueError("MemoryShard.append: sharded memories cannot grow while resident")
+        if not self.live:
+            raise ValueError("MemoryShard.append: construct the shard with live=True")
+        if (clouds is None) != (self.clouds is None):
+            raise ValueError("MemoryShard.append: an embedding-only memory takes no clouds, a memory with clouds needs them")
+        embs = [np.asarray(e, dtype=np.float32) for e in embeddings]
+        dim = self.mem_emb.shape[1]
+        if any(e.ndim != 2 or e.shape[1] != dim or len(e) == 0 for e in embs):
+            raise ValueError(f"MemoryShard.append: every instance needs an (E, {dim}) array of embeddings")
+        if clouds is not None:
+            if len(clouds) != len(embs) or any(x is not None and len(x) != len(embs) for x in (colors, intensities)):
+                raise ValueError("MemoryShard.append: as many clouds (colours, intensities) as instances")
+            if any(np.asarray(c).ndim != 2 or np.asarray(c).shape[1] != 3 or len(c) == 0 for c in clouds):
+                raise ValueError("MemoryShard.append: every cloud is a non-empty (n, 3) array")
+            if self.clouds.n + sum(len(c) for c in clouds) > 0x7FFFFFF0:
+                raise ValueError("MemoryShard.append: more than 0x7FFFFFF0 memory points")
+        if not embs:
+            return
+        torch.cuda.synchronize(self.device)
+        if clouds is not None:
+            if intensities is None:
+                intensities = [intensity_from_colors(c) for c in colors] if colors is not None else None
+            new = CloudBatch.from_numpy(clouds, intensities, device=self.device)
+            # the new instances' features first, from their own batch: nothing resident has changed if this raises
+            new_feat = {key: instance_features_batch(self.ctx, new, key[0], 2.0 * (key[0] * key[1]), compact=self.compact_features)
+                        for key in self._features}
+            self.grid.append(new.pts4)
+            self.clouds.append(new)
+            for key, feat in self._features.items():
+                feat.append(new_feat[key])
+        rows = match.normalize_rows(torch.from_numpy(np.ascontiguousarray(np.concatenate(embs))).to(self.device))
+        self._emb_buf, self.mem_emb = grow_rows(self._emb_buf, self.mem_emb.shape[0], rows)
+        counts = np.cumsum([len(e) for e in embs]).astype(np.int32)
+        self.emb_offsets_host = np.concatenate([self.emb_offsets_host, self.emb_offsets_host[-1] + counts]).astype(np.int32)
+        self.emb_offsets = torch.from_numpy(self.emb_offsets_host).to(self.device)
+        self.M += len(embs)
+        self.hi = self.M
+        torch.cuda.synchronize(self.device)
+
     def close(self):
-        """Frees the host side of the spatial hash (the device side lives in the context arena)."""
+        """Frees the host side of the spatial hash (the device side lives in the context arena; a live memory's hash frees its own)."""
         if self.grid is not None:
             self.grid.close()
             self.grid = None

@@ -75,6 +75,10 @@ class ObjectMemory():
         self.dataset_floor_thickness = dataset_floor_thickness
         self.iou_func = None            # (points_i, points_j) -> IoU for _recluster_IoU; the reference's Objectron IoU is third-party
         self.iou_backend = "host"       # default measure of _recluster_IoU: "host" pair loop, or "device" (boxes on host threads, pairs on the GPU)
+        # live_memory: add_object / process_detections after a localise() attach the new instances to the resident memory (embeddings,
+        # clouds, instance features, spatial hash: MemoryShard.append) instead of discarding it; False rebuilds it at the next query, as
+        # every other mutation does.  Same results either way.
+        self.live_memory = True
         self.memory = []
         self.floors = None
         self._ctx = RegContext(arena_bytes)
@@ -93,7 +97,21 @@ class ObjectMemory():
         info.embeddings = embs
         info._compute_means()
         self.memory.append(info)
-        self._engine = None
+        self._appended([info])
+
+    def _appended(self, infos):
+        """`infos` were appended to self.memory and nothing else changed: a resident live memory takes them in, otherwise the engine is
+        dropped and the next query rebuilds it"""
+        if self._engine is None or not self.live_memory or not self._shard.live:
+            self._engine = None
+            return
+        try:
+            self._shard.append([np.stack(m.embeddings).astype(np.float32) for m in infos],
+                               [np.asarray(m.pointcloud.points) for m in infos],
+                               colors=[np.asarray(m.pointcloud.colors) for m in infos])
+        except Exception:
+            self._engine = None          # whatever state the shard is in, the next query rebuilds it from self.memory
+            raise
 
     # ---- memory build (object_memory.py:163-256) ----------------------------------------------------------
     def _log(self, *a):
@@ -112,6 +130,7 @@ class ObjectMemory():
             nq = np.linalg.norm(q)
             pose[3:] = q if nq == 0 else q / nq
             obj_clouds = [(np.asarray(p) + np.random.normal(0, depth_noise, np.asarray(p).shape), c) for p, c in obj_clouds]
+        added = []
         for phrase, emb, (p, c) in zip(obj_phrases, embs, [(transform_points(p, pose), c) for p, c in obj_clouds]):
             if len(p) < min_points:
                 self._log(f"\t\tSkipping as number of points {len(p)} < min_points = {min_points}.")
@@ -121,7 +140,9 @@ class ObjectMemory():
                 self.floors = info if self.floors is None else self.floors + info
             else:
                 self.memory.append(info)
-        self._engine = None
+                added.append(info)
+        if added:                        # (the floor is not part of the resident memory)
+            self._appended(added)
 
     def process_image(self, rgb_image_path, depth_image_path, pose, consider_floor, outlier_removal_config=DEFAULT_OUTLIER_REMOVAL_CONFIG,
                       add_noise=False, pose_noise={'trans': 0.0005, 'rot': 0.0005}, depth_noise=0.003, min_points=500,
@@ -324,6 +345,8 @@ class ObjectMemory():
         self._engine = None
 
     def _get_engine(self):
+        if self._engine is not None and self._shard.M != len(self.memory):      # the list was changed behind the resident memory's back
+            self._engine = None
         if self._engine is None:
             if not self.memory:
                 raise RuntimeError("object memory is empty")
@@ -332,7 +355,7 @@ class ObjectMemory():
             self._ctx.reset()
             shard = self._shard = MemoryShard(self._ctx, [np.stack(m.embeddings).astype(np.float32) for m in self.memory],
                                 [np.asarray(m.pointcloud.points) for m in self.memory],
-                                colors=[np.asarray(m.pointcloud.colors) for m in self.memory], device=self.device)
+                                colors=[np.asarray(m.pointcloud.colors) for m in self.memory], device=self.device, live=True)
             self._engine = LocaliseEngine(shard)
         return self._engine
 

@@ -70,12 +70,25 @@ class RegContext:
                 self.diag_set(name, value)
 
 
+def grow_rows(buf: torch.Tensor, n_used: int, rows: torch.Tensor):
+    """Rows appended to a device buffer with headroom (live memory): `rows` are copied behind the first n_used rows of `buf`; a buffer
+    that is too small is replaced by one 1.5 times as large (one copy of the used rows).  Returns (buffer, view of its used rows)."""
+    n = n_used + rows.shape[0]
+    if n > buf.shape[0]:
+        grown = torch.empty((max(n, buf.shape[0] + buf.shape[0] // 2),) + tuple(buf.shape[1:]), dtype=buf.dtype, device=buf.device)
+        grown[:n_used].copy_(buf[:n_used])
+        buf = grown
+    buf[n_used:n].copy_(rows)
+    return buf, buf[:n]
+
+
 class CloudBatch:
     """Packed clouds on the device."""
 
     def __init__(self, pts4: torch.Tensor, seg_off_host: np.ndarray):
         assert pts4.is_cuda and pts4.dtype == torch.float32 and pts4.dim() == 2 and pts4.shape[1] == 4 and pts4.is_contiguous()
         self.pts4 = pts4
+        self._buf = pts4                 # backing buffer; longer than pts4 once the batch has headroom (from_numpy reserve_points, append)
         self.seg_off_host = np.ascontiguousarray(seg_off_host, dtype=np.int32)
         assert self.seg_off_host[-1] == pts4.shape[0]
         self.seg_off = torch.from_numpy(self.seg_off_host).to(pts4.device)
@@ -89,8 +102,9 @@ class CloudBatch:
         return int(self.seg_off_host[-1])
 
     @staticmethod
-    def from_numpy(clouds, intensities=None, device="cuda"):
-        """clouds: list of (n_i, 3) arrays; intensities: list of (n_i,) or None (zeros)."""
+    def from_numpy(clouds, intensities=None, device="cuda", reserve_points=0):
+        """clouds: list of (n_i, 3) arrays; intensities: list of (n_i,) or None (zeros).  reserve_points: room for that many further
+        points behind the clouds (`append` then copies only what it adds)."""
         sizes = [len(c) for c in clouds]
         off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
         p4 = np.zeros((int(off[-1]), 4), dtype=np.float32)
@@ -98,7 +112,25 @@ class CloudBatch:
             p4[off[i]:off[i + 1], :3] = np.asarray(c, dtype=np.float32)
             if intensities is not None:
                 p4[off[i]:off[i + 1], 3] = np.asarray(intensities[i], dtype=np.float32)
-        return CloudBatch(torch.from_numpy(p4).to(device), off)
+        if reserve_points <= 0:
+            return CloudBatch(torch.from_numpy(p4).to(device), off)
+        buf = torch.empty((len(p4) + int(reserve_points), 4), dtype=torch.float32, device=device)
+        buf[:len(p4)].copy_(torch.from_numpy(p4))
+        batch = CloudBatch(buf[:len(p4)], off)
+        batch._buf = buf
+        return batch
+
+    def append(self, clouds, intensities=None):
+        """Further clouds behind the last one (segments n_seg ..): `clouds` / `intensities` as `from_numpy` takes them, or a CloudBatch
+        on the same device.  Only the new points are copied unless the buffer has to grow (by 1.5).  `pts4` and `seg_off` are NEW
+        tensor objects afterwards (pts4 a longer view of the same buffer when it did not grow)."""
+        new = clouds if isinstance(clouds, CloudBatch) else CloudBatch.from_numpy(clouds, intensities, device=self.pts4.device)
+        if int(self.seg_off_host[-1]) + new.n > 0x7FFFFFF0:
+            raise ValueError("more than 0x7FFFFFF0 points in a cloud batch")
+        self._buf, self.pts4 = grow_rows(self._buf, self.n, new.pts4[:new.n])
+        self.seg_off_host = np.concatenate([self.seg_off_host, self.seg_off_host[-1] + new.seg_off_host[1:]]).astype(np.int32)
+        self.seg_off = torch.from_numpy(self.seg_off_host).to(self.pts4.device)
+        return new
 
 
 def unproject_masks(ctx: RegContext, depth: torch.Tensor, rgb: torch.Tensor, masks: torch.Tensor, fx: float, fy: float,
@@ -177,10 +209,34 @@ class InstanceFeatures:
     FPFH and (for memory instances) colour gradients, plus host bounding boxes.  fpfh_split is None for COMPACT features (168 instead
     of 264 bytes per point): the feature search then builds its fp16 operands from the fp32 rows while it stages them."""
 
-    def __init__(self, normals, fpfh, fpfh_split, fpfh_norm, grad, bbox, voxel_size, grad_radius):
+    DEVICE_ARRAYS = ("normals", "fpfh", "fpfh_split", "fpfh_norm", "grad")
+
+    def __init__(self, normals, fpfh, fpfh_split, fpfh_norm, grad, bbox, voxel_size, grad_radius, n=None, n_seg=None):
         self.normals, self.fpfh, self.grad, self.bbox = normals, fpfh, grad, bbox
         self.fpfh_split, self.fpfh_norm = fpfh_split, fpfh_norm
         self.voxel_size, self.grad_radius = float(voxel_size), float(grad_radius)
+        self.n, self.n_seg = n, n_seg          # points / clouds described (instance_features_batch sets them; `append` needs them)
+        self._bufs = {}                        # backing buffers of arrays that are views with headroom behind them
+
+    def append(self, new: "InstanceFeatures"):
+        """Attaches the features of further clouds (computed on their own: a feature depends on its own cloud only, DESIGN (c)
+        conventions 5 and 7) behind the resident ones.  Same parameters and same form (compact or not, with gradients or not) only.
+        The arrays are views of buffers with headroom; only the new rows are copied unless a buffer has to grow (by 1.5)."""
+        if self.n is None or new.n is None:
+            raise ValueError("InstanceFeatures.append: point counts unknown (features not made by instance_features_batch)")
+        if (self.voxel_size, self.grad_radius) != (new.voxel_size, new.grad_radius):
+            raise ValueError("InstanceFeatures.append: the features were computed with other parameters")
+        for name in self.DEVICE_ARRAYS:
+            if (getattr(self, name) is None) != (getattr(new, name) is None):
+                raise ValueError(f"InstanceFeatures.append: `{name}` is present on one side only")
+        for name in self.DEVICE_ARRAYS:
+            cur = getattr(self, name)
+            if cur is not None:
+                self._bufs[name], view = grow_rows(self._bufs.get(name, cur), self.n, getattr(new, name)[:new.n])
+                setattr(self, name, view)
+        self.bbox = np.ascontiguousarray(np.concatenate([self.bbox[:self.n_seg], new.bbox[:new.n_seg]]))
+        self.n += new.n
+        self.n_seg += new.n_seg
 
     def as_struct(self):
         return _FeatStruct(self.normals.data_ptr(), self.fpfh.data_ptr(), self.fpfh_split.data_ptr() if self.fpfh_split is not None else None,
@@ -190,13 +246,14 @@ class InstanceFeatures:
 
 
 def instance_features_batch(ctx: RegContext, batch: CloudBatch, voxel_size: float, grad_radius: float = 0.0,
-                            compact: bool = False) -> InstanceFeatures:
+                            compact: bool = False, reserve_points: int = 0) -> InstanceFeatures:
     """Normals (2 voxel, 30 nn), FPFH (5 voxel, 100 nn) and, with grad_radius > 0, colour gradients (grad_radius, 30 nn) of
     every cloud on its own, in the frame it is stored in -- what ibl_register_batch_cached reuses across jobs.
     compact: do not keep the rows a second time as fp16 search operands (96 of the 264 bytes per point; same registration results,
-    the matrix-core search converts on the fly -- for memories whose resident features would not fit otherwise)."""
+    the matrix-core search converts on the fly -- for memories whose resident features would not fit otherwise).
+    reserve_points: the arrays are allocated with room for that many further points (InstanceFeatures.append) and exposed as views."""
     dev = batch.pts4.device
-    n = max(batch.n, 1)
+    n = max(batch.n, 1) + max(int(reserve_points), 0)
     normals = torch.empty((n, 4), dtype=torch.float32, device=dev)
     fpfh = torch.empty((n, 33), dtype=torch.float32, device=dev)
     # the rows once more as fp16 search operands (csrc/reg_featnn.hip)
@@ -209,7 +266,13 @@ def instance_features_batch(ctx: RegContext, batch: CloudBatch, voxel_size: floa
                                               fpfh_split.data_ptr() if fpfh_split is not None else None, fpfh_norm.data_ptr(),
                                               grad.data_ptr() if grad is not None else None, bbox.ctypes.data, _stream())
     _lib.check(st, "ibl_instance_features_batch")
-    return InstanceFeatures(normals, fpfh, fpfh_split, fpfh_norm, grad, bbox, voxel_size, grad_radius)
+    feat = InstanceFeatures(normals, fpfh, fpfh_split, fpfh_norm, grad, bbox, voxel_size, grad_radius, n=batch.n, n_seg=batch.n_seg)
+    if reserve_points > 0:
+        for name in InstanceFeatures.DEVICE_ARRAYS:
+            if getattr(feat, name) is not None:
+                feat._bufs[name] = getattr(feat, name)
+                setattr(feat, name, feat._bufs[name][:batch.n])
+    return feat
 
 
 REG_HAVE_COLORS = 1
@@ -315,16 +378,39 @@ def register_evaluate_batch(ctx: RegContext, det: CloudBatch, q_per_frame, assns
 
 
 class MemGrid:
-    """Persistent spatial hash over all memory points (lives in the context arena)."""
+    """Persistent spatial hash over all memory points.  It lives in the context arena; with live=True it owns its device memory
+    instead (room for reserve_points further points), `append` merges further points into it and `close` frees it."""
 
-    def __init__(self, ctx: RegContext, mem_pts4: torch.Tensor, cell=0.04):
+    def __init__(self, ctx: RegContext, mem_pts4: torch.Tensor, cell=0.04, live=False, reserve_points=0):
         assert mem_pts4.is_cuda and mem_pts4.dtype == torch.float32 and mem_pts4.shape[1] == 4 and mem_pts4.is_contiguous()
         self.ctx = ctx
         self.cell = cell
+        self.live = bool(live)
         self._h = C.c_void_p()
+        if self.live:
+            st = _lib.lib.ibl_memgrid_build_owned(ctx.handle, mem_pts4.data_ptr(), mem_pts4.shape[0], float(cell), int(reserve_points),
+                                                  C.byref(self._h), _stream())
+            _lib.check(st, "ibl_memgrid_build_owned")
+            return
         st = _lib.lib.ibl_memgrid_build(ctx.handle, mem_pts4.data_ptr(), mem_pts4.shape[0], float(cell), C.byref(self._h),
                                         _stream())
         _lib.check(st, "ibl_memgrid_build")
+
+    def append(self, pts4_new: torch.Tensor):
+        """Merges further points (they count as the points behind all earlier ones) into a live grid: afterwards it equals the grid
+        built from all points at once.  The call synchronises the current stream; no evaluation that uses the grid may be in flight
+        on another stream meanwhile.  On a grid of the arena the library refuses (IblError) and the grid is unchanged."""
+        assert pts4_new.is_cuda and pts4_new.dtype == torch.float32 and pts4_new.dim() == 2 and pts4_new.shape[1] == 4 and pts4_new.is_contiguous()
+        st = _lib.lib.ibl_memgrid_append(self.ctx.handle, self._h, pts4_new.data_ptr(), pts4_new.shape[0], _stream())
+        _lib.check(st, "ibl_memgrid_append")
+
+    def info(self):
+        """dict(n, n_cells, table_slots, point_capacity, ustart_end = ustart[n_cells]) of the grid as it stands"""
+        n, cap, slots = C.c_int64(), C.c_int64(), C.c_int64()
+        cells, end = C.c_int32(), C.c_int32()
+        st = _lib.lib.ibl_memgrid_info(self._h, C.byref(n), C.byref(cells), C.byref(slots), C.byref(cap), C.byref(end), _stream())
+        _lib.check(st, "ibl_memgrid_info")
+        return dict(n=n.value, n_cells=cells.value, table_slots=slots.value, point_capacity=cap.value, ustart_end=end.value)
 
     def close(self):
         if self._h:
