@@ -173,9 +173,43 @@ int ibl_vit_forward(const ibl_vit_desc* desc, const ibl_vit_weights* weights, co
  *   epilogue: IBL_LINEAR_F16 -> out fp16; IBL_LINEAR_GELU_F16 -> out = gelu(.) fp16 (erf form);
  *             IBL_LINEAR_RESID_F32 -> out fp32 += scale[n] * (.) (scale NULL = 1); IBL_LINEAR_F32 -> out fp32
  *   n_out % 128 == 0, n_in % 64 == 0, ldx / ldw / ldo in elements with 16-byte aligned rows */
-enum { IBL_LINEAR_F16 = 0, IBL_LINEAR_GELU_F16 = 1, IBL_LINEAR_RESID_F32 = 2, IBL_LINEAR_F32 = 4 };
+enum { IBL_LINEAR_F16 = 0, IBL_LINEAR_GELU_F16 = 1, IBL_LINEAR_RESID_F32 = 2, IBL_LINEAR_PATCH_F32 = 3, IBL_LINEAR_F32 = 4,
+       IBL_LINEAR_RESID_PRE_F32 = 5, IBL_LINEAR_GELU_F16_X2 = 6, IBL_LINEAR_GELU_F16_X3 = 7 };
 int ibl_linear_f16(const void* x, int64_t ldx, const void* W, int64_t ldw, const float* bias, const float* scale,
                     int64_t rows, int n_out, int n_in, int epilogue, void* out, int64_t ldo, void* stream);
+
+/* The same GEMM with every epilogue ibl_vit_forward runs (ibl_linear_f16 forwards here with its four).  y = x W^T, fp32 accumulation
+ * of the fp16 operands; the kernel, the tile shape (256 x 256 persistent where n_out % 256 == 0 and rows >= 4096, else 128 x 128) and
+ * the launch are those of the encoder.
+ *   x, W, bias, ldx / ldw / ldo as for ibl_linear_f16; rows of x at and beyond `rows`, and columns beyond n_in, are never read
+ *   epilogue IBL_LINEAR_F16 / _GELU_F16 / _RESID_F32 / _F32: as above
+ *            IBL_LINEAR_PATCH_F32: the patch-embedding scatter.  Row r = b * patches_per_crop + p of x goes to row
+ *                b * tokens_per_crop + 1 + p of out (fp32): out = y + bias + pos[p] (pos [dev] fp32 [patches_per_crop][n_out]), or, with
+ *                accumulate = 1, out += alpha * (y + bias) (the second weight term; pos is not read).  Row 0 of every crop (the CLS
+ *                token) and rows beyond patches_per_crop are not touched.  rows must be whole crops: a multiple of patches_per_crop
+ *            IBL_LINEAR_RESID_PRE_F32: out fp32 = out + bias + alpha * y, with the tile of out preloaded into the accumulators as
+ *                (out + bias) / alpha; selected here and nowhere else ($IBL_GEMM_RESID_PRE concerns ibl_vit_forward and ibl_linear_f16)
+ *            IBL_LINEAR_GELU_F16_X2 / _X3: out fp16 [rows][ldo] of 2 / 3 column blocks of n_out: [h | h / S], [h | (value - h) * S | h / S]
+ *                with h = gelu(y + bias) rounded to fp16 from the fp32 `value` (S = IBL_VIT_SPLIT_SCALE): ldo >= 2 / 3 * n_out
+ *   scale is read by IBL_LINEAR_RESID_F32 only; alpha by IBL_LINEAR_RESID_PRE_F32 and by the accumulate form of the patch scatter, where it
+ *   must be a positive power of two (the kernel divides and multiplies by it and both must be exact)
+ *   rows 0 returns IBL_OK without a launch.  A null x / W / out, n_out % 128, n_in % 64, a stride shorter than its row or not a
+ *   multiple of 8 elements, an alpha that is no positive power of two where it is read, patches_per_crop <= 0, tokens_per_crop <=
+ *   patches_per_crop, part of a crop, pos NULL without accumulate and an unknown epilogue are refused with a status before any launch. */
+typedef struct {
+    const void* x;  int64_t ldx;       /* fp16 [rows][ldx]                                              */
+    const void* W;  int64_t ldw;       /* fp16 [n_out][ldw]                                             */
+    const float* bias;                 /* [n_out] or NULL                                               */
+    const float* scale;                /* [n_out] or NULL (IBL_LINEAR_RESID_F32)                        */
+    const float* pos;                  /* [patches_per_crop][n_out] (IBL_LINEAR_PATCH_F32)              */
+    void* out;      int64_t ldo;
+    int64_t rows;
+    int32_t n_out, n_in, epilogue;
+    int32_t accumulate;                /* IBL_LINEAR_PATCH_F32: 0 or 1                                  */
+    int32_t tokens_per_crop, patches_per_crop;
+    float alpha;
+} ibl_linear_desc;
+int ibl_linear_f16_ex(const ibl_linear_desc* desc, void* stream);
 
 /* The encoder's attention on its own: out = softmax(q k^T / 8) v per (crop, head), head_dim 64 -- what transformers'
  * ViTSelfAttention / Dinov2SelfAttention and open_clip's nn.MultiheadAttention compute inside the encoders of

@@ -46,6 +46,7 @@ _SIGS = {
                                        vp, vp, vp, vp, vp]),
     "ibl_vit_workspace_bytes": (C.c_int64, [vp, C.c_int]),
     "ibl_linear_f16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp]),
+    "ibl_linear_f16_ex": (C.c_int, [vp, vp]),
     "ibl_vit_forward": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp]),
     "ibl_attention_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ibl_layernorm_f32": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_float, vp, C.c_int64, C.c_int, vp]),

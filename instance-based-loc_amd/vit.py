@@ -466,6 +466,14 @@ class VitEncoder:
 
 
 LINEAR_F16, LINEAR_GELU_F16, LINEAR_RESID_F32, LINEAR_F32 = 0, 1, 2, 4
+LINEAR_PATCH_F32, LINEAR_RESID_PRE_F32, LINEAR_GELU_F16_X2, LINEAR_GELU_F16_X3 = 3, 5, 6, 7
+
+
+class LinearDesc(C.Structure):              # ibl_linear_desc (include/ibloc.h)
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("W", C.c_void_p), ("ldw", C.c_int64), ("bias", C.c_void_p),
+                ("scale", C.c_void_p), ("pos", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int64), ("rows", C.c_int64),
+                ("n_out", C.c_int32), ("n_in", C.c_int32), ("epilogue", C.c_int32), ("accumulate", C.c_int32),
+                ("tokens_per_crop", C.c_int32), ("patches_per_crop", C.c_int32), ("alpha", C.c_float)]
 
 
 def linear_f16(x: torch.Tensor, W: torch.Tensor, bias=None, epilogue=LINEAR_F16, out=None, scale=None) -> torch.Tensor:
@@ -490,6 +498,26 @@ def linear_f16(x: torch.Tensor, W: torch.Tensor, bias=None, epilogue=LINEAR_F16,
                                   scale.data_ptr() if scale is not None else None, rows, n_out, n_in, epilogue, out.data_ptr(),
                                   out.stride(0), torch.cuda.current_stream().cuda_stream)
     _lib.check(st, "ibl_linear_f16")
+    return out
+
+
+def linear_f16_ex(x: torch.Tensor, W: torch.Tensor, out: torch.Tensor, epilogue, bias=None, scale=None, pos=None, alpha=1.0,
+                  accumulate=False, tokens_per_crop=0, patches_per_crop=0) -> torch.Tensor:
+    """`ibl_linear_f16_ex`: the encoder's GEMM with any of its eight epilogues, written into `out` (include/ibloc.h says what each one
+    computes).  x (rows, n_in) fp16, W (n_out, n_in) fp16, `out` fp16 (rows, terms * n_out) for LINEAR_F16 / _GELU_F16 / _GELU_F16_X2 /
+    _X3, else fp32 (rows, n_out) -- for LINEAR_PATCH_F32 fp32 (rows / patches_per_crop * tokens_per_crop, n_out), the token rows.  All
+    three may be row-strided views.  Only the dtypes and the devices are checked here: what the library cannot run it refuses (IblError)."""
+    for t in (x, W, out):
+        assert t.is_cuda and t.dim() == 2 and t.stride(1) == 1
+    assert x.dtype == torch.float16 and W.dtype == torch.float16
+    assert out.dtype == (torch.float16 if epilogue in (LINEAR_F16, LINEAR_GELU_F16, LINEAR_GELU_F16_X2, LINEAR_GELU_F16_X3) else torch.float32)
+    for t in (bias, scale, pos):
+        assert t is None or (t.dtype == torch.float32 and t.is_cuda and t.is_contiguous())
+    d = LinearDesc(x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), bias.data_ptr() if bias is not None else None,
+                   scale.data_ptr() if scale is not None else None, pos.data_ptr() if pos is not None else None, out.data_ptr(),
+                   out.stride(0), x.shape[0], W.shape[0], x.shape[1], int(epilogue), int(accumulate), int(tokens_per_crop),
+                   int(patches_per_crop), float(alpha))
+    _lib.check(_lib.lib.ibl_linear_f16_ex(C.byref(d), torch.cuda.current_stream().cuda_stream), "ibl_linear_f16_ex")
     return out
 
 

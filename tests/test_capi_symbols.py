@@ -50,7 +50,7 @@ def test_struct_layouts_match_the_header(tmp_path):
     from ibloc_amd import preprocess as pp
     from ibloc_amd import registration as R
     from ibloc_amd import vit as V
-    pairs = [("ibl_vit_desc", V.VitDesc), ("ibl_vit_layer", V.VitLayer), ("ibl_vit_weights", V.VitWeights),
+    pairs = [("ibl_vit_desc", V.VitDesc), ("ibl_vit_layer", V.VitLayer), ("ibl_vit_weights", V.VitWeights), ("ibl_linear_desc", V.LinearDesc),
              ("ibl_dator_head_weights", D.DatorHeadWeights), ("ibl_crop_desc", pp.CropDesc), ("ibl_instance_features", R._FeatStruct)]
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "ibloc.h"', 'int main(void) {']
     for cname, ct in pairs:
