@@ -13,14 +13,15 @@
  *     thread-local).  No exception crosses the boundary.
  *   - the CALLER owns all memory.  Pointers marked [dev] are device (HBM) pointers, e.g.
  *     torch.Tensor.data_ptr(); pointers marked [host] are host pointers.  Workspace sizes come
- *     from the *_workspace_bytes() queries.  The library never allocates persistent device memory.
+ *     from the *_workspace_bytes() queries.  The library's own device memory is explicit: the arena of a registration context
+ *     (scratch: every call releases what it took) and the arrays of a memory grid (ibl_memgrid_build* .. ibl_memgrid_destroy).
  *   - all launches are asynchronous on the hipStream_t passed as `void* stream`
  *     (torch.cuda.current_stream().cuda_stream).  Functions whose results are DEVICE arrays (embed, match, candidate selection)
  *     never synchronise.  Functions that return HOST results synchronise the stream -- how often is stated per function:
  *     ibl_radius_outlier_batch 1 (grid table size), ibl_instance_features_batch 2 (bounding boxes; end),
  *     ibl_register_batch_cached 2-4 (one per group of RANSAC rounds -- most calls need one -- plus the results; one more when
- *     instances of a job lie within the influence radius of each other), ibl_evaluate_batch 1, ibl_memgrid_build 2 (once per
- *     memory).  Plan tables are staged through pinned host memory of the registration context, so uploads never wait.
+ *     instances of a job lie within the influence radius of each other), ibl_evaluate_batch 1, ibl_memgrid_build / _build_owned / _append 2
+ *     (cell count; end).  Plan tables are staged through pinned host memory of the registration context, so uploads never wait.
  *   - plain C types only; no torch types in any signature.
  */
 #ifndef IBLOC_H
@@ -376,12 +377,12 @@ int ibl_allreduce_max_i32(ibl_comm* comm, int32_t* buf, int64_t n, void* stream)
 /* ------------------------------------------------------------------------------------------ */
 
 /* Registration context: one device arena (bump allocator) that the batched calls carve their
- * grids, neighbour lists and per-job state from.  The only persistent device allocation of the
- * library; created and destroyed explicitly.  Not thread-safe: one context per stream/thread. */
+ * grids, neighbour lists and per-job state from, as scratch: every call releases what it took.
+ * Created and destroyed explicitly.  Not thread-safe: one context per stream/thread. */
 typedef struct ibl_reg_ctx ibl_reg_ctx;
 int ibl_reg_ctx_create(ibl_reg_ctx** out, int64_t arena_bytes);
 int ibl_reg_ctx_destroy(ibl_reg_ctx* ctx);
-/* drop every allocation of the arena, including memory grids built from it (they become invalid) */
+/* drop every allocation of the arena (between calls nothing is held; memory grids own their arrays and stay valid) */
 int ibl_reg_ctx_reset(ibl_reg_ctx* ctx);
 int64_t ibl_reg_ctx_high_water(const ibl_reg_ctx* ctx);
 /* device status word (bit 0: grid table overflow, bit 1: a k-NN query took the re-scan slow path; bits 2-3 are internal to
@@ -565,25 +566,27 @@ int ibl_voxel_downsample_batch(ibl_reg_ctx* ctx, const double* points, const dou
 int ibl_dbscan_batch(ibl_reg_ctx* ctx, const double* points, const int32_t* grp_off_host, int32_t n_grp, double eps, int32_t min_points,
                      int32_t* labels, int32_t* n_clusters_host, void* stream);
 
-/* Persistent spatial hash over ALL memory points (world frame), built once per memory upload from the
- * context arena.  Replaces the KD-tree Open3D rebuilds over `all_memory_pcd` on every evaluate_registration
- * call (utils/fpfh_register.py:146-148 <- object_memory/object_memory.py:1104).  cell >= 2 * threshold keeps a
- * query to <= 8 cells. */
+/* Persistent spatial hash over ALL memory points (world frame), built once per memory upload.  Replaces the
+ * KD-tree Open3D rebuilds over `all_memory_pcd` on every evaluate_registration call (utils/fpfh_register.py:146-148
+ * <- object_memory/object_memory.py:1104).  cell >= 2 * threshold keeps a query to <= 8 cells.
+ *   The grid owns its device arrays (hipMalloc: 16 bytes per point, 12 per occupied cell, 12 per table slot); ctx's arena is
+ *   scratch only (40 bytes per point + the sort's, released on return).  A grid of ibl_memgrid_build is immutable.  A failed
+ *   build frees what it allocated; a cell table found full is IBL_ERR_OVERFLOW.
+ * ibl_memgrid_destroy frees the grid and its device arrays (NULL is a no-op); nothing may still be using it on any stream. */
 typedef struct ibl_memgrid ibl_memgrid;
 int ibl_memgrid_build(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, ibl_memgrid** out, void* stream);
 int ibl_memgrid_destroy(ibl_memgrid* grid);
 
 /* The same grid for a memory that GROWS while it is resident (live memory): same keys, same hash, same arrays as ibl_memgrid_build
- * gives for the same points -- every evaluation entry point below takes either kind.
- *   Ownership: the device arrays belong to the grid (hipMalloc), not to the context arena; they are sized for n + reserve_points
- *   points and freed by ibl_memgrid_destroy, so such a grid survives ibl_reg_ctx_reset and must be destroyed before the process
- *   gives the device up.  The arena is used as scratch only (the size of an arena build, released on return).
+ * gives for the same points (it is the same build) -- every evaluation entry point below takes either kind.
+ *   ibl_memgrid_build_owned differs from ibl_memgrid_build in two things: the point buffer holds n + reserve_points points (and the
+ *   cell arrays min(reserve_points, cells / 2) further cells), and the grid accepts ibl_memgrid_append.
  *   ibl_memgrid_append merges n_new further points (new_pts4 [dev] n_new x 4 floats; they count as the points n .. n + n_new - 1)
  *   into the grid: afterwards it holds what ibl_memgrid_build returns for the old points followed by the new ones, array for array
  *   (the sort is stable and a cell keeps its points in index order, so the merge "old before new" is that sort).  One pass over
  *   the resident points into the second buffer of a ping-pong pair (allocated by the first append), cell arrays and table
  *   rebuilt; buffers that no longer fit grow by a factor of 1.5, the table keeps the rule of the build (smallest power of two
- *   >= 3 x cells, >= 1024).  Scratch: 16 bytes per resident point + 24 per new point from ctx's arena, released on return.
+ *   >= 3 x cells, >= 1024).  Scratch: 16 bytes per point of the merged grid + 24 per new point from ctx's arena, released on return.
  *   n_new == 0 is a no-op (IBL_OK); n + n_new <= 0x7FFFFFF0; a grid of ibl_memgrid_build is refused with IBL_ERR_ARG and nothing
  *   is launched.  A failed append that returns IBL_ERR_ARG, the arena error or an allocation error leaves the grid as it was.
  *   Synchronisation: both calls synchronise `stream` before they return.  An append frees and replaces arrays of the grid: no

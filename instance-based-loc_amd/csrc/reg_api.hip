@@ -144,7 +144,7 @@ extern "C" int ibl_reg_ctx_destroy(ibl_reg_ctx* ctx) {
 
 extern "C" int ibl_reg_ctx_reset(ibl_reg_ctx* ctx) {
     if (!ctx) return ibl_set_error(IBL_ERR_ARG, "ibl_reg_ctx_reset: null context");
-    ctx->used = 256;           // drops every persistent allocation (memory grids built from this arena become invalid)
+    ctx->used = 256;           // (between calls the arena holds nothing: memory grids own their arrays)
     return IBL_OK;
 }
 

@@ -20,17 +20,30 @@
 // ------------------------------------------------------------------------------------------------
 // whole-memory hash grid + evaluate_registration
 // ------------------------------------------------------------------------------------------------
-struct ibl_memgrid {
+// what the evaluation kernel takes by value
+struct MemGridView {
     float cell, inv;
     int64_t n;
     int n_cells;
-    int owned;                      // 0: arrays in the context arena; 1: an ibl_memgrid_live (below) that owns its device memory
     unsigned long long hmask;
     float4* sorted;                 // points in cell order
     unsigned long long* ukeys;      // unique cell keys
     int* ustart;                    // [n_cells + 1]
     unsigned long long* tkeys;      // hash table keys (EMPTY = ~0)
     int* tvals;                     // cell index
+};
+
+// The grid owns its device arrays (hipMalloc; freed by ibl_memgrid_destroy): a ping-pong pair for the points (a merge writes buf[cur]
+// and the new points into buf[1 - cur], which the first append that needs it allocates), cell arrays and a table with their own
+// capacities.  v.sorted is buf[cur].
+struct ibl_memgrid {
+    MemGridView v = {};
+    int fixed = 0;                      // 1: made by ibl_memgrid_build -- immutable, ibl_memgrid_append refuses it
+    float4* buf[2] = {nullptr, nullptr};
+    int64_t buf_cap[2] = {0, 0};        // points
+    int cur = 0;
+    int64_t cell_cap = 0;               // ukeys holds cell_cap, ustart cell_cap + 1 entries
+    unsigned long long tab_cap = 0;     // slots of tkeys / tvals
 };
 
 #define MG_EMPTY 0xFFFFFFFFFFFFFFFFull
@@ -56,170 +69,6 @@ __global__ __launch_bounds__(256) void ibl_mg_heads_kernel(const unsigned long l
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     head[i] = (i == 0 || skeys[i] != skeys[i - 1]) ? 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void ibl_mg_cells_kernel(const unsigned long long* __restrict__ skeys, const int* __restrict__ head,
-                                                           const int* __restrict__ head_scan, const int* __restrict__ order,
-                                                           const float4* __restrict__ pts, int64_t n, unsigned long long* __restrict__ ukeys,
-                                                           int* __restrict__ ustart, float4* __restrict__ sorted) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    sorted[i] = pts[order[i]];
-    if (head[i]) { const int c = head_scan[i]; ukeys[c] = skeys[i]; ustart[c] = (int)i; }
-}
-
-__global__ __launch_bounds__(256) void ibl_mg_insert_kernel(const unsigned long long* __restrict__ ukeys, int n_cells, unsigned long long hmask,
-                                                            unsigned long long* __restrict__ tkeys, int* __restrict__ tvals) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= n_cells) return;
-    const unsigned long long k = ukeys[c];
-    unsigned long long h = mg_hash(k) & hmask;
-    while (true) {
-        const unsigned long long prev = atomicCAS(&tkeys[h], MG_EMPTY, k);
-        if (prev == MG_EMPTY) { tvals[h] = c; return; }
-        h = (h + 1) & hmask;
-    }
-}
-
-extern "C" int ibl_memgrid_build(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, ibl_memgrid** out, void* stream) {
-    if (!ctx || !mem_pts4 || !out || n <= 0 || n > 0x7FFFFFF0ll || cell <= 0) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_build: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    std::unique_ptr<ibl_memgrid> owner(new ibl_memgrid());      // freed on every error return below
-    ibl_memgrid* g = owner.get();
-    g->cell = (float)cell; g->inv = 1.0f / (float)cell; g->n = n;
-    const float4* P = reinterpret_cast<const float4*>(mem_pts4);
-    // persistent part (stays allocated in the arena until the context is destroyed)
-    IBL_ARENA(g->sorted, float4, n + 1);
-    IBL_ARENA(g->ukeys, unsigned long long, n + 1);
-    IBL_ARENA(g->ustart, int, n + 2);
-    {
-        ArenaMark scratch(ctx);
-        unsigned long long *keys, *skeys; int *vals, *order, *head, *hscan; unsigned char* tmp;
-        IBL_ARENA(keys, unsigned long long, n);
-        IBL_ARENA(skeys, unsigned long long, n);
-        IBL_ARENA(vals, int, n);
-        IBL_ARENA(order, int, n);
-        IBL_ARENA(head, int, n + 1);
-        IBL_ARENA(hscan, int, n + 1);
-        const unsigned nb = (unsigned)((n + 255) / 256);
-        hipLaunchKernelGGL(ibl_mg_key_kernel, dim3(nb), dim3(256), 0, s, P, n, g->inv, keys, vals);
-        IBL_LAUNCH_CHECK();
-        size_t t1 = 0, t2 = 0;
-        IBL_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, keys, skeys, vals, order, (int)n, 0, 63, s));
-        IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, head, hscan, (int)n, s));
-        IBL_ARENA(tmp, unsigned char, (int64_t)std::max(t1, t2) + 256);
-        IBL_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, t1, keys, skeys, vals, order, (int)n, 0, 63, s));
-        hipLaunchKernelGGL(ibl_mg_heads_kernel, dim3(nb), dim3(256), 0, s, skeys, n, head);
-        IBL_LAUNCH_CHECK();
-        IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, t2, head, hscan, (int)n, s));
-        hipLaunchKernelGGL(ibl_mg_cells_kernel, dim3(nb), dim3(256), 0, s, skeys, head, hscan, order, P, n, g->ukeys, g->ustart, g->sorted);
-        IBL_LAUNCH_CHECK();
-        int last_scan = 0, last_head = 0;
-        IBL_HIP_CHECK(hipMemcpyAsync(&last_scan, hscan + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-        IBL_HIP_CHECK(hipMemcpyAsync(&last_head, head + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-        IBL_HIP_CHECK(hipStreamSynchronize(s));
-        g->n_cells = last_scan + last_head;
-        const int nn = (int)n;
-        IBL_HIP_CHECK(hipMemcpyAsync(g->ustart + g->n_cells, &nn, sizeof(int), hipMemcpyHostToDevice, s));
-        IBL_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    // The table is dimensioned from the OCCUPIED CELLS, now that they are counted (round 4): it used to hold 2 n slots -- 128 M slots = 1.5 GB
-    // for a 10 000-instance memory whose 50 M surface points occupy a few million 4 cm cells -- so that every probe of the evaluation was
-    // a first touch of HBM (1.9 GB moved per launch for 158 MB of points).  At <= 1 / 3 load the table of the same memory is ~100 MB: it stays
-    // in the Infinity Cache, and a miss walks 1.5 slots on average.  Same cells, same points, same minima.
-    unsigned long long H = 1024;
-    while (H < (unsigned long long)g->n_cells * 3) H <<= 1;
-    g->hmask = H - 1;
-    IBL_ARENA(g->tkeys, unsigned long long, (int64_t)H);
-    IBL_ARENA(g->tvals, int, (int64_t)H);
-    IBL_HIP_CHECK(hipMemsetAsync(g->tkeys, 0xFF, sizeof(unsigned long long) * H, s));
-    hipLaunchKernelGGL(ibl_mg_insert_kernel, dim3((g->n_cells + 255) / 256), dim3(256), 0, s, g->ukeys, g->n_cells, g->hmask, g->tkeys, g->tvals);
-    IBL_LAUNCH_CHECK();
-    IBL_HIP_CHECK(hipStreamSynchronize(s));
-    *out = owner.release();
-    return IBL_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// live grid: the same structure in device memory of its own, with room to grow (ibl_memgrid_build_owned / ibl_memgrid_append)
-// ------------------------------------------------------------------------------------------------
-// An owned grid is the arena grid's struct (what the evaluation kernels take by value) plus the book-keeping of its buffers: a
-// ping-pong pair for the points (an append merges buf[cur] and the new points into buf[1 - cur]), cell arrays and a table with their
-// own capacities.  buf[1 - cur] is allocated by the first append that needs it.
-struct ibl_memgrid_live : ibl_memgrid {
-    float4* buf[2] = {nullptr, nullptr};
-    int64_t buf_cap[2] = {0, 0};        // points
-    int cur = 0;
-    int64_t cell_cap = 0;               // ukeys holds cell_cap, ustart cell_cap + 1 entries
-    unsigned long long tab_cap = 0;     // slots of tkeys / tvals
-};
-
-static void mg_live_free(ibl_memgrid_live* g) {
-    (void)hipFree(g->buf[0]); (void)hipFree(g->buf[1]); (void)hipFree(g->ukeys); (void)hipFree(g->ustart);
-    (void)hipFree(g->tkeys); (void)hipFree(g->tvals);
-    delete g;
-}
-
-extern "C" int ibl_memgrid_build_owned(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, int64_t reserve_points,
-                                       ibl_memgrid** out, void* stream) {
-    if (!ctx || !mem_pts4 || !out || n <= 0 || n > 0x7FFFFFF0ll || cell <= 0 || reserve_points < 0 || reserve_points > 0x7FFFFFF0ll - n)
-        return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_build_owned: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    // the arena build, under a mark: its arrays are copied out and its arena space is released on return -- one build, one set of values
-    ArenaMark scratch(ctx);
-    ibl_memgrid* a = nullptr;
-    const int st = ibl_memgrid_build(ctx, mem_pts4, n, cell, &a, stream);
-    if (st != IBL_OK) return st;
-    std::unique_ptr<ibl_memgrid> arena_grid(a);
-    ibl_memgrid_live* g = new ibl_memgrid_live();
-    static_cast<ibl_memgrid&>(*g) = *a;
-    g->owned = 1;
-    g->sorted = nullptr; g->ukeys = nullptr; g->ustart = nullptr; g->tkeys = nullptr; g->tvals = nullptr;
-    const unsigned long long H = a->hmask + 1;
-    g->buf_cap[0] = n + reserve_points;
-    g->cell_cap = a->n_cells + std::min<int64_t>(reserve_points, a->n_cells / 2);
-    g->tab_cap = H;
-    hipError_t e = hipMalloc(&g->buf[0], sizeof(float4) * (size_t)g->buf_cap[0]);
-    if (e == hipSuccess) e = hipMalloc(&g->ukeys, sizeof(unsigned long long) * (size_t)g->cell_cap);
-    if (e == hipSuccess) e = hipMalloc(&g->ustart, sizeof(int) * (size_t)(g->cell_cap + 1));
-    if (e == hipSuccess) e = hipMalloc(&g->tkeys, sizeof(unsigned long long) * H);
-    if (e == hipSuccess) e = hipMalloc(&g->tvals, sizeof(int) * H);
-    if (e == hipSuccess) e = hipMemcpyAsync(g->buf[0], a->sorted, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(g->ukeys, a->ukeys, sizeof(unsigned long long) * (size_t)a->n_cells, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(g->ustart, a->ustart, sizeof(int) * (size_t)(a->n_cells + 1), hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(g->tkeys, a->tkeys, sizeof(unsigned long long) * H, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(g->tvals, a->tvals, sizeof(int) * H, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        mg_live_free(g);
-        return ibl_set_error(IBL_ERR_HIP, "ibl_memgrid_build_owned: %s", hipGetErrorString(e));
-    }
-    g->sorted = g->buf[0];
-    *out = g;
-    return IBL_OK;
-}
-
-extern "C" int ibl_memgrid_destroy(ibl_memgrid* g) {
-    if (g && g->owned) { mg_live_free(static_cast<ibl_memgrid_live*>(g)); return IBL_OK; }
-    delete g;       // device memory belongs to the context arena
-    return IBL_OK;
-}
-
-extern "C" int ibl_memgrid_info(const ibl_memgrid* g, int64_t* n, int32_t* n_cells, int64_t* table_slots, int64_t* point_capacity,
-                                int32_t* ustart_end, void* stream) {
-    if (!g) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_info: grid is null");
-    if (n) *n = g->n;
-    if (n_cells) *n_cells = g->n_cells;
-    if (table_slots) *table_slots = (int64_t)(g->hmask + 1);
-    if (point_capacity) {
-        const ibl_memgrid_live* l = g->owned ? static_cast<const ibl_memgrid_live*>(g) : nullptr;
-        *point_capacity = l ? l->buf_cap[l->cur] : g->n;
-    }
-    if (ustart_end) {
-        IBL_HIP_CHECK(hipMemcpyAsync(ustart_end, g->ustart + g->n_cells, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-        IBL_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    }
-    return IBL_OK;
 }
 
 // first index of the sorted keys[0, n) whose key is not below k (strict = 0) / is above k (strict = 1)
@@ -249,6 +98,7 @@ __global__ __launch_bounds__(256) void ibl_mg_merge_old_kernel(const float4* __r
 }
 
 // new side: sorted new point j moves up by the number of old points in cells up to and including its own, read from the old cell arrays
+// (none for an empty grid: ustart[0] = 0, and the sorted new points are the grid's points)
 __global__ __launch_bounds__(256) void ibl_mg_merge_new_kernel(const float4* __restrict__ pts, const int* __restrict__ order,
                                                                const unsigned long long* __restrict__ nkeys, int n_new,
                                                                const unsigned long long* __restrict__ ukeys, const int* __restrict__ ustart,
@@ -269,7 +119,7 @@ __global__ __launch_bounds__(256) void ibl_mg_merged_cells_kernel(const unsigned
     if (head[i]) { const int c = head_scan[i]; ukeys[c] = mkeys[i]; ustart[c] = (int)i; }
 }
 
-// as ibl_mg_insert_kernel, with the probe walk bounded by the table: a key that found no slot (cannot happen at <= 1 / 3 load) is reported
+// linear probing, the walk bounded by the table: a key that found no slot (cannot happen at <= 1 / 3 load) is reported, never waited for
 __global__ __launch_bounds__(256) void ibl_mg_insert_bounded_kernel(const unsigned long long* __restrict__ ukeys, int n_cells,
                                                                     unsigned long long hmask, unsigned long long* __restrict__ tkeys,
                                                                     int* __restrict__ tvals, int* __restrict__ failed) {
@@ -285,15 +135,12 @@ __global__ __launch_bounds__(256) void ibl_mg_insert_bounded_kernel(const unsign
     atomicExch(failed, 1);
 }
 
-extern "C" int ibl_memgrid_append(ibl_reg_ctx* ctx, ibl_memgrid* grid, const float* new_pts4, int64_t n_new, void* stream) {
-    if (!ctx || !grid || n_new < 0 || (n_new > 0 && !new_pts4)) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_append: bad argument");
-    if (!grid->owned) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_append: the grid lives in the context arena (build it with ibl_memgrid_build_owned)");
-    if (n_new == 0) return IBL_OK;
-    ibl_memgrid_live* g = static_cast<ibl_memgrid_live*>(grid);
-    const int64_t n_old = g->n, n = n_old + n_new;
-    if (n > 0x7FFFFFF0ll) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_append: more than 0x7FFFFFF0 points");
-    hipStream_t s = (hipStream_t)stream;
-    const float4* P = reinterpret_cast<const float4*>(new_pts4);
+// Merges n_new (> 0) further points into the grid -- all of them into an empty grid: that is the build.  The new points are keyed and
+// sorted (stable: equal keys keep their index order), both sides are merged into the other point buffer, the cells are read off the
+// merged keys and the table is refilled.  reserve_points: room for further cells when the cell arrays are (re)allocated.
+// The arena is scratch only.  Synchronises `s` after the cells are counted and before it returns.
+static int mg_merge(ibl_reg_ctx* ctx, ibl_memgrid* g, const float4* P, int64_t n_new, int64_t reserve_points, hipStream_t s, const char* who) {
+    const int64_t n_old = g->v.n, n = n_old + n_new;
     ArenaMark scratch(ctx);
     unsigned long long *keys, *nkeys, *mkeys; int *vals, *order, *head, *hscan, *failed; unsigned char* tmp;
     IBL_ARENA(keys, unsigned long long, n_new);
@@ -319,17 +166,18 @@ extern "C" int ibl_memgrid_append(ibl_reg_ctx* ctx, ibl_memgrid* grid, const flo
         g->buf_cap[o] = cap;
     }
     float4* dst = g->buf[o];
-    // key and sort the new points (stable: equal keys keep their index order), merge both sides into dst
     const unsigned nb_new = (unsigned)((n_new + 255) / 256), nb_old = (unsigned)((n_old + 255) / 256), nb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(ibl_mg_key_kernel, dim3(nb_new), dim3(256), 0, s, P, n_new, g->inv, keys, vals);
+    hipLaunchKernelGGL(ibl_mg_key_kernel, dim3(nb_new), dim3(256), 0, s, P, n_new, g->v.inv, keys, vals);
     IBL_LAUNCH_CHECK();
     IBL_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, t1, keys, nkeys, vals, order, (int)n_new, 0, 63, s));
-    hipLaunchKernelGGL(ibl_mg_merge_old_kernel, dim3(nb_old), dim3(256), 0, s, g->sorted, n_old, g->inv, nkeys, (int)n_new, dst, mkeys);
+    if (n_old > 0) {
+        hipLaunchKernelGGL(ibl_mg_merge_old_kernel, dim3(nb_old), dim3(256), 0, s, g->v.sorted, n_old, g->v.inv, nkeys, (int)n_new, dst, mkeys);
+        IBL_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(ibl_mg_merge_new_kernel, dim3(nb_new), dim3(256), 0, s, P, order, nkeys, (int)n_new, g->v.ukeys, g->v.ustart,
+                       g->v.n_cells, dst, mkeys);
     IBL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ibl_mg_merge_new_kernel, dim3(nb_new), dim3(256), 0, s, P, order, nkeys, (int)n_new, g->ukeys, g->ustart, g->n_cells,
-                       dst, mkeys);
-    IBL_LAUNCH_CHECK();
-    // cells of the merged order
+    // cells of the merged order, counted
     hipLaunchKernelGGL(ibl_mg_heads_kernel, dim3(nb), dim3(256), 0, s, mkeys, n, head);
     IBL_LAUNCH_CHECK();
     IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, t2, head, hscan, (int)n, s));
@@ -338,17 +186,21 @@ extern "C" int ibl_memgrid_append(ibl_reg_ctx* ctx, ibl_memgrid* grid, const flo
     IBL_HIP_CHECK(hipMemcpyAsync(&last_head, head + (n - 1), sizeof(int), hipMemcpyDeviceToHost, s));
     IBL_HIP_CHECK(hipStreamSynchronize(s));         // (the merge has read the old cell arrays: they may be replaced now)
     const int n_cells = last_scan + last_head;
-    // every allocation the new state needs before any of the old state is overwritten: a failure here leaves the grid as it was
+    // The table is dimensioned from the OCCUPIED CELLS (round 4): it used to hold 2 n slots -- 128 M slots = 1.5 GB for a 10 000-instance
+    // memory whose 50 M surface points occupy a few million 4 cm cells -- so that every probe of the evaluation was a first touch of HBM
+    // (1.9 GB moved per launch for 158 MB of points).  At <= 1 / 3 load the table of the same memory is ~100 MB: it stays in the
+    // Infinity Cache, and a miss walks 1.5 slots on average.
     unsigned long long H = 1024;
     while (H < (unsigned long long)n_cells * 3) H <<= 1;
-    unsigned long long* ukeys = g->ukeys; int* ustart = g->ustart; int64_t cell_cap = g->cell_cap;
-    unsigned long long* tkeys = g->tkeys; int* tvals = g->tvals;
+    // every allocation the new state needs before any of the old state is overwritten: a failure here leaves the grid as it was
+    unsigned long long* ukeys = g->v.ukeys; int* ustart = g->v.ustart; int64_t cell_cap = g->cell_cap;
+    unsigned long long* tkeys = g->v.tkeys; int* tvals = g->v.tvals;
     if (n_cells > cell_cap) {
-        cell_cap = std::max<int64_t>(n_cells, cell_cap + cell_cap / 2);
+        cell_cap = std::max<int64_t>(n_cells + std::min<int64_t>(reserve_points, n_cells / 2), cell_cap + cell_cap / 2);
         ukeys = nullptr; ustart = nullptr;
         hipError_t e = hipMalloc(&ukeys, sizeof(unsigned long long) * (size_t)cell_cap);
         if (e == hipSuccess) e = hipMalloc(&ustart, sizeof(int) * (size_t)(cell_cap + 1));
-        if (e != hipSuccess) { (void)hipFree(ukeys); return ibl_set_error(IBL_ERR_HIP, "ibl_memgrid_append: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) { (void)hipFree(ukeys); return ibl_set_error(IBL_ERR_HIP, "%s: %s", who, hipGetErrorString(e)); }
     }
     if (H > g->tab_cap) {
         tkeys = nullptr; tvals = nullptr;
@@ -356,27 +208,86 @@ extern "C" int ibl_memgrid_append(ibl_reg_ctx* ctx, ibl_memgrid* grid, const flo
         if (e == hipSuccess) e = hipMalloc(&tvals, sizeof(int) * H);
         if (e != hipSuccess) {
             (void)hipFree(tkeys);
-            if (ukeys != g->ukeys) { (void)hipFree(ukeys); (void)hipFree(ustart); }
-            return ibl_set_error(IBL_ERR_HIP, "ibl_memgrid_append: %s", hipGetErrorString(e));
+            if (ukeys != g->v.ukeys) { (void)hipFree(ukeys); (void)hipFree(ustart); }
+            return ibl_set_error(IBL_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
         }
     }
-    if (ukeys != g->ukeys) { (void)hipFree(g->ukeys); (void)hipFree(g->ustart); g->ukeys = ukeys; g->ustart = ustart; g->cell_cap = cell_cap; }
-    if (tkeys != g->tkeys) { (void)hipFree(g->tkeys); (void)hipFree(g->tvals); g->tkeys = tkeys; g->tvals = tvals; g->tab_cap = H; }
-    g->sorted = dst; g->cur = o; g->n = n; g->n_cells = n_cells; g->hmask = H - 1;
-    hipLaunchKernelGGL(ibl_mg_merged_cells_kernel, dim3(nb), dim3(256), 0, s, mkeys, head, hscan, n, g->ukeys, g->ustart);
+    if (ukeys != g->v.ukeys) { (void)hipFree(g->v.ukeys); (void)hipFree(g->v.ustart); g->v.ukeys = ukeys; g->v.ustart = ustart; g->cell_cap = cell_cap; }
+    if (tkeys != g->v.tkeys) { (void)hipFree(g->v.tkeys); (void)hipFree(g->v.tvals); g->v.tkeys = tkeys; g->v.tvals = tvals; g->tab_cap = H; }
+    g->v.sorted = dst; g->cur = o; g->v.n = n; g->v.n_cells = n_cells; g->v.hmask = H - 1;
+    hipLaunchKernelGGL(ibl_mg_merged_cells_kernel, dim3(nb), dim3(256), 0, s, mkeys, head, hscan, n, g->v.ukeys, g->v.ustart);
     IBL_LAUNCH_CHECK();
     const int nn = (int)n;
-    IBL_HIP_CHECK(hipMemcpyAsync(g->ustart + n_cells, &nn, sizeof(int), hipMemcpyHostToDevice, s));
-    // the table by the build's rule (smallest power of two >= 3 n_cells, >= 1024), refilled: the cell indices have shifted
-    IBL_HIP_CHECK(hipMemsetAsync(g->tkeys, 0xFF, sizeof(unsigned long long) * H, s));
+    IBL_HIP_CHECK(hipMemcpyAsync(g->v.ustart + n_cells, &nn, sizeof(int), hipMemcpyHostToDevice, s));
+    // the table (smallest power of two >= 3 n_cells, >= 1024), refilled: the cell indices have shifted
+    IBL_HIP_CHECK(hipMemsetAsync(g->v.tkeys, 0xFF, sizeof(unsigned long long) * H, s));
     IBL_HIP_CHECK(hipMemsetAsync(failed, 0, sizeof(int), s));
-    hipLaunchKernelGGL(ibl_mg_insert_bounded_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, s, g->ukeys, n_cells, g->hmask, g->tkeys,
-                       g->tvals, failed);
+    hipLaunchKernelGGL(ibl_mg_insert_bounded_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, s, g->v.ukeys, n_cells, g->v.hmask, g->v.tkeys,
+                       g->v.tvals, failed);
     IBL_LAUNCH_CHECK();
     int h_failed = 0;
     IBL_HIP_CHECK(hipMemcpyAsync(&h_failed, failed, sizeof(int), hipMemcpyDeviceToHost, s));
     IBL_HIP_CHECK(hipStreamSynchronize(s));
-    if (h_failed) return ibl_set_error(IBL_ERR_OVERFLOW, "ibl_memgrid_append: the cell table is full");
+    if (h_failed) return ibl_set_error(IBL_ERR_OVERFLOW, "%s: the cell table is full", who);
+    return IBL_OK;
+}
+
+extern "C" int ibl_memgrid_destroy(ibl_memgrid* g) {
+    if (!g) return IBL_OK;
+    (void)hipFree(g->buf[0]); (void)hipFree(g->buf[1]); (void)hipFree(g->v.ukeys); (void)hipFree(g->v.ustart);
+    (void)hipFree(g->v.tkeys); (void)hipFree(g->v.tvals);
+    delete g;
+    return IBL_OK;
+}
+
+// a build is the merge of all points into an empty grid (n = 0, no cells, ustart[0] = 0) whose point buffer holds n + reserve_points
+static int mg_build(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, int64_t reserve_points, int fixed, ibl_memgrid** out,
+                    hipStream_t s, const char* who) {
+    std::unique_ptr<ibl_memgrid, int (*)(ibl_memgrid*)> g(new ibl_memgrid(), ibl_memgrid_destroy);      // freed on every error return below
+    g->v.cell = (float)cell; g->v.inv = 1.0f / (float)cell;
+    g->fixed = fixed;
+    g->cur = 1;                                                                                          // the merge writes buf[0]
+    IBL_HIP_CHECK(hipMalloc(&g->buf[0], sizeof(float4) * (size_t)(n + reserve_points)));
+    g->buf_cap[0] = n + reserve_points;
+    IBL_HIP_CHECK(hipMalloc(&g->v.ustart, sizeof(int)));
+    IBL_HIP_CHECK(hipMemsetAsync(g->v.ustart, 0, sizeof(int), s));
+    const int st = mg_merge(ctx, g.get(), reinterpret_cast<const float4*>(mem_pts4), n, reserve_points, s, who);
+    if (st != IBL_OK) return st;
+    *out = g.release();
+    return IBL_OK;
+}
+
+extern "C" int ibl_memgrid_build(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, ibl_memgrid** out, void* stream) {
+    if (!ctx || !mem_pts4 || !out || n <= 0 || n > 0x7FFFFFF0ll || cell <= 0) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_build: bad argument");
+    return mg_build(ctx, mem_pts4, n, cell, 0, 1, out, (hipStream_t)stream, "ibl_memgrid_build");
+}
+
+extern "C" int ibl_memgrid_build_owned(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, int64_t reserve_points,
+                                       ibl_memgrid** out, void* stream) {
+    if (!ctx || !mem_pts4 || !out || n <= 0 || n > 0x7FFFFFF0ll || cell <= 0 || reserve_points < 0 || reserve_points > 0x7FFFFFF0ll - n)
+        return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_build_owned: bad argument");
+    return mg_build(ctx, mem_pts4, n, cell, reserve_points, 0, out, (hipStream_t)stream, "ibl_memgrid_build_owned");
+}
+
+extern "C" int ibl_memgrid_append(ibl_reg_ctx* ctx, ibl_memgrid* g, const float* new_pts4, int64_t n_new, void* stream) {
+    if (!ctx || !g || n_new < 0 || (n_new > 0 && !new_pts4)) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_append: bad argument");
+    if (g->fixed) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_append: a grid of ibl_memgrid_build is immutable (build it with ibl_memgrid_build_owned)");
+    if (n_new == 0) return IBL_OK;
+    if (g->v.n + n_new > 0x7FFFFFF0ll) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_append: more than 0x7FFFFFF0 points");
+    return mg_merge(ctx, g, reinterpret_cast<const float4*>(new_pts4), n_new, 0, (hipStream_t)stream, "ibl_memgrid_append");
+}
+
+extern "C" int ibl_memgrid_info(const ibl_memgrid* g, int64_t* n, int32_t* n_cells, int64_t* table_slots, int64_t* point_capacity,
+                                int32_t* ustart_end, void* stream) {
+    if (!g) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_info: grid is null");
+    if (n) *n = g->v.n;
+    if (n_cells) *n_cells = g->v.n_cells;
+    if (table_slots) *table_slots = (int64_t)(g->v.hmask + 1);
+    if (point_capacity) *point_capacity = g->buf_cap[g->cur];
+    if (ustart_end) {
+        IBL_HIP_CHECK(hipMemcpyAsync(ustart_end, g->v.ustart + g->v.n_cells, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+        IBL_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    }
     return IBL_OK;
 }
 
@@ -387,7 +298,7 @@ struct EvalJob {
 };
 
 // grid (ICP_BPJ, J): fitness / rmse partials of evaluate_registration against the whole memory
-__global__ __launch_bounds__(256) void ibl_evaluate_kernel(ibl_memgrid g, const float4* __restrict__ det, const EvalJob* __restrict__ jobs,
+__global__ __launch_bounds__(256) void ibl_evaluate_kernel(MemGridView g, const float4* __restrict__ det, const EvalJob* __restrict__ jobs,
                                                            float thr, float thr2, double* __restrict__ partial /* [J][BPJ][2] */,
                                                            float* __restrict__ d2_out /* per (job, point) or null */, int prune) {
     const int j = blockIdx.y;
@@ -501,7 +412,7 @@ static int evaluate_impl(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float*
     const int prune = !ctx->diag.eval_fullscan;          // diagnostics: full scan = every cell of the query's box (the tests compare both)
     void* tok;
     ibl_prof_begin(IBL_PROF_ST_EVAL, 24.0 * (double)(jobs[J - 1].out + (jobs[J - 1].end - jobs[J - 1].begin)), s, &tok);
-    hipLaunchKernelGGL(ibl_evaluate_kernel, dim3(ICP_BPJ, J), dim3(256), 0, s, *grid, reinterpret_cast<const float4*>(det_pts4), d_jobs,
+    hipLaunchKernelGGL(ibl_evaluate_kernel, dim3(ICP_BPJ, J), dim3(256), 0, s, grid->v, reinterpret_cast<const float4*>(det_pts4), d_jobs,
                        (float)threshold, (float)(threshold * threshold), partial, d2_out, prune);
     ibl_prof_end(tok, s);
     IBL_LAUNCH_CHECK();

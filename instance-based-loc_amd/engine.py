@@ -52,8 +52,8 @@ class MemoryShard:
     that range), registration jobs are routed between the ranks and the evaluation is reduced over them (routing.py).
     live=True (unsharded memories): the memory can grow while it is resident -- `append` adds instances without rebuilding anything.
     The embeddings, clouds and instance features then sit in buffers with room for reserve_points further points (default: an
-    eighth of the memory + 65 536) and reserve_rows further embedding rows, and the spatial hash owns its device memory
-    (ibl_memgrid_build_owned) instead of living in the arena.  Everything computed is the same as with live=False."""
+    eighth of the memory + 65 536) and reserve_rows further embedding rows, and the spatial hash accepts appends
+    (ibl_memgrid_build_owned).  Without live there is no headroom anywhere.  Everything computed is the same either way."""
 
     def __init__(self, ctx: RegContext, embeddings, clouds=None, colors=None, intensities=None, eval_threshold=0.02, device="cuda",
                  shard=None, shard_clouds=False, compact_features=False, live=False, reserve_points=None, reserve_rows=None):
@@ -77,8 +77,8 @@ class MemoryShard:
             self.mem_emb = torch.zeros((0, dim), dtype=torch.float32, device=self.device)
         self.emb_offsets = torch.from_numpy(self.emb_offsets_host).to(self.device)
         self._emb_buf = self.mem_emb
-        if self.live:
-            rows = len(raw) // 8 + 1024 if reserve_rows is None else int(reserve_rows)
+        rows = 0 if not self.live else len(raw) // 8 + 1024 if reserve_rows is None else int(reserve_rows)
+        if rows > 0:
             self._emb_buf = torch.empty((len(raw) + rows, dim), dtype=torch.float32, device=self.device)
             self._emb_buf[:len(raw)].copy_(self.mem_emb)
             self.mem_emb = self._emb_buf[:len(raw)]
@@ -97,27 +97,19 @@ class MemoryShard:
         if clouds is not None:
             if intensities is None:
                 intensities = [intensity_from_colors(c) for c in colors] if colors is not None else None
-            if not self.live:
-                self.clouds = CloudBatch.from_numpy(clouds, intensities, device=device)
-                self.grid = MemGrid(ctx, self.clouds.pts4, cell=2 * eval_threshold)
-            else:
-                n_pts = sum(len(c) for c in clouds)
-                self.reserve_points = n_pts // 8 + 65536 if reserve_points is None else int(reserve_points)
-                self.clouds = CloudBatch.from_numpy(clouds, intensities, device=device, reserve_points=self.reserve_points)
-                self.grid = MemGrid(ctx, self.clouds.pts4, cell=2 * eval_threshold, live=True, reserve_points=self.reserve_points)
+            if self.live:
+                self.reserve_points = sum(len(c) for c in clouds) // 8 + 65536 if reserve_points is None else int(reserve_points)
+            self.clouds = CloudBatch.from_numpy(clouds, intensities, device=device, reserve_points=self.reserve_points)
+            self.grid = MemGrid(ctx, self.clouds.pts4, cell=2 * eval_threshold, live=self.live, reserve_points=self.reserve_points)
 
     def features(self, voxel_size, local_dist_factor):
         """Normals, FPFH and colour gradients of every memory instance for these registration parameters: computed on first
         use, then resident in HBM (1.3 GB per 1 000 instances of 5 000 points; 0.84 GB with compact_features) for every later query."""
         key = (float(voxel_size), float(local_dist_factor))
         if key not in self._features:
-            if not self.live:
-                self._features[key] = instance_features_batch(self.ctx, self.clouds, voxel_size, 2.0 * (voxel_size * local_dist_factor),
-                                                              compact=self.compact_features)
-            else:       # room behind the rows for what is left of the clouds' own headroom
-                room = max(self.clouds._buf.shape[0] - self.clouds.n, 0)
-                self._features[key] = instance_features_batch(self.ctx, self.clouds, voxel_size, 2.0 * (voxel_size * local_dist_factor),
-                                                              compact=self.compact_features, reserve_points=room)
+            room = max(self.clouds._buf.shape[0] - self.clouds.n, 0)        # what is left of the clouds' own headroom (none unless live)
+            self._features[key] = instance_features_batch(self.ctx, self.clouds, voxel_size, 2.0 * (voxel_size * local_dist_factor),
+                                                          compact=self.compact_features, reserve_points=room)
         return self._features[key]
 
     def append(self, embeddings, clouds=None, colors=None, intensities=None):
@@ -170,7 +162,7 @@ class MemoryShard:
         torch.cuda.synchronize(self.device)
 
     def close(self):
-        """Frees the host side of the spatial hash (the device side lives in the context arena; a live memory's hash frees its own)."""
+        """Frees the spatial hash and drops the resident features."""
         if self.grid is not None:
             self.grid.close()
             self.grid = None

@@ -350,9 +350,8 @@ class ObjectMemory():
         if self._engine is None:
             if not self.memory:
                 raise RuntimeError("object memory is empty")
-            if self._shard is not None:          # a rebuilt memory: release the previous spatial hash's host record, then its arena
+            if self._shard is not None:          # a rebuilt memory: free the previous spatial hash
                 self._shard.close()
-            self._ctx.reset()
             shard = self._shard = MemoryShard(self._ctx, [np.stack(m.embeddings).astype(np.float32) for m in self.memory],
                                 [np.asarray(m.pointcloud.points) for m in self.memory],
                                 colors=[np.asarray(m.pointcloud.colors) for m in self.memory], device=self.device, live=True)

@@ -378,8 +378,9 @@ def register_evaluate_batch(ctx: RegContext, det: CloudBatch, q_per_frame, assns
 
 
 class MemGrid:
-    """Persistent spatial hash over all memory points.  It lives in the context arena; with live=True it owns its device memory
-    instead (room for reserve_points further points), `append` merges further points into it and `close` frees it."""
+    """Spatial hash over all memory points.  It owns its device memory: `close` frees it, and nothing of it lives in the context
+    arena (RegContext.reset leaves it valid).  Built once and immutable unless live=True: then the grid has room for reserve_points
+    further points and `append` merges further points into it."""
 
     def __init__(self, ctx: RegContext, mem_pts4: torch.Tensor, cell=0.04, live=False, reserve_points=0):
         assert mem_pts4.is_cuda and mem_pts4.dtype == torch.float32 and mem_pts4.shape[1] == 4 and mem_pts4.is_contiguous()
@@ -387,19 +388,17 @@ class MemGrid:
         self.cell = cell
         self.live = bool(live)
         self._h = C.c_void_p()
+        args = (ctx.handle, mem_pts4.data_ptr(), mem_pts4.shape[0], float(cell))
         if self.live:
-            st = _lib.lib.ibl_memgrid_build_owned(ctx.handle, mem_pts4.data_ptr(), mem_pts4.shape[0], float(cell), int(reserve_points),
-                                                  C.byref(self._h), _stream())
-            _lib.check(st, "ibl_memgrid_build_owned")
-            return
-        st = _lib.lib.ibl_memgrid_build(ctx.handle, mem_pts4.data_ptr(), mem_pts4.shape[0], float(cell), C.byref(self._h),
-                                        _stream())
-        _lib.check(st, "ibl_memgrid_build")
+            st = _lib.lib.ibl_memgrid_build_owned(*args, int(reserve_points), C.byref(self._h), _stream())
+        else:
+            st = _lib.lib.ibl_memgrid_build(*args, C.byref(self._h), _stream())
+        _lib.check(st, "ibl_memgrid_build_owned" if self.live else "ibl_memgrid_build")
 
     def append(self, pts4_new: torch.Tensor):
         """Merges further points (they count as the points behind all earlier ones) into a live grid: afterwards it equals the grid
         built from all points at once.  The call synchronises the current stream; no evaluation that uses the grid may be in flight
-        on another stream meanwhile.  On a grid of the arena the library refuses (IblError) and the grid is unchanged."""
+        on another stream meanwhile.  On a grid built without live=True the library refuses (IblError) and the grid is unchanged."""
         assert pts4_new.is_cuda and pts4_new.dtype == torch.float32 and pts4_new.dim() == 2 and pts4_new.shape[1] == 4 and pts4_new.is_contiguous()
         st = _lib.lib.ibl_memgrid_append(self.ctx.handle, self._h, pts4_new.data_ptr(), pts4_new.shape[0], _stream())
         _lib.check(st, "ibl_memgrid_append")
@@ -413,6 +412,7 @@ class MemGrid:
         return dict(n=n.value, n_cells=cells.value, table_slots=slots.value, point_capacity=cap.value, ustart_end=end.value)
 
     def close(self):
+        """Frees the grid, device arrays included."""
         if self._h:
             _lib.lib.ibl_memgrid_destroy(self._h)
             self._h = C.c_void_p()

@@ -15,14 +15,14 @@ import torch
 from ibloc_amd.engine import intensity_from_colors
 from ibloc_amd.registration import CloudBatch, MemGrid, RegContext, evaluate_batch, normals_fpfh_batch, register_batch
 
-_CTX = {"reg": None, "eval": None, "calls": 0}
+_CTX = {"reg": None, "calls": 0}
 RANSAC_SEED = 0          # Open3D draws from an unseeded global RNG; here the draw sequence is a function of (seed, call #)
 
 
-def _ctx(kind="reg"):
-    if _CTX[kind] is None:
-        _CTX[kind] = RegContext(4 << 30)
-    return _CTX[kind]
+def _ctx():
+    if _CTX["reg"] is None:
+        _CTX["reg"] = RegContext(4 << 30)
+    return _CTX["reg"]
 
 
 class Cloud:
@@ -115,8 +115,7 @@ def register_point_clouds(source, target, voxel_size, global_dist_factor=1.5, lo
 
 def evaluate_transform(source, target, trans_init, threshold=0.02):
     s, t = _as_cloud(source), _as_cloud(target)
-    ctx = _ctx("eval")
-    ctx.reset()
+    ctx = _ctx()
     tb = _batch(t)
     grid = MemGrid(ctx, tb.pts4, cell=2 * threshold)
     sb = _batch(s)

@@ -57,12 +57,10 @@ def main():
     build_small = MemoryShard(ctx, emb[:2], w.points[:2], intensities=ints[:2])       # warm-up (code object load)
     build_small.features(0.05, 0.4)
     build_small.close()
-    ctx.reset()
     m, out["rebuild_shard_s"], out["rebuild_features_s"] = build(False)
     out["rebuild_s"] = out["rebuild_shard_s"] + out["rebuild_features_s"]
     m.close()
     del m
-    ctx.reset()
     sync()
     t = time.perf_counter()
     cb = CloudBatch.from_numpy(w.points[:a.n], ints[:a.n])
