@@ -25,7 +25,7 @@
 #endif
 #define ICP_ACT_Y 32      // block rows of the ICP kernels once they walk the active-job list (iterations >= ICP_GROUP_FROM >= 1)
 static_assert(ICP_GROUP_FROM >= 1, "the first active-job list is written by the update of iteration ICP_GROUP_FROM - 1");
-#define ICP_NACC 29      // 21 (JTJ upper) + 6 (JTr) + count + err2  |  p2p: 3 + 3 + 9 + count + err2
+#define ICP_NACC 29      // 21 (JTJ upper) + 6 (JTr) + count + err2  |  p2p: 3 + 3 + 9, [15, 21) second moments, count + err2
 
 // ------------------------------------------------------------------------------------------------
 // ICP (coloured / point-to-point)
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256) void ibl_icp_step_kernel(const float4* __restr
             for (int a = 0; a < 6; ++a) { for (int b = a; b < 6; ++b) acc[q++] += Jr[a] * Jr[b]; }
             for (int a = 0; a < 6; ++a) acc[21 + a] += Jr[a] * r;
         } else {
-            for (int a = 0; a < 3; ++a) { acc[a] += vs[a]; acc[3 + a] += vt[a]; }
+            for (int a = 0; a < 3; ++a) { acc[a] += vs[a]; acc[3 + a] += vt[a]; acc[15 + a] += vs[a] * vs[a]; acc[18 + a] += vt[a] * vt[a]; }
             for (int rr = 0; rr < 3; ++rr) for (int cc = 0; cc < 3; ++cc) acc[6 + 3 * rr + cc] += vt[rr] * vs[cc];
         }
     }
@@ -411,6 +411,16 @@ __device__ __forceinline__ void icp_update_job(IcpState* __restrict__ st, int j,
             double sm[3], dm[3], H[3][3];
             for (int t = 0; t < 3; ++t) { sm[t] = a[t] / cnt; dm[t] = a[3 + t] / cnt; }
             for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) H[r][c] = a[6 + 3 * r + c] - cnt * dm[r] * sm[c];
+            // Every correspondence on ONE target point (a single point within reach), or from one source point: H is zero but for the
+            // rounding of the two moments it is the difference of, and the rank test of the Kabsch step is relative to the largest
+            // singular value, so it would read a rotation out of that noise (the centred sum gives exact zeros and the identity).
+            // The roundings (~24 of them along the fold, each relative to a partial sum) are bounded by
+            // |sum vt_r vs_c| <= sqrt(sum vt_r^2 * sum vs_c^2); an H that is below 2^-46 of that bound in all nine entries is zero.
+            // (A genuine cloud cannot fall under it: its H is ~ cnt * extent^2 against a bound of ~ cnt * distance^2 from the origin, so a
+            // 1 cm cluster 1 km away still sits at 1e-10 of the bound, four orders above the threshold.)
+            bool zero = true;
+            for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) zero = zero && fabs(H[r][c]) <= 0x1p-46 * sqrt(a[18 + r] * a[15 + c]);
+            if (zero) for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) H[r][c] = 0.0;
             kabsch_from_moments(sm, dm, H, U);
         }
     }
