@@ -14,13 +14,13 @@
  *   - the CALLER owns all memory.  Pointers marked [dev] are device (HBM) pointers, e.g.
  *     torch.Tensor.data_ptr(); pointers marked [host] are host pointers.  Workspace sizes come
  *     from the *_workspace_bytes() queries.  The library's own device memory is explicit: the arena of a registration context
- *     (scratch: every call releases what it took) and the arrays of a memory grid (ibl_memgrid_build* .. ibl_memgrid_destroy).
+ *     (scratch: every call releases what it took) and the arrays of a memory grid (ibl_memgrid_build .. ibl_memgrid_destroy).
  *   - all launches are asynchronous on the hipStream_t passed as `void* stream`
  *     (torch.cuda.current_stream().cuda_stream).  Functions whose results are DEVICE arrays (embed, match, candidate selection)
  *     never synchronise.  Functions that return HOST results synchronise the stream -- how often is stated per function:
  *     ibl_radius_outlier_batch 1 (grid table size), ibl_instance_features_batch 2 (bounding boxes; end),
- *     ibl_register_batch_cached 2-4 (one per group of RANSAC rounds -- most calls need one -- plus the results; one more when
- *     instances of a job lie within the influence radius of each other), ibl_evaluate_batch 1, ibl_memgrid_build / _build_owned / _append 2
+ *     ibl_register_jobs 2-4 (one per group of RANSAC rounds -- most calls need one -- plus the results; one more when
+ *     instances of a job lie within the influence radius of each other), ibl_evaluate_batch 1, ibl_memgrid_build / _append 2
  *     (cell count; end).  Plan tables are staged through pinned host memory of the registration context, so uploads never wait.
  *   - plain C types only; no torch types in any signature.
  */
@@ -367,7 +367,7 @@ int ibl_allgather_topk(ibl_comm* comm, const void* send, void* recv, int64_t byt
  * of `recv` comes from rank r.  The exchange of the per-shard candidate lists since round 3: the owner of a query row receives the
  * `world` lists of that row and nothing else (the all-gather above delivered every rank's lists to every rank). */
 int ibl_alltoall(ibl_comm* comm, const void* send, void* recv, int64_t bytes_per_pair, void* stream);
-/* in place, element-wise minimum over the ranks of n floats (ibl_evaluate_points distances) */
+/* in place, element-wise minimum over the ranks of n floats (the d2_out distances of ibl_evaluate_batch) */
 int ibl_allreduce_min(ibl_comm* comm, float* buf, int64_t n, void* stream);
 /* in place, element-wise maximum of n int32 (the "some rank needs the full rows" flag of a step) */
 int ibl_allreduce_max_i32(ibl_comm* comm, int32_t* buf, int64_t n, void* stream);
@@ -386,7 +386,7 @@ int ibl_reg_ctx_destroy(ibl_reg_ctx* ctx);
 int ibl_reg_ctx_reset(ibl_reg_ctx* ctx);
 int64_t ibl_reg_ctx_high_water(const ibl_reg_ctx* ctx);
 /* device status word (bit 0: grid table overflow, bit 1: a k-NN query took the re-scan slow path; bits 2-3 are internal to
- * ibl_register_batch_cached; bits 4 / 5, informational: a registration call since the last clear was redone with the VALU feature
+ * ibl_register_jobs; bits 4 / 5, informational: a registration call since the last clear was redone with the VALU feature
  * search / with a full-size RANSAC survivor list after the fast path's list overflowed -- same results, more time); synchronises the
  * device */
 int ibl_reg_ctx_status(ibl_reg_ctx* ctx, int clear);
@@ -417,7 +417,8 @@ int ibl_reg_ctx_set_diag(ibl_reg_ctx* ctx, const char* name, double value);
 int ibl_reg_ctx_get_diag(const ibl_reg_ctx* ctx, const char* name, double* value);
 
 /* Clouds are passed as batches of segments: pts4 [dev] N x float4 (x, y, z, intensity =
- * (r+g+b)/3), seg_off [dev] and [host] copies of the (n_seg + 1) int32 segment boundaries. */
+ * (r+g+b)/3), seg_off [dev] and [host] copies of the (n_seg + 1) int32 segment boundaries.  The registration calls take such a batch
+ * as one ibl_cloud_pool (below, after ibl_instance_features). */
 
 /* Depth image + instance masks -> one coloured cloud per mask.  Replaces
  * get_mask_coloured_pointclouds_from_depth / get_coloured_pointcloud_from_depth (utils/depth_utils.py:176-206, 46-90)
@@ -429,17 +430,14 @@ int ibl_reg_ctx_get_diag(const ibl_reg_ctx* ctx, const char* name, double* value
  * float64 one promotes the products to float64 (then rounded to the float32 of the HBM layout).
  *   depth [dev] H x W; depth_type IBL_DEPTH_F32 / IBL_DEPTH_U16 / IBL_DEPTH_F64; rgb [dev] H x W x 3 u8; masks [dev] n_masks x H x W u8
  *   pts4 [dev] capacity x float4 (n_masks * H * W always suffices), seg_off_dev [dev] / seg_off_host [HOST] n_masks + 1
+ * Additionally, on request, the clouds as the reference's Open3D containers hold them for the memory build (process_image,
+ * object_memory/object_memory.py:163-256): pts3_f64 / colors3_f64 [dev] capacity x 3 doubles, each or NULL = the numpy values (float32
+ * or float64 by the promotion rule above; colours = float32 rgb / 255) widened to double, same order as pts4.
  * The call synchronises (the cloud sizes are returned to the host). */
 enum { IBL_DEPTH_F32 = 0, IBL_DEPTH_U16 = 1, IBL_DEPTH_F64 = 2 };
 int ibl_unproject_masks(ibl_reg_ctx* ctx, const void* depth, int depth_type, const uint8_t* rgb, const uint8_t* masks, int n_masks,
-                        int H, int W, double fx, double fy, double depth_factor, float* pts4, int64_t capacity,
-                        int32_t* seg_off_dev, int32_t* seg_off_host, void* stream);
-/* Same, and additionally the clouds as the reference's Open3D containers hold them for the memory build (process_image,
- * object_memory/object_memory.py:163-256): pts3_f64 / colors3_f64 [dev] capacity x 3 doubles or NULL = the numpy values (float32
- * or float64 by the promotion rule above; colours = float32 rgb / 255) widened to double, same order as pts4. */
-int ibl_unproject_masks_f64(ibl_reg_ctx* ctx, const void* depth, int depth_type, const uint8_t* rgb, const uint8_t* masks, int n_masks,
-                            int H, int W, double fx, double fy, double depth_factor, float* pts4, double* pts3_f64, double* colors3_f64,
-                            int64_t capacity, int32_t* seg_off_dev, int32_t* seg_off_host, void* stream);
+                        int H, int W, double fx, double fy, double depth_factor, float* pts4, double* pts3_f64, double* colors3_f64,
+                        int64_t capacity, int32_t* seg_off_dev, int32_t* seg_off_host, void* stream);
 
 /* keep[i] = 1 iff the point has more than nb_points points (itself included) within `radius` of its
  * own cloud.  Replaces PointCloud.remove_radius_outlier (object_memory/object_memory.py:994-995,
@@ -457,31 +455,6 @@ int ibl_normals_fpfh_batch(ibl_reg_ctx* ctx, const float* pts4, const int32_t* s
                            int n_seg, double radius_normal, int max_nn_normal, double radius_feature, int max_nn_feature,
                            float* normals4, float* fpfh, void* stream);
 
-/* Batched register_point_clouds (utils/fpfh_register.py:100-143) over n_jobs (frame, assignment) jobs.
- * Job j registers the concatenation of up to three segments of the detected pool (job_src_seg[3j..],
- * -1 padded) onto the concatenation of up to three segments of the memory pool (job_tgt_seg), exactly
- * like object_memory/object_memory.py:1023-1034,1087-1089:
- *   IBL_REG_CENTER      subtract each side's mean first (localise does; the stand-alone function does not)
- *   IBL_REG_HAVE_COLORS normals + FPFH + RANSAC + coloured ICP; without it the reference's exception path:
- *                       point-to-point ICP from the identity (fpfh_register.py:137-141)
- * Normals, FPFH and the targets' colour gradients are evaluated on the concatenations BEFORE centring (they are
- * translation invariant; see ibl_instance_features); RANSAC and ICP run between the centred clouds.
- * RANSAC hypothesis i of job j is drawn from Philox4x32-10(counter = (i, job_id_base + j, 0, 0), key = seed).
- * Outputs are HOST arrays (the call synchronises): T_out [n_jobs][16] row-major double (between the centred
- * clouds), rmse_out / fitness_out [n_jobs] (result_icp.inlier_rmse / .fitness), means_out [n_jobs][2][3]
- * (detected mean, memory mean; zeros without IBL_REG_CENTER) or NULL, T_ransac_out [n_jobs][16] or NULL,
- * ransac_stats_out [n_jobs][3] = (hypotheses walked, validated, best inlier count) or NULL. */
-#define IBL_REG_HAVE_COLORS 1
-#define IBL_REG_CENTER 2
-#define IBL_REG_FIXED_BUDGET 4   /* RANSAC walks exactly ransac_max_iter hypotheses per job (confidence exit off): the fixed-budget
-                                    hypotheses/s figure of the benchmark, never the product setting */
-int ibl_register_batch(ibl_reg_ctx* ctx, const float* det_pts4, const int32_t* det_off_dev, const int32_t* det_off_host,
-                       int n_det_seg, const float* mem_pts4, const int32_t* mem_off_dev, const int32_t* mem_off_host,
-                       int n_mem_seg, const int32_t* job_src_seg, const int32_t* job_tgt_seg, int n_jobs, double voxel_size,
-                       double global_dist_factor, double local_dist_factor, uint64_t seed, uint32_t job_id_base,
-                       int64_t ransac_max_iter, int flags, double* T_out, double* rmse_out, double* fitness_out,
-                       double* means_out, double* T_ransac_out, int64_t* ransac_stats_out, void* stream);
-
 /* Per-instance registration features, computed ONCE per cloud and kept resident in HBM instead of once per
  * (frame, assignment) job: the reference re-runs estimate_normals / compute_fpfh_feature
  * (utils/fpfh_register.py:86-98) and the colour gradients inside registration_colored_icp
@@ -491,10 +464,10 @@ int ibl_register_batch(ibl_reg_ctx* ctx, const float* det_pts4, const int32_t* d
  * the clouds are stored in (before the per-job centring) and the value at a point of instance A inside a
  * concatenation A+B+C equals its stand-alone value unless a point of B or C lies within the influence radius
  *     R = max(2 * 5 * voxel + 2 * voxel, grad_radius + 2 * voxel)
- * of A.  ibl_register_batch_cached uses the stored values for every instance none of whose points is within R (plus a
+ * of A.  ibl_register_jobs uses the stored values for every instance none of whose points is within R (plus a
  * rounding margin) of a point of another instance of its job side -- bounding boxes first, then an exact point-set test
  * on the device for the box pairs that are close -- and recomputes the rest in the context of the job's concatenation,
- * which makes its results bit-identical to ibl_register_batch.
+ * which makes its results bit-identical to those with features == NULL.
  *   normals4 [dev] N x float4, fpfh [dev] N x 33 with every row in MATCHING ORDER (bin 11 b + c at position
  *   3 * rank(c) + {b=1: 0, b=2: 1, b=0: 2}, rank over c = 5,4,6,3,7,2,8,1,9,0,10: the three histograms from their centre
  *   bins outwards, interleaved -- the order in which the feature search sums its squared differences, so that its
@@ -519,28 +492,59 @@ typedef struct {
 int ibl_instance_features_batch(ibl_reg_ctx* ctx, const float* pts4, const int32_t* seg_off_dev, const int32_t* seg_off_host,
                                 int n_seg, double voxel_size, double grad_radius, float* normals4, float* fpfh, uint16_t* fpfh_split,
                                 float* fpfh_norm, float* grad4, float* bbox_host, void* stream);
-/* ibl_register_batch with the instance features of the detected pool and / or the memory pool (either may be NULL).
- * reuse_stats_out [HOST][6] or NULL: points served by the instance features, points recomputed, recomputed groups,
- * job sides, distinct (query instance, database instance) feature-matching pairs searched, pair uses by the jobs. */
-int ibl_register_batch_cached(ibl_reg_ctx* ctx, const float* det_pts4, const int32_t* det_off_dev, const int32_t* det_off_host,
-                              int n_det_seg, const float* mem_pts4, const int32_t* mem_off_dev, const int32_t* mem_off_host,
-                              int n_mem_seg, const int32_t* job_src_seg, const int32_t* job_tgt_seg, int n_jobs, double voxel_size,
-                              double global_dist_factor, double local_dist_factor, uint64_t seed, uint32_t job_id_base,
-                              int64_t ransac_max_iter, int flags, const ibl_instance_features* det_features,
-                              const ibl_instance_features* mem_features, double* T_out, double* rmse_out, double* fitness_out,
-                              double* means_out, double* T_ransac_out, int64_t* ransac_stats_out, int64_t* reuse_stats_out,
-                              void* stream);
-/* ibl_register_batch_cached with an explicit RANSAC job id per job (job_ids [HOST][n_jobs]) in place of job_id_base + j: the result of
- * a job is a function of its clouds, the seed and its id only, so a job routed to another rank (memory clouds sharded by instance
- * range: the owner of its target instances runs it, SURVEY 8e / routing.py) returns the bits it would have returned at home.  The
- * loop being distributed: object_memory/object_memory.py:1020-1106.  Synchronisation: as ibl_register_batch_cached. */
-int ibl_register_batch_ids(ibl_reg_ctx* ctx, const float* det_pts4, const int32_t* det_off_dev, const int32_t* det_off_host,
-                           int n_det_seg, const float* mem_pts4, const int32_t* mem_off_dev, const int32_t* mem_off_host,
-                           int n_mem_seg, const int32_t* job_src_seg, const int32_t* job_tgt_seg, const uint32_t* job_ids, int n_jobs,
-                           double voxel_size, double global_dist_factor, double local_dist_factor, uint64_t seed,
-                           int64_t ransac_max_iter, int flags, const ibl_instance_features* det_features,
-                           const ibl_instance_features* mem_features, double* T_out, double* rmse_out, double* fitness_out,
-                           double* means_out, double* T_ransac_out, int64_t* ransac_stats_out, int64_t* reuse_stats_out, void* stream);
+
+/* The arguments of the registration calls, named once. */
+typedef struct {                 /* a batch of clouds */
+    const float* pts4;           /* [dev] N x float4 */
+    const int32_t* off_dev;      /* [dev]  n_seg + 1 */
+    const int32_t* off_host;     /* [HOST] n_seg + 1 */
+    const ibl_instance_features* features;   /* or NULL: none, every instance is recomputed per job */
+    int32_t n_seg;
+} ibl_cloud_pool;
+
+#define IBL_REG_HAVE_COLORS 1
+#define IBL_REG_CENTER 2
+#define IBL_REG_FIXED_BUDGET 4   /* RANSAC walks exactly ransac_max_iter hypotheses per job (confidence exit off): the fixed-budget
+                                    hypotheses/s figure of the benchmark, never the product setting */
+typedef struct {
+    double voxel_size, global_dist_factor, local_dist_factor;
+    uint64_t seed;
+    int64_t ransac_max_iter;
+    uint32_t job_id_base;        /* used when job_ids == NULL */
+    int32_t flags;               /* IBL_REG_* */
+} ibl_register_params;
+
+typedef struct {                 /* HOST arrays, [n_jobs] rows each; which may be NULL is stated at ibl_register_jobs */
+    double *T, *rmse, *fitness, *means, *T_ransac;
+    int64_t *ransac_stats, *reuse_stats;
+} ibl_register_out;
+
+/* Batched register_point_clouds (utils/fpfh_register.py:100-143) over n_jobs (frame, assignment) jobs.
+ * Job j registers the concatenation of up to three segments of the detected pool `det` (job_src_seg[3j..],
+ * -1 padded) onto the concatenation of up to three segments of the memory pool `mem` (job_tgt_seg), exactly
+ * like object_memory/object_memory.py:1023-1034,1087-1089:
+ *   IBL_REG_CENTER      subtract each side's mean first (localise does; the stand-alone function does not)
+ *   IBL_REG_HAVE_COLORS normals + FPFH + RANSAC + coloured ICP; without it the reference's exception path:
+ *                       point-to-point ICP from the identity (fpfh_register.py:137-141)
+ * Normals, FPFH and the targets' colour gradients are evaluated on the concatenations BEFORE centring (they are
+ * translation invariant; see ibl_instance_features); RANSAC and ICP run between the centred clouds.  Either pool may carry its
+ * instance features (features != NULL): the results do not depend on them, only the work does.  Features computed for another
+ * voxel_size, or memory features whose gradient radius is not 2 * voxel_size * local_dist_factor, are refused (IBL_ERR_ARG).
+ * RANSAC hypothesis i of job j is drawn from Philox4x32-10(counter = (i, id_j, 0, 0), key = seed) with id_j = job_ids[j], or
+ * job_id_base + j when job_ids == NULL.  The result of a job is a function of its clouds, the seed and its id only, so a job routed
+ * to another rank with its id (memory clouds sharded by instance range: the owner of its target instances runs it, SURVEY 8e /
+ * routing.py; the loop being distributed: object_memory/object_memory.py:1020-1106) returns the bits it would have returned at home.
+ * Outputs are HOST arrays (the call synchronises): out->T [n_jobs][16] row-major double (between the centred
+ * clouds), rmse / fitness [n_jobs] (result_icp.inlier_rmse / .fitness), means [n_jobs][2][3]
+ * (detected mean, memory mean; zeros without IBL_REG_CENTER) or NULL, T_ransac [n_jobs][16] or NULL,
+ * ransac_stats [n_jobs][3] = (hypotheses walked, validated, best inlier count) or NULL, reuse_stats [6] or NULL: points served by
+ * the instance features, points recomputed, recomputed groups, job sides, distinct (query instance, database instance)
+ * feature-matching pairs searched, pair uses by the jobs.
+ * A null ctx / pool / pool array / job table / params / out / T / rmse / fitness, n_jobs <= 0 and voxel_size <= 0 are refused before
+ * anything is launched. */
+int ibl_register_jobs(ibl_reg_ctx* ctx, const ibl_cloud_pool* det, const ibl_cloud_pool* mem, const int32_t* job_src_seg,
+                      const int32_t* job_tgt_seg, const uint32_t* job_ids /* [HOST] n_jobs or NULL */, int n_jobs,
+                      const ibl_register_params* params, const ibl_register_out* out, void* stream);
 
 /* ---- memory build / consolidation; fp64 clouds, as the build side of the reference keeps them ---- */
 
@@ -570,75 +574,68 @@ int ibl_dbscan_batch(ibl_reg_ctx* ctx, const double* points, const int32_t* grp_
  * KD-tree Open3D rebuilds over `all_memory_pcd` on every evaluate_registration call (utils/fpfh_register.py:146-148
  * <- object_memory/object_memory.py:1104).  cell >= 2 * threshold keeps a query to <= 8 cells.
  *   The grid owns its device arrays (hipMalloc: 16 bytes per point, 12 per occupied cell, 12 per table slot); ctx's arena is
- *   scratch only (40 bytes per point + the sort's, released on return).  A grid of ibl_memgrid_build is immutable.  A failed
+ *   scratch only (40 bytes per point + the sort's, released on return).  live == 0: the grid is immutable and reserve_points must
+ *   be 0 (else IBL_ERR_ARG); live != 0: a grid for a memory that grows while it is resident, see ibl_memgrid_append.  A failed
  *   build frees what it allocated; a cell table found full is IBL_ERR_OVERFLOW.
  * ibl_memgrid_destroy frees the grid and its device arrays (NULL is a no-op); nothing may still be using it on any stream. */
 typedef struct ibl_memgrid ibl_memgrid;
-int ibl_memgrid_build(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, ibl_memgrid** out, void* stream);
+int ibl_memgrid_build(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, int live, int64_t reserve_points, ibl_memgrid** out,
+                      void* stream);
 int ibl_memgrid_destroy(ibl_memgrid* grid);
 
-/* The same grid for a memory that GROWS while it is resident (live memory): same keys, same hash, same arrays as ibl_memgrid_build
- * gives for the same points (it is the same build) -- every evaluation entry point below takes either kind.
- *   ibl_memgrid_build_owned differs from ibl_memgrid_build in two things: the point buffer holds n + reserve_points points (and the
- *   cell arrays min(reserve_points, cells / 2) further cells), and the grid accepts ibl_memgrid_append.
+/* Live memory: a grid built with live != 0 has the same keys, the same hash and the same arrays as one built with live == 0 from the
+ * same points (it is the same build) -- every evaluation entry point below takes either kind.
+ *   It differs in two things: the point buffer holds n + reserve_points points (and the cell arrays min(reserve_points, cells / 2)
+ *   further cells), and the grid accepts ibl_memgrid_append.
  *   ibl_memgrid_append merges n_new further points (new_pts4 [dev] n_new x 4 floats; they count as the points n .. n + n_new - 1)
  *   into the grid: afterwards it holds what ibl_memgrid_build returns for the old points followed by the new ones, array for array
  *   (the sort is stable and a cell keeps its points in index order, so the merge "old before new" is that sort).  One pass over
  *   the resident points into the second buffer of a ping-pong pair (allocated by the first append), cell arrays and table
  *   rebuilt; buffers that no longer fit grow by a factor of 1.5, the table keeps the rule of the build (smallest power of two
  *   >= 3 x cells, >= 1024).  Scratch: 16 bytes per point of the merged grid + 24 per new point from ctx's arena, released on return.
- *   n_new == 0 is a no-op (IBL_OK); n + n_new <= 0x7FFFFFF0; a grid of ibl_memgrid_build is refused with IBL_ERR_ARG and nothing
+ *   n_new == 0 is a no-op (IBL_OK); n + n_new <= 0x7FFFFFF0; a grid built with live == 0 is refused with IBL_ERR_ARG and nothing
  *   is launched.  A failed append that returns IBL_ERR_ARG, the arena error or an allocation error leaves the grid as it was.
  *   Synchronisation: both calls synchronise `stream` before they return.  An append frees and replaces arrays of the grid: no
  *   evaluation that uses the grid may be in flight on ANY other stream during the call, and none may be issued until it returns.
  * ibl_memgrid_info: n, occupied cells, table slots, point capacity of the current buffer and ustart[n_cells] (any pointer may be
  * NULL; asking for ustart_end reads it from the device and synchronises `stream`). */
-int ibl_memgrid_build_owned(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, int64_t reserve_points, ibl_memgrid** out,
-                            void* stream);
 int ibl_memgrid_append(ibl_reg_ctx* ctx, ibl_memgrid* grid, const float* new_pts4, int64_t n_new, void* stream);
 int ibl_memgrid_info(const ibl_memgrid* grid, int64_t* n, int32_t* n_cells, int64_t* table_slots, int64_t* point_capacity,
                      int32_t* ustart_end, void* stream);
 
 /* evaluate_transform(all_detected_pcd, all_memory_pcd, T) for n_jobs candidates: job j transforms the detected
  * points [job_begin[j], job_end[j]) of det_pts4 [dev] by T_global[j] (host, 16 doubles row-major) and looks for
- * the nearest memory point within `threshold`.  rmse_out / fitness_out: HOST arrays (the call synchronises). */
+ * the nearest memory point within `threshold`.  rmse_out / fitness_out: HOST arrays (the call synchronises).
+ *   d2_out [dev] floats or NULL: additionally the squared distance of every transformed detected point to its nearest memory point
+ *   within `threshold` (+inf when there is none), job j's points at offset sum_{i<j} (job_end[i] - job_begin[i]).  This is the
+ *   per-shard half of the sharded whole-memory evaluation of SURVEY 8(e): every rank evaluates against the memory points it owns, the
+ *   distances are combined with an all-reduce(MIN) (RCCL) and fitness / rmse follow from the combined array
+ *   (ibloc_amd.parallel.evaluate_sharded). */
 int ibl_evaluate_batch(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float* det_pts4, const int32_t* job_begin,
-                       const int32_t* job_end, const double* T_global, int n_jobs, double threshold, double* rmse_out,
-                       double* fitness_out, void* stream);
+                       const int32_t* job_end, const double* T_global, int n_jobs, double threshold, float* d2_out /* [dev] or NULL */,
+                       double* rmse_out, double* fitness_out, void* stream);
 
 /* Stage B of localise() for a batch of frames in ONE call (SURVEY 8b's fused driver; csrc/localise.hip): radius-outlier removal of
  * every detected cloud and ordered compaction (object_memory/object_memory.py:992-998), the detections' instance features, one
  * registration job per candidate assignment (:1020-1095), the global-frame transform of every job (:1096-1101), its whole-memory
  * evaluation (:1104) and the winner of every frame (highest whole-memory fitness, the first on ties, :1111-1114).  Everything is
  * the library's own stage entry points composed on the host -- the results are those of calling ibl_radius_outlier_batch,
- * ibl_instance_features_batch, ibl_register_batch_cached and ibl_evaluate_batch in turn, bit for bit.
- *   det_pts4 / det_off_dev / det_off_host: the RAW detected clouds, segments in frame order, q_per_frame [HOST][n_frames] of them per
- *   frame (<= 7 each); assn [HOST][n_frames][max_assn][6] = up to three (detection within its frame, GLOBAL memory instance) pairs
- *   per assignment, assn_len [HOST][n_frames][max_assn] pairs used, assn_count [HOST][n_frames] -- the output layout of
- *   ibl_assign_batch / ibl_assign_candidates; mem_*: the memory pool, its resident instance features and its spatial hash.
- * Outputs (HOST; the call synchronises): clean_off_host [n_det_seg + 1] offsets of the cleaned clouds, *n_jobs_out = J (jobs in
- * frame order, a frame's jobs in assignment order; J <= max_jobs = the capacity of the per-job arrays), T_out .. reuse_stats_out as
- * ibl_register_batch_cached, T_global_out [J][16], full_rmse_out / full_fitness_out [J], best_out [n_frames] = winning assignment of
+ * ibl_instance_features_batch, ibl_register_jobs and ibl_evaluate_batch in turn, bit for bit.
+ *   det: the RAW detected clouds, segments in frame order, q_per_frame [HOST][n_frames] of them per frame (<= 7 each); det->features
+ *   must be NULL (the call computes them for the cleaned clouds), else IBL_ERR_ARG; assn [HOST][n_frames][max_assn][6] = up to three
+ *   (detection within its frame, GLOBAL memory instance) pairs per assignment, assn_len [HOST][n_frames][max_assn] pairs used,
+ *   assn_count [HOST][n_frames] -- the output layout of ibl_assign_batch / ibl_assign_candidates; mem: the memory pool with its
+ *   resident instance features (required); grid: its spatial hash; params: as for ibl_register_jobs (job ids are job_id_base + j).
+ * Outputs (HOST; the call synchronises): clean_off_host [det->n_seg + 1] offsets of the cleaned clouds, *n_jobs_out = J (jobs in
+ * frame order, a frame's jobs in assignment order; J <= max_jobs = the capacity of the per-job arrays), out as for ibl_register_jobs
+ * (means is required here), T_global_out [J][16], full_rmse_out / full_fitness_out [J], best_out [n_frames] = winning assignment of
  * the frame (index into its list) or -1 for a frame without assignments. */
-int ibl_register_evaluate_batch(ibl_reg_ctx* ctx, const float* det_pts4, const int32_t* det_off_dev, const int32_t* det_off_host,
-                                int n_det_seg, const int32_t* q_per_frame, int n_frames, const int32_t* assn, const int32_t* assn_len,
-                                const int32_t* assn_count, int max_assn, const float* mem_pts4, const int32_t* mem_off_dev,
-                                const int32_t* mem_off_host, int n_mem_seg, const ibl_instance_features* mem_features,
-                                const ibl_memgrid* grid, double voxel_size, double global_dist_factor, double local_dist_factor,
-                                double outlier_radius, int outlier_nb_points, double eval_threshold, uint64_t seed, uint32_t job_id_base,
-                                int64_t ransac_max_iter, int flags, int max_jobs, int32_t* clean_off_host, int32_t* n_jobs_out,
-                                double* T_out, double* rmse_out, double* fitness_out, double* means_out, double* T_ransac_out,
-                                int64_t* ransac_stats_out, int64_t* reuse_stats_out, double* T_global_out, double* full_rmse_out,
-                                double* full_fitness_out, int32_t* best_out, void* stream);
-
-/* Same, and additionally the squared distance of every transformed detected point to its nearest memory point within `threshold`
- * (+inf when there is none): d2_out [dev] floats, job j's points at offset sum_{i<j} (job_end[i] - job_begin[i]).  This is the
- * per-shard half of the sharded whole-memory evaluation of SURVEY 8(e): every rank evaluates against the memory points it owns, the
- * distances are combined with an all-reduce(MIN) (RCCL) and fitness / rmse follow from the combined array
- * (ibloc_amd.parallel.evaluate_sharded). */
-int ibl_evaluate_points(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float* det_pts4, const int32_t* job_begin,
-                        const int32_t* job_end, const double* T_global, int n_jobs, double threshold, float* d2_out, double* rmse_out,
-                        double* fitness_out, void* stream);
+int ibl_register_evaluate_batch(ibl_reg_ctx* ctx, const ibl_cloud_pool* det, const int32_t* q_per_frame, int n_frames, const int32_t* assn,
+                                const int32_t* assn_len, const int32_t* assn_count, int max_assn, const ibl_cloud_pool* mem,
+                                const ibl_memgrid* grid, const ibl_register_params* params, double outlier_radius, int outlier_nb_points,
+                                double eval_threshold, int max_jobs, int32_t* clean_off_host, int32_t* n_jobs_out,
+                                const ibl_register_out* out, double* T_global_out, double* full_rmse_out, double* full_fitness_out,
+                                int32_t* best_out, void* stream);
 
 /* 1 - IoU of the oriented boxes of n objects, as ObjectMemory._recluster_IoU feeds scikit-learn.
  * boxes [dev] n x 15 f64 (centre, R row-major, half extents); valid [dev] n int32 (0: no box -> IoU 0 with everything);

@@ -57,32 +57,22 @@ _SIGS = {
     "ibl_reg_ctx_status": (C.c_int, [vp, C.c_int]),
     "ibl_reg_ctx_set_diag": (C.c_int, [vp, C.c_char_p, C.c_double]),
     "ibl_reg_ctx_get_diag": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_double)]),
-    "ibl_unproject_masks": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp, C.c_int64,
-                                      vp, vp, vp]),
+    "ibl_unproject_masks": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp, vp, vp,
+                                      C.c_int64, vp, vp, vp]),
     "ibl_voxel_downsample_batch": (C.c_int, [vp, vp, vp, vp, C.c_int32, C.c_double, vp, vp, vp, vp, vp]),
     "ibl_dbscan_batch": (C.c_int, [vp, vp, vp, C.c_int32, C.c_double, C.c_int32, vp, vp, vp]),
-    "ibl_unproject_masks_f64": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp, vp, vp,
-                                          C.c_int64, vp, vp, vp]),
     "ibl_radius_outlier_batch": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_double, C.c_int, vp, vp]),
     "ibl_normals_fpfh_batch": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, vp, vp, vp]),
-    "ibl_register_batch": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_double, C.c_double,
-                                     C.c_double, C.c_uint64, C.c_uint32, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "ibl_instance_features_batch": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp]),
-    "ibl_register_batch_cached": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_double, C.c_double,
-                                            C.c_double, C.c_uint64, C.c_uint32, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
-                                            vp, vp]),
-    "ibl_register_batch_ids": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_double, C.c_double,
-                                         C.c_double, C.c_uint64, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "ibl_memgrid_build": (C.c_int, [vp, vp, C.c_int64, C.c_double, C.POINTER(vp), vp]),
+    # ctx, det pool, mem pool, job_src_seg, job_tgt_seg, job_ids, n_jobs, params, out, stream (the structs: registration.py)
+    "ibl_register_jobs": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]),
+    "ibl_memgrid_build": (C.c_int, [vp, vp, C.c_int64, C.c_double, C.c_int, C.c_int64, C.POINTER(vp), vp]),
     "ibl_memgrid_destroy": (C.c_int, [vp]),
-    "ibl_memgrid_build_owned": (C.c_int, [vp, vp, C.c_int64, C.c_double, C.c_int64, C.POINTER(vp), vp]),
     "ibl_memgrid_append": (C.c_int, [vp, vp, vp, C.c_int64, vp]),
     "ibl_memgrid_info": (C.c_int, [vp, C.POINTER(C.c_int64), c_i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_i32p, vp]),
-    "ibl_evaluate_batch": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp]),
-    "ibl_register_evaluate_batch": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp,
-                                              C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_uint64, C.c_uint32,
-                                              C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "ibl_evaluate_points": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp]),
+    "ibl_evaluate_batch": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp]),
+    "ibl_register_evaluate_batch": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_double, C.c_int, C.c_double, C.c_int,
+                                              vp, vp, vp, vp, vp, vp, vp, vp]),
     "ibl_dator_head_workspace_bytes": (C.c_int64, [C.c_int]),
     "ibl_dator_head_forward": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp]),
     "ibl_preprocess_depth": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp, vp]),

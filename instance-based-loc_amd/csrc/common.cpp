@@ -20,7 +20,7 @@ int ibl_set_error(int code, const char* fmt, ...) {
 }
 
 extern "C" const char* ibl_last_error(void) { return g_err; }
-extern "C" int ibl_version(void) { return 100; }
+extern "C" int ibl_version(void) { return 101; }
 
 // ---- kernel timer: HIP events recorded on the launch stream around selected kernel families ----------
 namespace {

@@ -39,21 +39,22 @@ __global__ __launch_bounds__(256) void ibl_compact_offsets_kernel(const int* __r
 
 }  // namespace
 
-extern "C" int ibl_register_evaluate_batch(ibl_reg_ctx* ctx, const float* det_pts4, const int32_t* det_off_dev, const int32_t* det_off_host,
-                                           int n_det_seg, const int32_t* q_per_frame, int n_frames, const int32_t* assn,
-                                           const int32_t* assn_len, const int32_t* assn_count, int max_assn, const float* mem_pts4,
-                                           const int32_t* mem_off_dev, const int32_t* mem_off_host, int n_mem_seg,
-                                           const ibl_instance_features* mem_features, const ibl_memgrid* grid, double voxel_size,
-                                           double global_dist_factor, double local_dist_factor, double outlier_radius, int outlier_nb_points,
-                                           double eval_threshold, uint64_t seed, uint32_t job_id_base, int64_t ransac_max_iter, int flags,
-                                           int max_jobs, int32_t* clean_off_host, int32_t* n_jobs_out, double* T_out, double* rmse_out,
-                                           double* fitness_out, double* means_out, double* T_ransac_out, int64_t* ransac_stats_out,
-                                           int64_t* reuse_stats_out, double* T_global_out, double* full_rmse_out, double* full_fitness_out,
-                                           int32_t* best_out, void* stream) {
-    if (!ctx || !det_pts4 || !det_off_dev || !det_off_host || !q_per_frame || !assn || !assn_len || !assn_count || !mem_pts4 || !mem_off_dev ||
-        !mem_off_host || !mem_features || !grid || !clean_off_host || !n_jobs_out || !T_out || !rmse_out || !fitness_out || !means_out ||
-        !T_global_out || !full_rmse_out || !full_fitness_out || !best_out)
+extern "C" int ibl_register_evaluate_batch(ibl_reg_ctx* ctx, const ibl_cloud_pool* det, const int32_t* q_per_frame, int n_frames,
+                                           const int32_t* assn, const int32_t* assn_len, const int32_t* assn_count, int max_assn,
+                                           const ibl_cloud_pool* mem, const ibl_memgrid* grid, const ibl_register_params* params,
+                                           double outlier_radius, int outlier_nb_points, double eval_threshold, int max_jobs,
+                                           int32_t* clean_off_host, int32_t* n_jobs_out, const ibl_register_out* out, double* T_global_out,
+                                           double* full_rmse_out, double* full_fitness_out, int32_t* best_out, void* stream) {
+    if (!ctx || !det || !mem || !params || !out || !det->pts4 || !det->off_dev || !det->off_host || !q_per_frame || !assn || !assn_len ||
+        !assn_count || !mem->pts4 || !mem->off_dev || !mem->off_host || !mem->features || !grid || !clean_off_host || !n_jobs_out ||
+        !out->T || !out->rmse || !out->fitness || !out->means || !T_global_out || !full_rmse_out || !full_fitness_out || !best_out)
         return ibl_set_error(IBL_ERR_ARG, "ibl_register_evaluate_batch: null pointer");
+    if (det->features) return ibl_set_error(IBL_ERR_ARG, "ibl_register_evaluate_batch: det->features must be null (the call computes them)");
+    const float* det_pts4 = det->pts4;
+    const int32_t *det_off_dev = det->off_dev, *det_off_host = det->off_host;
+    const int n_det_seg = det->n_seg, n_mem_seg = mem->n_seg;
+    const double voxel_size = params->voxel_size;
+    double *T_out = out->T, *means_out = out->means;
     if (n_frames < 0 || n_det_seg < 0 || max_assn <= 0 || voxel_size <= 0 || outlier_radius <= 0 || eval_threshold <= 0)
         return ibl_set_error(IBL_ERR_ARG, "ibl_register_evaluate_batch: bad sizes");
     hipStream_t s = (hipStream_t)stream;
@@ -135,10 +136,8 @@ extern "C" int ibl_register_evaluate_batch(ibl_reg_ctx* ctx, const float* det_pt
     ibl_instance_features det_feat{reinterpret_cast<const float*>(nrm), fpfh, split, fnorm, nullptr, bbox.data(), voxel_size, 0.0};
 
     // ---- register every candidate assignment (:1036-1095) ---------------------------------------------------------------------------
-    st = ibl_register_batch_cached(ctx, reinterpret_cast<const float*>(clean), new_off, clean_off_host, n_det_seg, mem_pts4, mem_off_dev,
-                                   mem_off_host, n_mem_seg, job_src.data(), job_tgt.data(), J, voxel_size, global_dist_factor, local_dist_factor,
-                                   seed, job_id_base, ransac_max_iter, flags, &det_feat, mem_features, T_out, rmse_out, fitness_out, means_out,
-                                   T_ransac_out, ransac_stats_out, reuse_stats_out, stream);
+    const ibl_cloud_pool clean_pool = {reinterpret_cast<const float*>(clean), new_off, clean_off_host, &det_feat, n_det_seg};
+    st = ibl_register_jobs(ctx, &clean_pool, mem, job_src.data(), job_tgt.data(), nullptr, J, params, out, stream);
     if (st) return st;
 
     // ---- global-frame transforms (:1096-1101) and the whole-memory evaluation (:1104) -------------------------------------------------
@@ -155,8 +154,8 @@ extern "C" int ibl_register_evaluate_batch(ibl_reg_ctx* ctx, const float* det_pt
         jb[j] = clean_off_host[row0[f]];
         je[j] = clean_off_host[row0[f + 1]];
     }
-    st = ibl_evaluate_batch(ctx, grid, reinterpret_cast<const float*>(clean), jb.data(), je.data(), T_global_out, J, eval_threshold, full_rmse_out,
-                            full_fitness_out, stream);
+    st = ibl_evaluate_batch(ctx, grid, reinterpret_cast<const float*>(clean), jb.data(), je.data(), T_global_out, J, eval_threshold, nullptr,
+                            full_rmse_out, full_fitness_out, stream);
     if (st) return st;
 
     // ---- the winner of every frame: highest whole-memory fitness, the first on ties (sorted(..., reverse=True)[0], stable; :1111) ------

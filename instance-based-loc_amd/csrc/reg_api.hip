@@ -1,5 +1,6 @@
-// reg_api.hip -- C-ABI entry points of the registration path: context (device arena), batched
-// radius-outlier removal and normals + FPFH.  The fused register driver lives in reg_register.hip (its stages in
+// reg_api.hip -- C-ABI entry points of the registration path: context (device arena, diagnostic switches), batched radius-outlier
+// removal, normals + FPFH, the instance-feature driver (ibl_instance_features_batch and what the registration shares with it) and the
+// whole unproject path (depth + masks -> coloured clouds).  The register driver lives in reg_register.hip (its stages in
 // reg_match.hip, reg_ransac.hip, reg_icp.hip), the evaluation against the whole memory in reg_eval.hip.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
@@ -233,7 +234,7 @@ extern "C" int ibl_normals_fpfh_batch(ibl_reg_ctx* ctx, const float* pts4, const
 }
 
 // ------------------------------------------------------------------------------------------------
-// registration features of a batch of clouds (shared by the instance cache and by ibl_register_batch_cached)
+// registration features of a batch of clouds (shared by the instance cache and by ibl_register_jobs)
 // ------------------------------------------------------------------------------------------------
 // every FPFH row once more as the 48 fp16 search operands of reg_featnn.hip (layout, centring and error budget in its header and at
 // fm_operand_piece, reg_common.h), and the squared norm of the CENTRED row.  split may be null (instance features kept without their
@@ -442,20 +443,9 @@ static void linspace_f32(double start, double stop, int num, std::vector<float>&
     out[num - 1] = (float)stop;
 }
 
-extern "C" int ibl_unproject_masks_f64(ibl_reg_ctx* ctx, const void* depth, int depth_type, const uint8_t* rgb, const uint8_t* masks,
-                                       int n_masks, int H, int W, double fx, double fy, double depth_factor, float* pts4, double* pts3_f64,
-                                       double* colors3_f64, int64_t capacity, int32_t* seg_off_dev, int32_t* seg_off_host, void* stream);
-
 extern "C" int ibl_unproject_masks(ibl_reg_ctx* ctx, const void* depth, int depth_type, const uint8_t* rgb, const uint8_t* masks,
-                                   int n_masks, int H, int W, double fx, double fy, double depth_factor, float* pts4, int64_t capacity,
-                                   int32_t* seg_off_dev, int32_t* seg_off_host, void* stream) {
-    return ibl_unproject_masks_f64(ctx, depth, depth_type, rgb, masks, n_masks, H, W, fx, fy, depth_factor, pts4, nullptr, nullptr, capacity,
-                                   seg_off_dev, seg_off_host, stream);
-}
-
-extern "C" int ibl_unproject_masks_f64(ibl_reg_ctx* ctx, const void* depth, int depth_type, const uint8_t* rgb, const uint8_t* masks,
-                                       int n_masks, int H, int W, double fx, double fy, double depth_factor, float* pts4, double* pts3_f64,
-                                       double* colors3_f64, int64_t capacity, int32_t* seg_off_dev, int32_t* seg_off_host, void* stream) {
+                                   int n_masks, int H, int W, double fx, double fy, double depth_factor, float* pts4, double* pts3_f64,
+                                   double* colors3_f64, int64_t capacity, int32_t* seg_off_dev, int32_t* seg_off_host, void* stream) {
     if (!ctx || !seg_off_dev || !seg_off_host || n_masks < 0 || (n_masks > 0 && (!depth || !rgb || !masks || !pts4)) || H <= 0 || W <= 0 || fx == 0 || fy == 0 ||
         depth_factor == 0 || capacity < 0 || depth_type < 0 || depth_type > 2)
         return ibl_set_error(IBL_ERR_ARG, "ibl_unproject_masks: bad argument");

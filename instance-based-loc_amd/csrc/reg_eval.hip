@@ -38,7 +38,7 @@ struct MemGridView {
 // capacities.  v.sorted is buf[cur].
 struct ibl_memgrid {
     MemGridView v = {};
-    int fixed = 0;                      // 1: made by ibl_memgrid_build -- immutable, ibl_memgrid_append refuses it
+    int fixed = 0;                      // 1: made by ibl_memgrid_build with live = 0 -- immutable, ibl_memgrid_append refuses it
     float4* buf[2] = {nullptr, nullptr};
     int64_t buf_cap[2] = {0, 0};        // points
     int cur = 0;
@@ -257,21 +257,17 @@ static int mg_build(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double c
     return IBL_OK;
 }
 
-extern "C" int ibl_memgrid_build(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, ibl_memgrid** out, void* stream) {
-    if (!ctx || !mem_pts4 || !out || n <= 0 || n > 0x7FFFFFF0ll || cell <= 0) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_build: bad argument");
-    return mg_build(ctx, mem_pts4, n, cell, 0, 1, out, (hipStream_t)stream, "ibl_memgrid_build");
-}
-
-extern "C" int ibl_memgrid_build_owned(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, int64_t reserve_points,
-                                       ibl_memgrid** out, void* stream) {
+extern "C" int ibl_memgrid_build(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double cell, int live, int64_t reserve_points,
+                                 ibl_memgrid** out, void* stream) {
     if (!ctx || !mem_pts4 || !out || n <= 0 || n > 0x7FFFFFF0ll || cell <= 0 || reserve_points < 0 || reserve_points > 0x7FFFFFF0ll - n)
-        return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_build_owned: bad argument");
-    return mg_build(ctx, mem_pts4, n, cell, reserve_points, 0, out, (hipStream_t)stream, "ibl_memgrid_build_owned");
+        return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_build: bad argument");
+    if (!live && reserve_points != 0) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_build: reserve_points needs a live grid");
+    return mg_build(ctx, mem_pts4, n, cell, reserve_points, live ? 0 : 1, out, (hipStream_t)stream, "ibl_memgrid_build");
 }
 
 extern "C" int ibl_memgrid_append(ibl_reg_ctx* ctx, ibl_memgrid* g, const float* new_pts4, int64_t n_new, void* stream) {
     if (!ctx || !g || n_new < 0 || (n_new > 0 && !new_pts4)) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_append: bad argument");
-    if (g->fixed) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_append: a grid of ibl_memgrid_build is immutable (build it with ibl_memgrid_build_owned)");
+    if (g->fixed) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_append: a grid built with live = 0 is immutable (build it with live = 1)");
     if (n_new == 0) return IBL_OK;
     if (g->v.n + n_new > 0x7FFFFFF0ll) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_append: more than 0x7FFFFFF0 points");
     return mg_merge(ctx, g, reinterpret_cast<const float4*>(new_pts4), n_new, 0, (hipStream_t)stream, "ibl_memgrid_append");
@@ -294,7 +290,7 @@ extern "C" int ibl_memgrid_info(const ibl_memgrid* g, int64_t* n, int32_t* n_cel
 struct EvalJob {
     double T[12];
     int begin, end;      // detected point range (all cleaned detected clouds of the job's frame)
-    long long out;       // offset of this job's per-point distances (ibl_evaluate_points)
+    long long out;       // offset of this job's per-point distances (d2_out of ibl_evaluate_batch)
 };
 
 // grid (ICP_BPJ, J): fitness / rmse partials of evaluate_registration against the whole memory
@@ -375,24 +371,9 @@ __global__ __launch_bounds__(256) void ibl_evaluate_kernel(MemGridView g, const 
             ((sh[threadIdx.x][0] + sh[threadIdx.x][1]) + sh[threadIdx.x][2]) + sh[threadIdx.x][3];
 }
 
-static int evaluate_impl(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float* det_pts4, const int32_t* job_begin, const int32_t* job_end,
-                         const double* T_global, int n_jobs, double threshold, double* rmse_out, double* fitness_out, float* d2_out, void* stream);
-
 extern "C" int ibl_evaluate_batch(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float* det_pts4, const int32_t* job_begin,
-                                  const int32_t* job_end, const double* T_global, int n_jobs, double threshold, double* rmse_out,
-                                  double* fitness_out, void* stream) {
-    return evaluate_impl(ctx, grid, det_pts4, job_begin, job_end, T_global, n_jobs, threshold, rmse_out, fitness_out, nullptr, stream);
-}
-
-extern "C" int ibl_evaluate_points(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float* det_pts4, const int32_t* job_begin,
-                                   const int32_t* job_end, const double* T_global, int n_jobs, double threshold, float* d2_out,
-                                   double* rmse_out, double* fitness_out, void* stream) {
-    if (!d2_out) return ibl_set_error(IBL_ERR_ARG, "ibl_evaluate_points: d2_out is null");
-    return evaluate_impl(ctx, grid, det_pts4, job_begin, job_end, T_global, n_jobs, threshold, rmse_out, fitness_out, d2_out, stream);
-}
-
-static int evaluate_impl(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float* det_pts4, const int32_t* job_begin, const int32_t* job_end,
-                         const double* T_global, int n_jobs, double threshold, double* rmse_out, double* fitness_out, float* d2_out, void* stream) {
+                                  const int32_t* job_end, const double* T_global, int n_jobs, double threshold, float* d2_out,
+                                  double* rmse_out, double* fitness_out, void* stream) {
     if (!ctx || !grid || !det_pts4 || !job_begin || !job_end || !T_global || !rmse_out || !fitness_out || n_jobs <= 0 || threshold <= 0)
         return ibl_set_error(IBL_ERR_ARG, "ibl_evaluate_batch: bad argument");
     hipStream_t s = (hipStream_t)stream;

@@ -470,16 +470,16 @@ static std::vector<float> group_boxes(const HostTables& h, const MatchPlan& plan
 struct MatchDev { int* nn; SidePairs* d_sides; FeatPair* d_pairs; int* pair_idx; float* pair_d2; };
 
 static int check_instance_features(const RegCall& c, double grad_radius) {
-    const ibl_instance_features* feat[2] = {c.det_features, c.mem_features};
+    const ibl_instance_features* feat[2] = {c.det.features, c.mem.features};
     for (int pl = 0; pl < 2; ++pl) {
         if (!feat[pl]) continue;
         if (!feat[pl]->normals4 || !feat[pl]->fpfh || !feat[pl]->fpfh_norm || !feat[pl]->bbox)       // (fpfh_split may be null: compact features)
-            return ibl_set_error(IBL_ERR_ARG, "ibl_register_batch_cached: instance features with null arrays");
-        if (fabs(feat[pl]->voxel_size - c.voxel_size) > 1e-12 * c.voxel_size)
-            return ibl_set_error(IBL_ERR_ARG, "ibl_register_batch_cached: instance features were built for voxel_size %g, not %g",
-                                 feat[pl]->voxel_size, c.voxel_size);
+            return ibl_set_error(IBL_ERR_ARG, "ibl_register_jobs: instance features with null arrays");
+        if (fabs(feat[pl]->voxel_size - c.params.voxel_size) > 1e-12 * c.params.voxel_size)
+            return ibl_set_error(IBL_ERR_ARG, "ibl_register_jobs: instance features were built for voxel_size %g, not %g",
+                                 feat[pl]->voxel_size, c.params.voxel_size);
         if (pl == 1 && (!feat[pl]->grad4 || fabs(feat[pl]->grad_radius - grad_radius) > 1e-12 * grad_radius))
-            return ibl_set_error(IBL_ERR_ARG, "ibl_register_batch_cached: memory features need colour gradients of radius %g "
+            return ibl_set_error(IBL_ERR_ARG, "ibl_register_jobs: memory features need colour gradients of radius %g "
                                  "(2 * voxel_size * local_dist_factor)", grad_radius);
     }
     return IBL_OK;
@@ -500,8 +500,8 @@ static int test_near_pairs(ibl_reg_ctx* ctx, RegPass& ps, double R) {
     const float Rf = nextafterf((float)R, INFINITY);
     for (size_t p0 = 0; p0 < near.size(); p0 += 32768) {
         const unsigned np = (unsigned)std::min<size_t>(32768, near.size() - p0);
-        hipLaunchKernelGGL(ibl_near_pair_kernel, dim3(NEAR_SPLIT, np), dim3(256), 0, s, d_near + p0, ps.det, ps.call->det_off_dev, ps.mem,
-                           ps.call->mem_off_dev, Rf * Rf * 1.000001f, d_flags + p0);
+        hipLaunchKernelGGL(ibl_near_pair_kernel, dim3(NEAR_SPLIT, np), dim3(256), 0, s, d_near + p0, ps.det, ps.call->det.off_dev, ps.mem,
+                           ps.call->mem.off_dev, Rf * Rf * 1.000001f, d_flags + p0);
         IBL_LAUNCH_CHECK();
     }
     IBL_HIP_CHECK(hipMemcpyAsync(ps.plan.near_flag.data(), d_flags, sizeof(int) * near.size(), hipMemcpyDeviceToHost, s));
@@ -528,11 +528,11 @@ static int recompute_groups(ibl_reg_ctx* ctx, RegPass& ps, const HostTables& h, 
     if (st) return st;
     st = ibl_stage_upload(ctx, d_grp_off, plan.grp_off.data(), sizeof(int) * (int64_t)(G + 1), s);
     if (st) return st;
-    hipLaunchKernelGGL(ibl_group_gather_kernel, dim3((Nd + 255) / 256), dim3(256), 0, s, d_groups, G, ps.det, c.det_off_dev, ps.mem,
-                       c.mem_off_dev, d_grp_off, Pd);
+    hipLaunchKernelGGL(ibl_group_gather_kernel, dim3((Nd + 255) / 256), dim3(256), 0, s, d_groups, G, ps.det, c.det.off_dev, ps.mem,
+                       c.mem.off_dev, d_grp_off, Pd);
     IBL_LAUNCH_CHECK();
     const std::vector<float> grp_bbox = group_boxes(h, plan);
-    st = ibl_features_on_batch(ctx, Pd, d_grp_off, plan.grp_off.data(), G, grp_bbox.empty() ? nullptr : grp_bbox.data(), c.voxel_size, grad_radius,
+    st = ibl_features_on_batch(ctx, Pd, d_grp_off, plan.grp_off.data(), G, grp_bbox.empty() ? nullptr : grp_bbox.data(), c.params.voxel_size, grad_radius,
                                plan.grp_off[plan.G0], Nd, normals_d, fpfh_d, split_d, norm_d, grad_d, s);
     if (st) return st;
     src->normals[2] = normals_d; src->fpfh[2] = fpfh_d; src->grad[2] = grad_d; src->split[2] = split_d; src->norm[2] = norm_d;
@@ -649,7 +649,7 @@ static int features_and_search(ibl_reg_ctx* ctx, RegPass& ps, const HostTables& 
     const RegCall& c = *ps.call;
     ArenaMark md(ctx);
     FeatSources src{};
-    const ibl_instance_features* feat[2] = {c.det_features, c.mem_features};
+    const ibl_instance_features* feat[2] = {c.det.features, c.mem.features};
     for (int pl = 0; pl < 2; ++pl)
         if (feat[pl]) {
             src.normals[pl] = reinterpret_cast<const float4*>(feat[pl]->normals4);
@@ -685,20 +685,20 @@ int ibl_reg_match_stage(ibl_reg_ctx* ctx, RegPass& ps) {
     const double grad_radius = ps.max_dist_icp * 2.0;
     int st = check_instance_features(c, grad_radius);
     if (st) return st;
-    const HostTables h = {ps.J, ps.jobs.data(), ps.job_off.data(), {c.det_off_host, c.mem_off_host},
-                          {c.det_features ? c.det_features->bbox : nullptr, c.mem_features ? c.mem_features->bbox : nullptr}};
+    const HostTables h = {ps.J, ps.jobs.data(), ps.job_off.data(), {c.det.off_host, c.mem.off_host},
+                          {c.det.features ? c.det.features->bbox : nullptr, c.mem.features ? c.mem.features->bbox : nullptr}};
     // influence radius of a foreign point on the features of an instance (see ibloc.h) + rounding margin
-    const double rn = c.voxel_size * 2, rf = c.voxel_size * 5;
+    const double rn = c.params.voxel_size * 2, rf = c.params.voxel_size * 5;
     const double R = std::max(2 * rf + rn, grad_radius + rn) * 1.001 + 1e-4;
     list_near_candidates(h, R, &plan);
     st = test_near_pairs(ctx, ps, R);
     if (st) return st;
     ps.phase("near-pair test");
     plan_feature_reuse(h, &plan);
-    if (c.reuse_stats_out) for (int i = 0; i < 4; ++i) c.reuse_stats_out[i] = plan.reuse_stats[i];
+    if (c.out.reuse_stats) for (int i = 0; i < 4; ++i) c.out.reuse_stats[i] = plan.reuse_stats[i];
     st = plan_feature_pairs(h, &plan);
     if (st) return st;
-    if (c.reuse_stats_out) for (int i = 4; i < 6; ++i) c.reuse_stats_out[i] = plan.reuse_stats[i];
+    if (c.out.reuse_stats) for (int i = 4; i < 6; ++i) c.out.reuse_stats[i] = plan.reuse_stats[i];
     ps.phase("host plan");
     IBL_ARENA(d.d_sides, SidePairs, 2 * ps.J);
     IBL_ARENA(d.d_pairs, FeatPair, (int64_t)plan.pairs.size() + 1);

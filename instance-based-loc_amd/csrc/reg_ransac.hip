@@ -403,8 +403,8 @@ struct RansacScratch {
 static int ransac_round(ibl_reg_ctx* ctx, const RegPass& ps, const RansacScratch& r, int n_act, int round_size) {
     const RegCall& c = *ps.call;
     hipStream_t s = ps.s;
-    const unsigned seed_lo = (unsigned)c.seed, seed_hi = (unsigned)(c.seed >> 32);
-    const long long max_iter = (long long)c.ransac_max_iter;
+    const unsigned seed_lo = (unsigned)c.params.seed, seed_hi = (unsigned)(c.params.seed >> 32);
+    const long long max_iter = (long long)c.params.ransac_max_iter;
     const int nblk = round_size / 256;
     const int n_tab = n_act * nblk;           // tables are indexed by (slot in the active list, block)
     IBL_HIP_CHECK(hipMemsetAsync(r.hyp_flags, 0, (size_t)n_act * round_size, s));
@@ -414,10 +414,10 @@ static int ransac_round(ibl_reg_ctx* ctx, const RegPass& ps, const RansacScratch
     constexpr int BIG = 1024 * RANSAC_BIG_SUBS;
     if (round_size >= BIG && (int64_t)(round_size / 16384) * n_act >= RANSAC_WIDE_MIN_BLOCKS)
         hipLaunchKernelGGL(ibl_ransac_flag_kernel<RANSAC_BIG_SUBS>, dim3(round_size / BIG, n_act), dim3(256), 0, s, ps.rs, r.cp, ps.d_job_off, ps.n_corr,
-                           max_iter, r.max_dist, 0.9, seed_lo, seed_hi, c.job_id_base, round_size, r.hyp_flags, r.blk_cnt, r.active);
+                           max_iter, r.max_dist, 0.9, seed_lo, seed_hi, c.params.job_id_base, round_size, r.hyp_flags, r.blk_cnt, r.active);
     else
         hipLaunchKernelGGL(ibl_ransac_flag_kernel<4>, dim3(round_size / 4096, n_act), dim3(256), 0, s, ps.rs, r.cp, ps.d_job_off, ps.n_corr,
-                           max_iter, r.max_dist, 0.9, seed_lo, seed_hi, c.job_id_base, round_size, r.hyp_flags, r.blk_cnt, r.active);
+                           max_iter, r.max_dist, 0.9, seed_lo, seed_hi, c.params.job_id_base, round_size, r.hyp_flags, r.blk_cnt, r.active);
     IBL_LAUNCH_CHECK();
     IBL_HIP_CHECK(hipMemsetAsync(r.blk_cnt + n_tab, 0, sizeof(int), s));
     size_t tmp_bytes = r.tmp_bytes;
@@ -427,13 +427,13 @@ static int ransac_round(ibl_reg_ctx* ctx, const RegPass& ps, const RansacScratch
     IBL_LAUNCH_CHECK();
     const int sweep = (int)std::min<int64_t>(2048, ((int64_t)r.list_cap + 255) / 256);
     hipLaunchKernelGGL(ibl_ransac_transform_kernel, dim3(sweep), dim3(256), 0, s, ps.rs, r.cp, ps.d_job_off, ps.n_corr, r.active, n_act, r.max_dist, 0.9,
-                       seed_lo, seed_hi, c.job_id_base, round_size, r.blk_off, r.list, total_ptr, r.list_cap, ctx->d_status, r.e_job, r.e_T);
+                       seed_lo, seed_hi, c.params.job_id_base, round_size, r.blk_off, r.list, total_ptr, r.list_cap, ctx->d_status, r.e_job, r.e_T);
     IBL_LAUNCH_CHECK();
     hipLaunchKernelGGL(ibl_ransac_score_kernel, dim3(4096), dim3(256), 0, s, r.cp, ps.d_job_off, ps.n_corr, r.max_dist, total_ptr, r.list_cap, r.e_job,
                        r.e_T, r.e_inl, r.e_err2);
     IBL_LAUNCH_CHECK();
     hipLaunchKernelGGL(ibl_ransac_fold_kernel, dim3(n_act), dim3(64), 0, s, ps.rs, ps.J, ps.n_corr, max_iter,
-                       (c.flags & IBL_REG_FIXED_BUDGET) ? -1.0 : 0.99, round_size, r.blk_off, r.list, r.e_inl, r.e_err2, r.e_T, r.active);
+                       (c.params.flags & IBL_REG_FIXED_BUDGET) ? -1.0 : 0.99, round_size, r.blk_off, r.list, r.e_inl, r.e_err2, r.e_T, r.active);
     IBL_LAUNCH_CHECK();
     return IBL_OK;
 }
@@ -444,7 +444,7 @@ static int ransac_round(ibl_reg_ctx* ctx, const RegPass& ps, const RansacScratch
 // where most jobs stop) and then after every two -- to compact the list of running jobs and to stop.
 static int ransac_schedule(ibl_reg_ctx* ctx, const RegPass& ps, const RansacScratch& r, int* done_flags) {
     const int J = ps.J;
-    const int64_t ransac_max_iter = ps.call->ransac_max_iter;
+    const int64_t ransac_max_iter = ps.call->params.ransac_max_iter;
     hipStream_t s = ps.s;
     const int max_round = RANSAC_MAX_ROUND;
     std::vector<int> h_done(J, 0), h_list;
@@ -484,7 +484,7 @@ int ibl_reg_ransac_stage(ibl_reg_ctx* ctx, RegPass& ps) {
     ArenaMark m3(ctx);
     ibl_prof_begin(IBL_PROF_ST_RANSAC, 0.0, s, &ps.tok_ransac);
     RansacScratch r = {};
-    r.max_dist = c.voxel_size * c.global_dist_factor;
+    r.max_dist = c.params.voxel_size * c.params.global_dist_factor;
     // a round's tables hold (active jobs) x (round size) hypotheses; when only a few jobs are left (wrong assignments
     // that never reach the confidence exit walk all 4 M), rounds grow to RANSAC_TAIL_ROUND so that they still fill the GPU
     const int64_t cap_slots = std::max<int64_t>((int64_t)J * RANSAC_MAX_ROUND, (int64_t)RANSAC_TAIL_JOBS * RANSAC_TAIL_ROUND);
@@ -514,8 +514,8 @@ int ibl_reg_ransac_stage(ibl_reg_ctx* ctx, RegPass& ps) {
         const int st = ibl_stage_upload(ctx, d_job_ids, c.job_ids, sizeof(unsigned) * (int64_t)J, s);
         if (st) return st;
     }
-    hipLaunchKernelGGL(ibl_ransac_init_kernel, dim3((J + 63) / 64), dim3(64), 0, s, ps.rs, ps.n_corr, J, (long long)c.ransac_max_iter, r.max_dist,
-                       r.active, c.job_id_base, d_job_ids);
+    hipLaunchKernelGGL(ibl_ransac_init_kernel, dim3((J + 63) / 64), dim3(64), 0, s, ps.rs, ps.n_corr, J, (long long)c.params.ransac_max_iter, r.max_dist,
+                       r.active, c.params.job_id_base, d_job_ids);
     IBL_LAUNCH_CHECK();
     return ransac_schedule(ctx, ps, r, done_flags);
 }

@@ -1,4 +1,4 @@
-// reg_register.hip -- batched registration of (detected, memory) cloud pairs: the entry points, the retry loop and one pass
+// reg_register.hip -- batched registration of (detected, memory) cloud pairs: the entry point, the retry loop and one pass
 //   assemble jobs (concatenate + centre) -> grid C -> features + 33-d matching with mutual filter (reg_match.hip)
 //   -> RANSAC on correspondences (reg_ransac.hip) -> coloured / point-to-point ICP (reg_icp.hip) -> read back
 // Scoring against the whole memory is reg_eval.hip.
@@ -112,10 +112,10 @@ static int assemble_jobs(ibl_reg_ctx* ctx, RegPass& ps) {
         int ns = 0, nt = 0;
         for (int t = 0; t < 3; ++t) {
             const int a = c.job_src_seg[3 * j + t], b = c.job_tgt_seg[3 * j + t];
-            if (a >= c.n_det_seg || b >= c.n_mem_seg) return ibl_set_error(IBL_ERR_ARG, "ibl_register_batch: segment index out of range");
+            if (a >= c.det.n_seg || b >= c.mem.n_seg) return ibl_set_error(IBL_ERR_ARG, "ibl_register_jobs: segment index out of range");
             ps.jobs[j].src_seg[t] = a; ps.jobs[j].tgt_seg[t] = b;
-            if (a >= 0) ns += c.det_off_host[a + 1] - c.det_off_host[a];
-            if (b >= 0) nt += c.mem_off_host[b + 1] - c.mem_off_host[b];
+            if (a >= 0) ns += c.det.off_host[a + 1] - c.det.off_host[a];
+            if (b >= 0) nt += c.mem.off_host[b + 1] - c.mem.off_host[b];
         }
         ps.job_off[j + 1] = ns;          // sizes first, prefix below
         ps.job_off[J + j + 1] = nt;
@@ -133,11 +133,11 @@ static int assemble_jobs(ibl_reg_ctx* ctx, RegPass& ps) {
     if (st) return st;
     st = ibl_stage_upload(ctx, ps.d_job_off, ps.job_off.data(), sizeof(int) * (int64_t)(2 * J + 1), s);
     if (st) return st;
-    hipLaunchKernelGGL(ibl_job_mean_kernel, dim3(J, 2), dim3(256), 0, s, ps.d_jobs, ps.det, c.det_off_dev, ps.mem, c.mem_off_dev,
-                       (c.flags & IBL_REG_CENTER) ? 1 : 0, ps.d_means);
+    hipLaunchKernelGGL(ibl_job_mean_kernel, dim3(J, 2), dim3(256), 0, s, ps.d_jobs, ps.det, c.det.off_dev, ps.mem, c.mem.off_dev,
+                       (c.params.flags & IBL_REG_CENTER) ? 1 : 0, ps.d_means);
     IBL_LAUNCH_CHECK();
     if (N > 0) {
-        hipLaunchKernelGGL(ibl_job_gather_kernel, dim3((N + 255) / 256), dim3(256), 0, s, ps.d_jobs, J, ps.det, c.det_off_dev, ps.mem, c.mem_off_dev,
+        hipLaunchKernelGGL(ibl_job_gather_kernel, dim3((N + 255) / 256), dim3(256), 0, s, ps.d_jobs, J, ps.det, c.det.off_dev, ps.mem, c.mem.off_dev,
                            ps.d_job_off, ps.d_means, ps.P);
         IBL_LAUNCH_CHECK();
     }
@@ -152,8 +152,8 @@ static int64_t grid_c_cell_bound(const RegPass& ps, float cell0) {
     for (int sgi = 0; sgi < 4 * J; ++sgi) {
         const int pl = sgi >= J ? 1 : 0, j = pl ? (sgi - J) / 3 : sgi, only = pl ? (sgi - J) % 3 : -1;
         float lo[3], hi[3];
-        union_of_boxes(pl ? ps.jobs[j].tgt_seg : ps.jobs[j].src_seg, only, pl ? c.mem_off_host : c.det_off_host,
-                       pl ? c.mem_features->bbox : c.det_features->bbox, lo, hi);
+        union_of_boxes(pl ? ps.jobs[j].tgt_seg : ps.jobs[j].src_seg, only, pl ? c.mem.off_host : c.det.off_host,
+                       pl ? c.mem.features->bbox : c.det.features->bbox, lo, hi);
         double cells = 1;
         float cell = cell0;
         const float emax = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
@@ -174,7 +174,7 @@ static int build_grid_c(ibl_reg_ctx* ctx, RegPass& ps) {
     // side's extent -- centring moves a side, it does not stretch it beyond rounding -- and the build needs no read-back.
     // A batch with many spread-out job sides (assignments to instances far apart) would not fit the cell budget at the nominal cell
     // size: the cell grows until it does.  The neighbour walk derives its reach from the cell size, so only the work changes.
-    const bool have = c.det_features && c.mem_features && c.det_features->bbox && c.mem_features->bbox;
+    const bool have = c.det.features && c.mem.features && c.det.features->bbox && c.mem.features->bbox;
     const int64_t budget = (int64_t)128 << 20;
     float cellC = (float)(ps.max_dist_icp / ICP_CELL_DIV);
     std::vector<int> piece_off(4 * (size_t)J + 1, 0);
@@ -182,7 +182,7 @@ static int build_grid_c(ibl_reg_ctx* ctx, RegPass& ps) {
     for (int j = 0; j < J; ++j)
         for (int t = 0; t < 3; ++t) {
             const int b = ps.jobs[j].tgt_seg[t];
-            piece_off[J + 3 * j + t + 1] = piece_off[J + 3 * j + t] + (b >= 0 ? c.mem_off_host[b + 1] - c.mem_off_host[b] : 0);
+            piece_off[J + 3 * j + t + 1] = piece_off[J + 3 * j + t] + (b >= 0 ? c.mem.off_host[b + 1] - c.mem.off_host[b] : 0);
         }
     IBL_ARENA(ps.d_piece_off, int, 4 * (int64_t)J + 1);
     int st = ibl_stage_upload(ctx, ps.d_piece_off, piece_off.data(), sizeof(int) * (4 * (int64_t)J + 1), s);
@@ -209,7 +209,7 @@ static int read_back(ibl_reg_ctx* ctx, RegPass& ps, int* redo) {
     std::vector<IcpState> h_is(J);
     IBL_HIP_CHECK(hipMemcpyAsync(h_is.data(), ps.is, sizeof(IcpState) * J, hipMemcpyDeviceToHost, s));
     std::vector<RansacState> h_rs;
-    if (rs && (c.T_ransac_out || c.ransac_stats_out)) {
+    if (rs && (c.out.T_ransac || c.out.ransac_stats)) {
         h_rs.resize(J);
         IBL_HIP_CHECK(hipMemcpyAsync(h_rs.data(), rs, sizeof(RansacState) * J, hipMemcpyDeviceToHost, s));
     }
@@ -238,15 +238,15 @@ static int read_back(ibl_reg_ctx* ctx, RegPass& ps, int* redo) {
     if ((h_status & IBL_ST_FEAT_OVERFLOW) && !ps.opt.force_valu) *redo |= REDO_FEAT_VALU;
     if (*redo) return IBL_OK;
     for (int j = 0; j < J; ++j) {
-        for (int i = 0; i < 16; ++i) c.T_out[16 * j + i] = h_is[j].T[i];
-        c.rmse_out[j] = h_is[j].rmse;
-        c.fitness_out[j] = h_is[j].fitness;
-        if (c.means_out) for (int i = 0; i < 6; ++i) c.means_out[6 * j + i] = h_means[6 * j + i];
-        if (c.T_ransac_out) for (int i = 0; i < 16; ++i) c.T_ransac_out[16 * j + i] = rs ? h_rs[j].best_T[i] : ((i % 5) == 0 ? 1.0 : 0.0);
-        if (c.ransac_stats_out) {
-            c.ransac_stats_out[3 * j] = rs ? h_rs[j].walked : 0;
-            c.ransac_stats_out[3 * j + 1] = rs ? h_rs[j].validated : 0;
-            c.ransac_stats_out[3 * j + 2] = rs ? h_rs[j].best_inl : 0;
+        for (int i = 0; i < 16; ++i) c.out.T[16 * j + i] = h_is[j].T[i];
+        c.out.rmse[j] = h_is[j].rmse;
+        c.out.fitness[j] = h_is[j].fitness;
+        if (c.out.means) for (int i = 0; i < 6; ++i) c.out.means[6 * j + i] = h_means[6 * j + i];
+        if (c.out.T_ransac) for (int i = 0; i < 16; ++i) c.out.T_ransac[16 * j + i] = rs ? h_rs[j].best_T[i] : ((i % 5) == 0 ? 1.0 : 0.0);
+        if (c.out.ransac_stats) {
+            c.out.ransac_stats[3 * j] = rs ? h_rs[j].walked : 0;
+            c.out.ransac_stats[3 * j + 1] = rs ? h_rs[j].validated : 0;
+            c.out.ransac_stats[3 * j + 2] = rs ? h_rs[j].best_inl : 0;
         }
     }
     return IBL_OK;
@@ -259,10 +259,10 @@ static int register_pass(ibl_reg_ctx* ctx, const RegCall& c, RegPassOpts opt, in
     *redo = 0;
     RegPass ps = {};
     ps.call = &c; ps.opt = opt; ps.s = c.stream; ps.J = c.n_jobs;
-    ps.colored = (c.flags & IBL_REG_HAVE_COLORS) != 0;
-    ps.max_dist_icp = c.voxel_size * c.local_dist_factor;
-    ps.det = reinterpret_cast<const float4*>(c.det_pts4);
-    ps.mem = reinterpret_cast<const float4*>(c.mem_pts4);
+    ps.colored = (c.params.flags & IBL_REG_HAVE_COLORS) != 0;
+    ps.max_dist_icp = c.params.voxel_size * c.params.local_dist_factor;
+    ps.det = reinterpret_cast<const float4*>(c.det.pts4);
+    ps.mem = reinterpret_cast<const float4*>(c.mem.pts4);
     hipStream_t s = ps.s;
     ArenaMark mark(ctx);
     hipLaunchKernelGGL(ibl_status_clear_kernel, dim3(1), dim3(1), 0, s, ctx->d_status, IBL_ST_FEAT_OVERFLOW | IBL_ST_RANSAC_OVERFLOW);
@@ -298,13 +298,8 @@ static int register_pass(ibl_reg_ctx* ctx, const RegCall& c, RegPassOpts opt, in
     return read_back(ctx, ps, redo);
 }
 
-// the argument checks, then at most three passes: the first, one with the lists it asked to avoid, and one more if that pass
-// overflowed the OTHER list
+// at most three passes: the first, one with the lists it asked to avoid, and one more if that pass overflowed the OTHER list
 static int register_call(ibl_reg_ctx* ctx, const RegCall& c) {
-    if (!ctx || !c.det_pts4 || !c.mem_pts4 || !c.det_off_dev || !c.mem_off_dev || !c.det_off_host || !c.mem_off_host || !c.job_src_seg ||
-        !c.job_tgt_seg || !c.T_out || !c.rmse_out || !c.fitness_out)
-        return ibl_set_error(IBL_ERR_ARG, "ibl_register_batch: null pointer");
-    if (c.n_jobs <= 0 || c.voxel_size <= 0) return ibl_set_error(IBL_ERR_ARG, "ibl_register_batch: bad sizes");
     RegPassOpts opt;
     int st = IBL_OK;
     for (int pass = 0; pass < 3; ++pass) {
@@ -320,46 +315,15 @@ static int register_call(ibl_reg_ctx* ctx, const RegCall& c) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// entry points (include/ibloc.h): each fills a RegCall in the order of its fields
+// the entry point (include/ibloc.h): the argument checks, then the call with the public structs copied into a RegCall
 // ------------------------------------------------------------------------------------------------
-extern "C" int ibl_register_batch(ibl_reg_ctx* ctx, const float* det_pts4, const int32_t* det_off_dev, const int32_t* det_off_host,
-                                  int n_det_seg, const float* mem_pts4, const int32_t* mem_off_dev, const int32_t* mem_off_host,
-                                  int n_mem_seg, const int32_t* job_src_seg, const int32_t* job_tgt_seg, int n_jobs, double voxel_size,
-                                  double global_dist_factor, double local_dist_factor, uint64_t seed, uint32_t job_id_base,
-                                  int64_t ransac_max_iter, int flags, double* T_out, double* rmse_out, double* fitness_out,
-                                  double* means_out, double* T_ransac_out, int64_t* ransac_stats_out, void* stream) {
-    const RegCall c = {det_pts4, det_off_dev, det_off_host, n_det_seg, mem_pts4, mem_off_dev, mem_off_host, n_mem_seg, job_src_seg, job_tgt_seg,
-                       nullptr, n_jobs, voxel_size, global_dist_factor, local_dist_factor, seed, job_id_base, ransac_max_iter, flags, nullptr,
-                       nullptr, T_out, rmse_out, fitness_out, means_out, T_ransac_out, ransac_stats_out, nullptr, (hipStream_t)stream};
-    return register_call(ctx, c);
-}
-
-extern "C" int ibl_register_batch_cached(ibl_reg_ctx* ctx, const float* det_pts4, const int32_t* det_off_dev, const int32_t* det_off_host,
-                                         int n_det_seg, const float* mem_pts4, const int32_t* mem_off_dev, const int32_t* mem_off_host,
-                                         int n_mem_seg, const int32_t* job_src_seg, const int32_t* job_tgt_seg, int n_jobs,
-                                         double voxel_size, double global_dist_factor, double local_dist_factor, uint64_t seed,
-                                         uint32_t job_id_base, int64_t ransac_max_iter, int flags,
-                                         const ibl_instance_features* det_features, const ibl_instance_features* mem_features,
-                                         double* T_out, double* rmse_out, double* fitness_out, double* means_out, double* T_ransac_out,
-                                         int64_t* ransac_stats_out, int64_t* reuse_stats_out, void* stream) {
-    const RegCall c = {det_pts4, det_off_dev, det_off_host, n_det_seg, mem_pts4, mem_off_dev, mem_off_host, n_mem_seg, job_src_seg, job_tgt_seg,
-                       nullptr, n_jobs, voxel_size, global_dist_factor, local_dist_factor, seed, job_id_base, ransac_max_iter, flags, det_features,
-                       mem_features, T_out, rmse_out, fitness_out, means_out, T_ransac_out, ransac_stats_out, reuse_stats_out, (hipStream_t)stream};
-    return register_call(ctx, c);
-}
-
-// ibl_register_batch_cached with explicit RANSAC job ids (host array, one per job): a job keeps its id -- and therefore its result, bit
-// for bit -- whichever rank and batch it is executed in (the sharded-cloud routing of routing.py).
-extern "C" int ibl_register_batch_ids(ibl_reg_ctx* ctx, const float* det_pts4, const int32_t* det_off_dev, const int32_t* det_off_host,
-                                      int n_det_seg, const float* mem_pts4, const int32_t* mem_off_dev, const int32_t* mem_off_host,
-                                      int n_mem_seg, const int32_t* job_src_seg, const int32_t* job_tgt_seg, const uint32_t* job_ids, int n_jobs,
-                                      double voxel_size, double global_dist_factor, double local_dist_factor, uint64_t seed,
-                                      int64_t ransac_max_iter, int flags, const ibl_instance_features* det_features,
-                                      const ibl_instance_features* mem_features, double* T_out, double* rmse_out, double* fitness_out,
-                                      double* means_out, double* T_ransac_out, int64_t* ransac_stats_out, int64_t* reuse_stats_out, void* stream) {
-    if (!job_ids) return ibl_set_error(IBL_ERR_ARG, "ibl_register_batch_ids: null job ids");
-    const RegCall c = {det_pts4, det_off_dev, det_off_host, n_det_seg, mem_pts4, mem_off_dev, mem_off_host, n_mem_seg, job_src_seg, job_tgt_seg,
-                       job_ids, n_jobs, voxel_size, global_dist_factor, local_dist_factor, seed, 0, ransac_max_iter, flags, det_features,
-                       mem_features, T_out, rmse_out, fitness_out, means_out, T_ransac_out, ransac_stats_out, reuse_stats_out, (hipStream_t)stream};
+extern "C" int ibl_register_jobs(ibl_reg_ctx* ctx, const ibl_cloud_pool* det, const ibl_cloud_pool* mem, const int32_t* job_src_seg,
+                                 const int32_t* job_tgt_seg, const uint32_t* job_ids, int n_jobs, const ibl_register_params* params,
+                                 const ibl_register_out* out, void* stream) {
+    if (!ctx || !det || !mem || !params || !out || !det->pts4 || !mem->pts4 || !det->off_dev || !mem->off_dev || !det->off_host ||
+        !mem->off_host || !job_src_seg || !job_tgt_seg || !out->T || !out->rmse || !out->fitness)
+        return ibl_set_error(IBL_ERR_ARG, "ibl_register_jobs: null pointer");
+    if (n_jobs <= 0 || params->voxel_size <= 0) return ibl_set_error(IBL_ERR_ARG, "ibl_register_jobs: bad sizes");
+    const RegCall c = {*det, *mem, job_src_seg, job_tgt_seg, job_ids, n_jobs, *params, *out, (hipStream_t)stream};
     return register_call(ctx, c);
 }

@@ -13,18 +13,14 @@
 #define ICP_BPJ 8        // blocks per job in the ICP / evaluation reductions (each ends in a 29-value fp64 block reduction)
 
 // ---- the call -------------------------------------------------------------------------------------
-// Arguments of ibl_register_batch / _cached / _ids, in the order of the C-ABI (include/ibloc.h describes them).
+// Arguments of ibl_register_jobs: the public structs of include/ibloc.h (which describes them) by value, the job arrays and the stream.
 struct RegCall {
-    const float* det_pts4; const int32_t* det_off_dev; const int32_t* det_off_host; int n_det_seg;
-    const float* mem_pts4; const int32_t* mem_off_dev; const int32_t* mem_off_host; int n_mem_seg;
+    ibl_cloud_pool det, mem;
     const int32_t* job_src_seg; const int32_t* job_tgt_seg;
-    const uint32_t* job_ids;          // host array, one Philox counter word per job, or null: job_id_base + j
+    const uint32_t* job_ids;          // host array, one Philox counter word per job, or null: params.job_id_base + j
     int n_jobs;
-    double voxel_size, global_dist_factor, local_dist_factor;
-    uint64_t seed; uint32_t job_id_base; int64_t ransac_max_iter; int flags;
-    const ibl_instance_features* det_features; const ibl_instance_features* mem_features;
-    double *T_out, *rmse_out, *fitness_out, *means_out, *T_ransac_out;
-    int64_t *ransac_stats_out, *reuse_stats_out;
+    ibl_register_params params;
+    ibl_register_out out;
     hipStream_t stream;
 };
 // Choices of one pass: a call is redone with these set after a list overflowed (register_call)
@@ -49,7 +45,7 @@ struct RansacState {
     long long est_k, next_i, walked, validated, last_update;
     int best_inl;
     int done;
-    unsigned job_id;          // the Philox counter word of this job: job_id_base + slot, or the caller's own id (ibl_register_batch_ids)
+    unsigned job_id;          // the Philox counter word of this job: job_id_base + slot, or the caller's own id (job_ids of ibl_register_jobs)
     int pad_;
 };
 struct IcpState {
@@ -76,7 +72,7 @@ struct MatchPlan {
     std::vector<SidePairs> sides;
     int64_t pair_pts = 0, pts0 = 0;
     int n_pairs0 = 0, max_q = 1;
-    int64_t reuse_stats[6] = {0, 0, 0, 0, 0, 0};         // ibl_register_batch_cached's reuse_stats_out
+    int64_t reuse_stats[6] = {0, 0, 0, 0, 0, 0};         // ibl_register_out::reuse_stats
 };
 
 // union of the boxes ([6] = min xyz, max xyz) of the non-empty instances among segs[0..3) (only >= 0: that slot alone); zeros if none

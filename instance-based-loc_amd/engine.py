@@ -53,7 +53,7 @@ class MemoryShard:
     live=True (unsharded memories): the memory can grow while it is resident -- `append` adds instances without rebuilding anything.
     The embeddings, clouds and instance features then sit in buffers with room for reserve_points further points (default: an
     eighth of the memory + 65 536) and reserve_rows further embedding rows, and the spatial hash accepts appends
-    (ibl_memgrid_build_owned).  Without live there is no headroom anywhere.  Everything computed is the same either way."""
+    (ibl_memgrid_build with live = 1).  Without live there is no headroom anywhere.  Everything computed is the same either way."""
 
     def __init__(self, ctx: RegContext, embeddings, clouds=None, colors=None, intensities=None, eval_threshold=0.02, device="cuda",
                  shard=None, shard_clouds=False, compact_features=False, live=False, reserve_points=None, reserve_rows=None):

@@ -101,6 +101,16 @@ class CloudBatch:
     def n(self):
         return int(self.seg_off_host[-1])
 
+    def as_pool(self, features=None):
+        """the batch as the ibl_cloud_pool a registration call takes, with the InstanceFeatures of its clouds or none.  The struct holds
+        what its pointers need alive (tensors, host arrays, the feature struct): keep IT until the call has returned."""
+        pool = _PoolStruct(self.pts4.data_ptr(), self.seg_off.data_ptr(), self.seg_off_host.ctypes.data, None, self.n_seg)
+        pool._keep = (self.pts4, self.seg_off, self.seg_off_host, features)
+        if features is not None:
+            pool._feat = features.as_struct()
+            pool.features = C.addressof(pool._feat)
+        return pool
+
     @staticmethod
     def from_numpy(clouds, intensities=None, device="cuda", reserve_points=0):
         """clouds: list of (n_i, 3) arrays; intensities: list of (n_i,) or None (zeros).  reserve_points: room for that many further
@@ -158,10 +168,10 @@ def unproject_masks(ctx: RegContext, depth: torch.Tensor, rgb: torch.Tensor, mas
     off_host = np.zeros(n + 1, dtype=np.int32)
     p64 = torch.empty((max(cap, 1), 3), dtype=torch.float64, device=dev) if want_f64 else None
     c64 = torch.empty((max(cap, 1), 3), dtype=torch.float64, device=dev) if want_f64 else None
-    st = _lib.lib.ibl_unproject_masks_f64(ctx.handle, d.data_ptr(), is_u16, rgb.data_ptr(), m.data_ptr(), n, H, W, float(fx), float(fy),
-                                          float(depth_factor), pts4.data_ptr(), p64.data_ptr() if want_f64 else None,
-                                          c64.data_ptr() if want_f64 else None, cap, off_dev.data_ptr(), off_host.ctypes.data, _stream())
-    _lib.check(st, "ibl_unproject_masks_f64")
+    st = _lib.lib.ibl_unproject_masks(ctx.handle, d.data_ptr(), is_u16, rgb.data_ptr(), m.data_ptr(), n, H, W, float(fx), float(fy),
+                                      float(depth_factor), pts4.data_ptr(), p64.data_ptr() if want_f64 else None,
+                                      c64.data_ptr() if want_f64 else None, cap, off_dev.data_ptr(), off_host.ctypes.data, _stream())
+    _lib.check(st, "ibl_unproject_masks")
     batch = CloudBatch(pts4[:int(off_host[-1])].contiguous() if off_host[-1] != cap or cap == 0 else pts4, off_host)
     if want_f64:
         return batch, p64[:int(off_host[-1])], c64[:int(off_host[-1])]
@@ -202,6 +212,20 @@ class _FeatStruct(C.Structure):
     _fields_ = [("normals4", C.c_void_p), ("fpfh", C.c_void_p), ("fpfh_split", C.c_void_p), ("fpfh_norm", C.c_void_p),
                 ("grad4", C.c_void_p), ("bbox", C.c_void_p),
                 ("voxel_size", C.c_double), ("grad_radius", C.c_double)]
+
+
+class _PoolStruct(C.Structure):              # ibl_cloud_pool
+    _fields_ = [("pts4", C.c_void_p), ("off_dev", C.c_void_p), ("off_host", C.c_void_p), ("features", C.c_void_p), ("n_seg", C.c_int32)]
+
+
+class _ParamsStruct(C.Structure):            # ibl_register_params
+    _fields_ = [("voxel_size", C.c_double), ("global_dist_factor", C.c_double), ("local_dist_factor", C.c_double), ("seed", C.c_uint64),
+                ("ransac_max_iter", C.c_int64), ("job_id_base", C.c_uint32), ("flags", C.c_int32)]
+
+
+class _OutStruct(C.Structure):               # ibl_register_out
+    _fields_ = [("T", C.c_void_p), ("rmse", C.c_void_p), ("fitness", C.c_void_p), ("means", C.c_void_p), ("T_ransac", C.c_void_p),
+                ("ransac_stats", C.c_void_p), ("reuse_stats", C.c_void_p)]
 
 
 class InstanceFeatures:
@@ -248,7 +272,7 @@ class InstanceFeatures:
 def instance_features_batch(ctx: RegContext, batch: CloudBatch, voxel_size: float, grad_radius: float = 0.0,
                             compact: bool = False, reserve_points: int = 0) -> InstanceFeatures:
     """Normals (2 voxel, 30 nn), FPFH (5 voxel, 100 nn) and, with grad_radius > 0, colour gradients (grad_radius, 30 nn) of
-    every cloud on its own, in the frame it is stored in -- what ibl_register_batch_cached reuses across jobs.
+    every cloud on its own, in the frame it is stored in -- what ibl_register_jobs reuses across jobs.
     compact: do not keep the rows a second time as fp16 search operands (96 of the 264 bytes per point; same registration results,
     the matrix-core search converts on the fly -- for memories whose resident features would not fit otherwise).
     reserve_points: the arrays are allocated with room for that many further points (InstanceFeatures.append) and exposed as views."""
@@ -280,6 +304,24 @@ REG_CENTER = 2
 REG_FIXED_BUDGET = 4        # benchmark only: RANSAC walks exactly ransac_max_iter hypotheses per job (no confidence exit)
 
 
+def _register_args(J, voxel_size, global_dist_factor, local_dist_factor, seed, job_id_base, ransac_max_iter, have_colors, center, fixed_budget):
+    """params struct, out struct and the dict of host arrays (room for J jobs) the out struct points into"""
+    flags = (REG_HAVE_COLORS if have_colors else 0) | (REG_CENTER if center else 0) | (REG_FIXED_BUDGET if fixed_budget else 0)
+    params = _ParamsStruct(float(voxel_size), float(global_dist_factor), float(local_dist_factor), int(seed), int(ransac_max_iter),
+                           int(job_id_base), flags)
+    res = dict(T=np.zeros((J, 16)), rmse=np.zeros(J), fitness=np.zeros(J), means=np.zeros((J, 2, 3)), T_ransac=np.zeros((J, 16)),
+               ransac_stats=np.zeros((J, 3), dtype=np.int64), reuse=np.zeros(6, dtype=np.int64))
+    out = _OutStruct(*(res[k].ctypes.data for k in ("T", "rmse", "fitness", "means", "T_ransac", "ransac_stats", "reuse")))
+    return params, out, res
+
+
+def _job_results(res, J):
+    """the first J jobs of the host arrays of _register_args as the wrappers return them"""
+    r = {k: (v if k == "reuse" else v[:J]) for k, v in res.items()}
+    r["T"], r["T_ransac"] = r["T"].reshape(J, 4, 4), r["T_ransac"].reshape(J, 4, 4)
+    return r
+
+
 def register_batch(ctx: RegContext, det: CloudBatch, mem: CloudBatch, job_src_seg, job_tgt_seg, voxel_size,
                    global_dist_factor=1.5, local_dist_factor=0.4, seed=0, job_id_base=0, ransac_max_iter=4000000,
                    have_colors=True, center=True, det_features: InstanceFeatures = None, mem_features: InstanceFeatures = None,
@@ -289,7 +331,7 @@ def register_batch(ctx: RegContext, det: CloudBatch, mem: CloudBatch, job_src_se
     (instance_features_batch); the results do not depend on them, only the work does.  Returns dict of host arrays:
     T (J,4,4), rmse, fitness, means (J,2,3), T_ransac (J,4,4), ransac_stats (J,3), reuse (points served by the instance
     features, points recomputed, recomputed groups, job sides, distinct matching pairs, pair uses).
-    job_ids: (J,) explicit RANSAC ids instead of job_id_base + j (ibl_register_batch_ids: jobs routed between ranks keep theirs)."""
+    job_ids: (J,) explicit RANSAC ids instead of job_id_base + j (jobs routed between ranks keep theirs)."""
     def pad(a):
         a = np.asarray(a, dtype=np.int32)
         if a.ndim == 1:
@@ -301,39 +343,15 @@ def register_batch(ctx: RegContext, det: CloudBatch, mem: CloudBatch, job_src_se
     js, jt = pad(job_src_seg), pad(job_tgt_seg)
     J = js.shape[0]
     assert jt.shape[0] == J
-    T = np.zeros((J, 16), dtype=np.float64)
-    rmse = np.zeros(J, dtype=np.float64)
-    fit = np.zeros(J, dtype=np.float64)
-    means = np.zeros((J, 2, 3), dtype=np.float64)
-    Tr = np.zeros((J, 16), dtype=np.float64)
-    stats = np.zeros((J, 3), dtype=np.int64)
-    flags = (REG_HAVE_COLORS if have_colors else 0) | (REG_CENTER if center else 0) | (REG_FIXED_BUDGET if fixed_budget else 0)
-    reuse = np.zeros(6, dtype=np.int64)
-    df = det_features.as_struct() if det_features is not None else None
-    mf = mem_features.as_struct() if mem_features is not None else None
-    if job_ids is not None:
-        ids = np.ascontiguousarray(job_ids, dtype=np.uint32)
-        assert ids.shape == (J,)
-        st = _lib.lib.ibl_register_batch_ids(ctx.handle, det.pts4.data_ptr(), det.seg_off.data_ptr(), det.seg_off_host.ctypes.data,
-                                             det.n_seg, mem.pts4.data_ptr(), mem.seg_off.data_ptr(), mem.seg_off_host.ctypes.data,
-                                             mem.n_seg, js.ctypes.data, jt.ctypes.data, ids.ctypes.data, J, float(voxel_size),
-                                             float(global_dist_factor), float(local_dist_factor), int(seed), int(ransac_max_iter), flags,
-                                             C.byref(df) if df is not None else None, C.byref(mf) if mf is not None else None,
-                                             T.ctypes.data, rmse.ctypes.data, fit.ctypes.data, means.ctypes.data, Tr.ctypes.data,
-                                             stats.ctypes.data, reuse.ctypes.data, _stream())
-        _lib.check(st, "ibl_register_batch_ids")
-        return dict(T=T.reshape(J, 4, 4), rmse=rmse, fitness=fit, means=means, T_ransac=Tr.reshape(J, 4, 4), ransac_stats=stats,
-                    reuse=reuse)
-    st = _lib.lib.ibl_register_batch_cached(ctx.handle, det.pts4.data_ptr(), det.seg_off.data_ptr(), det.seg_off_host.ctypes.data,
-                                            det.n_seg, mem.pts4.data_ptr(), mem.seg_off.data_ptr(), mem.seg_off_host.ctypes.data,
-                                            mem.n_seg, js.ctypes.data, jt.ctypes.data, J, float(voxel_size), float(global_dist_factor),
-                                            float(local_dist_factor), int(seed), int(job_id_base), int(ransac_max_iter), flags,
-                                            C.byref(df) if df is not None else None, C.byref(mf) if mf is not None else None,
-                                            T.ctypes.data, rmse.ctypes.data, fit.ctypes.data, means.ctypes.data, Tr.ctypes.data,
-                                            stats.ctypes.data, reuse.ctypes.data, _stream())
-    _lib.check(st, "ibl_register_batch_cached")
-    return dict(T=T.reshape(J, 4, 4), rmse=rmse, fitness=fit, means=means, T_ransac=Tr.reshape(J, 4, 4), ransac_stats=stats,
-                reuse=reuse)
+    ids = None if job_ids is None else np.ascontiguousarray(job_ids, dtype=np.uint32)
+    assert ids is None or ids.shape == (J,)
+    params, out, res = _register_args(J, voxel_size, global_dist_factor, local_dist_factor, seed, job_id_base, ransac_max_iter, have_colors,
+                                      center, fixed_budget)
+    det_pool, mem_pool = det.as_pool(det_features), mem.as_pool(mem_features)
+    st = _lib.lib.ibl_register_jobs(ctx.handle, C.byref(det_pool), C.byref(mem_pool), js.ctypes.data, jt.ctypes.data,
+                                    None if ids is None else ids.ctypes.data, J, C.byref(params), C.byref(out), _stream())
+    _lib.check(st, "ibl_register_jobs")
+    return _job_results(res, J)
 
 
 def register_evaluate_batch(ctx: RegContext, det: CloudBatch, q_per_frame, assns, mem: CloudBatch, mem_features: InstanceFeatures, grid,
@@ -359,22 +377,18 @@ def register_evaluate_batch(ctx: RegContext, det: CloudBatch, q_per_frame, assns
     Jc = max(J, 1)
     clean_off = np.zeros(det.n_seg + 1, dtype=np.int32)
     n_jobs = C.c_int32(0)
-    T = np.zeros((Jc, 16)); rmse = np.zeros(Jc); fit = np.zeros(Jc); means = np.zeros((Jc, 2, 3)); Tr = np.zeros((Jc, 16))
-    stats = np.zeros((Jc, 3), dtype=np.int64); reuse = np.zeros(6, dtype=np.int64)
+    params, out, res = _register_args(Jc, voxel_size, global_dist_factor, local_dist_factor, seed, job_id_base, ransac_max_iter, have_colors,
+                                      center, fixed_budget)
     G = np.zeros((Jc, 16)); frmse = np.zeros(Jc); ffit = np.zeros(Jc); best = np.full(max(F, 1), -1, dtype=np.int32)
-    flags = (REG_HAVE_COLORS if have_colors else 0) | (REG_CENTER if center else 0) | (REG_FIXED_BUDGET if fixed_budget else 0)
-    mf = mem_features.as_struct()
+    det_pool, mem_pool = det.as_pool(), mem.as_pool(mem_features)
     st = _lib.lib.ibl_register_evaluate_batch(
-        ctx.handle, det.pts4.data_ptr(), det.seg_off.data_ptr(), det.seg_off_host.ctypes.data, det.n_seg, q.ctypes.data, F, assn.ctypes.data,
-        alen.ctypes.data, acnt.ctypes.data, max_assn, mem.pts4.data_ptr(), mem.seg_off.data_ptr(), mem.seg_off_host.ctypes.data, mem.n_seg,
-        C.byref(mf), grid.handle, float(voxel_size), float(global_dist_factor), float(local_dist_factor), float(outlier_radius),
-        int(outlier_nb_points), float(eval_threshold), int(seed), int(job_id_base), int(ransac_max_iter), flags, Jc, clean_off.ctypes.data,
-        C.byref(n_jobs), T.ctypes.data, rmse.ctypes.data, fit.ctypes.data, means.ctypes.data, Tr.ctypes.data, stats.ctypes.data,
-        reuse.ctypes.data, G.ctypes.data, frmse.ctypes.data, ffit.ctypes.data, best.ctypes.data, _stream())
+        ctx.handle, C.byref(det_pool), q.ctypes.data, F, assn.ctypes.data, alen.ctypes.data, acnt.ctypes.data, max_assn, C.byref(mem_pool),
+        grid.handle, C.byref(params), float(outlier_radius), int(outlier_nb_points), float(eval_threshold), Jc, clean_off.ctypes.data,
+        C.byref(n_jobs), C.byref(out), G.ctypes.data, frmse.ctypes.data, ffit.ctypes.data, best.ctypes.data, _stream())
     _lib.check(st, "ibl_register_evaluate_batch")
     assert n_jobs.value == J
-    return dict(clean_off=clean_off, T=T[:J].reshape(J, 4, 4), rmse=rmse[:J], fitness=fit[:J], means=means[:J], T_ransac=Tr[:J].reshape(J, 4, 4),
-                ransac_stats=stats[:J], reuse=reuse, T_global=G[:J].reshape(J, 4, 4), full_rmse=frmse[:J], full_fitness=ffit[:J], best=best[:F])
+    return dict(_job_results(res, J), clean_off=clean_off, T_global=G[:J].reshape(J, 4, 4), full_rmse=frmse[:J], full_fitness=ffit[:J],
+                best=best[:F])
 
 
 class MemGrid:
@@ -388,12 +402,9 @@ class MemGrid:
         self.cell = cell
         self.live = bool(live)
         self._h = C.c_void_p()
-        args = (ctx.handle, mem_pts4.data_ptr(), mem_pts4.shape[0], float(cell))
-        if self.live:
-            st = _lib.lib.ibl_memgrid_build_owned(*args, int(reserve_points), C.byref(self._h), _stream())
-        else:
-            st = _lib.lib.ibl_memgrid_build(*args, C.byref(self._h), _stream())
-        _lib.check(st, "ibl_memgrid_build_owned" if self.live else "ibl_memgrid_build")
+        st = _lib.lib.ibl_memgrid_build(ctx.handle, mem_pts4.data_ptr(), mem_pts4.shape[0], float(cell), int(self.live),
+                                        int(reserve_points) if self.live else 0, C.byref(self._h), _stream())
+        _lib.check(st, "ibl_memgrid_build")
 
     def append(self, pts4_new: torch.Tensor):
         """Merges further points (they count as the points behind all earlier ones) into a live grid: afterwards it equals the grid
@@ -437,7 +448,7 @@ def evaluate_batch(ctx: RegContext, grid: MemGrid, det_pts4: torch.Tensor, job_b
     rmse = np.zeros(J, dtype=np.float64)
     fit = np.zeros(J, dtype=np.float64)
     st = _lib.lib.ibl_evaluate_batch(ctx.handle, grid.handle, det_pts4.data_ptr(), jb.ctypes.data, je.ctypes.data, T.ctypes.data,
-                                     J, float(threshold), rmse.ctypes.data, fit.ctypes.data, _stream())
+                                     J, float(threshold), None, rmse.ctypes.data, fit.ctypes.data, _stream())
     _lib.check(st, "ibl_evaluate_batch")
     return rmse, fit
 
@@ -452,7 +463,7 @@ def evaluate_points(ctx: RegContext, grid: MemGrid, det_pts4: torch.Tensor, job_
     d2 = torch.empty(max(int((je - jb).sum()), 1), dtype=torch.float32, device=det_pts4.device)
     rmse = np.zeros(J, dtype=np.float64)
     fit = np.zeros(J, dtype=np.float64)
-    st = _lib.lib.ibl_evaluate_points(ctx.handle, grid.handle, det_pts4.data_ptr(), jb.ctypes.data, je.ctypes.data, T.ctypes.data,
-                                      J, float(threshold), d2.data_ptr(), rmse.ctypes.data, fit.ctypes.data, _stream())
-    _lib.check(st, "ibl_evaluate_points")
+    st = _lib.lib.ibl_evaluate_batch(ctx.handle, grid.handle, det_pts4.data_ptr(), jb.ctypes.data, je.ctypes.data, T.ctypes.data,
+                                     J, float(threshold), d2.data_ptr(), rmse.ctypes.data, fit.ctypes.data, _stream())
+    _lib.check(st, "ibl_evaluate_batch")
     return d2[:int((je - jb).sum())], rmse, fit

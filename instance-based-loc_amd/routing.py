@@ -10,7 +10,7 @@ Every rank localises its own frames ("home" of their jobs) and owns the clouds +
      (<= 3 x ~5 000 points x 16 B) travel to the owner, 50x less than the instance arrays (280 B per point with the cached features);
      a job whose targets span ranks runs at home, which fetches the missing instances' clouds + cached features from their owners;
   3. one point-to-point exchange moves both kinds of payload (each ordered pair of ranks: one message);
-  4. each executor registers its job list (`ibl_register_batch_ids`: a job keeps its RANSAC id, and per-instance features do not depend on
+  4. each executor registers its job list (`ibl_register_jobs` with `job_ids`: a job keeps its RANSAC id, and per-instance features do not depend on
      the batch they were computed in, so the result is bit-identical to the unsharded run);
   5. results (a few hundred bytes per job) return to the home ranks;
   6. whole-memory evaluation: the cleaned detected points and the global transforms are all-gathered, every rank measures every job

@@ -1,7 +1,7 @@
 """Drop-in for the reference's `utils/depth_utils.py` (/root/reference/utils/depth_utils.py) on the MI355X build: the same function
 names and arguments, `Cloud` records (`.points`, `.colors` as (N, 3) float64, like the Open3D clouds the reference returns) instead of
 `open3d.geometry.PointCloud`.  Unprojection, radius outlier removal and voxel down-sampling run in libibloc_hip.so
-(`ibl_unproject_masks_f64`, `ibl_radius_outlier_batch`, `ibl_voxel_downsample_batch`); pose arithmetic stays numpy / scipy like the
+(`ibl_unproject_masks`, `ibl_radius_outlier_batch`, `ibl_voxel_downsample_batch`); pose arithmetic stays numpy / scipy like the
 reference's.  Masks are read as booleans (the reference multiplies the depth image by the mask, :200-201, which is the same thing
 for the 0/1 masks SAM produces)."""
 import numpy as np

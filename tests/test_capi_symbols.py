@@ -31,6 +31,34 @@ def test_error_channel_without_gpu():
     assert st < 0 and b"null" in _lib.lib.ibl_last_error()
 
 
+def test_registration_calls_refuse_null_arguments_without_gpu():
+    """ibl_register_jobs and ibl_register_evaluate_batch with a null context, pool or params, and ibl_memgrid_build with a null context
+    and reserve_points on an immutable grid: a negative status and a message, decided before any HIP call"""
+    import numpy as np
+    from ibloc_amd import _lib
+    from ibloc_amd import registration as R
+    lib, ref = _lib.lib, ctypes.byref
+    seg = np.zeros(3, dtype=np.int32)
+    one = np.zeros(16, dtype=np.float64)
+    pool = R._PoolStruct(one.ctypes.data, seg.ctypes.data, seg.ctypes.data, None, 0)      # never dereferenced: every call below is refused
+    params = R._ParamsStruct(0.05, 1.5, 0.4, 0, 1000, 0, 3)
+    out = R._OutStruct(*([one.ctypes.data] * 7))
+    ctx = ctypes.c_void_p(1)                                                              # non-null, never dereferenced either
+    n_jobs, grid = ctypes.c_int32(0), ctypes.c_void_p()
+
+    def refused(st):
+        assert st < 0 and lib.ibl_last_error()
+
+    for c, d, m, p in [(None, ref(pool), ref(pool), ref(params)), (ctx, None, ref(pool), ref(params)), (ctx, ref(pool), None, ref(params)),
+                       (ctx, ref(pool), ref(pool), None)]:
+        refused(lib.ibl_register_jobs(c, d, m, seg.ctypes.data, seg.ctypes.data, None, 1, p, ref(out), None))
+        refused(lib.ibl_register_evaluate_batch(c, d, seg.ctypes.data, 0, seg.ctypes.data, seg.ctypes.data, seg.ctypes.data, 6, m, ctx, p,
+                                                0.05, 8, 0.02, 1, seg.ctypes.data, ref(n_jobs), ref(out), one.ctypes.data, one.ctypes.data,
+                                                one.ctypes.data, seg.ctypes.data, None))
+    refused(lib.ibl_memgrid_build(None, one.ctypes.data, 4, 0.04, 0, 1, ref(grid), None))
+    assert not grid
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     import importlib
     from ibloc_amd import _lib
@@ -51,7 +79,8 @@ def test_struct_layouts_match_the_header(tmp_path):
     from ibloc_amd import registration as R
     from ibloc_amd import vit as V
     pairs = [("ibl_vit_desc", V.VitDesc), ("ibl_vit_layer", V.VitLayer), ("ibl_vit_weights", V.VitWeights), ("ibl_linear_desc", V.LinearDesc),
-             ("ibl_dator_head_weights", D.DatorHeadWeights), ("ibl_crop_desc", pp.CropDesc), ("ibl_instance_features", R._FeatStruct)]
+             ("ibl_dator_head_weights", D.DatorHeadWeights), ("ibl_crop_desc", pp.CropDesc), ("ibl_instance_features", R._FeatStruct),
+             ("ibl_cloud_pool", R._PoolStruct), ("ibl_register_params", R._ParamsStruct), ("ibl_register_out", R._OutStruct)]
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "ibloc.h"', 'int main(void) {']
     for cname, ct in pairs:
         lines.append(f'  printf("{cname} %zu", sizeof({cname}));')

@@ -247,7 +247,7 @@ def test_pipelined_stream_equals_batch_by_batch():
 
 
 def test_sharded_evaluate_equals_whole_memory():
-    """ibl_evaluate_points against two instance-range shards of the memory, combined by the element-wise minimum (what the
+    """ibl_evaluate_batch with d2_out against two instance-range shards of the memory, combined by the element-wise minimum (what the
     all-reduce(MIN) of parallel.evaluate_sharded does across ranks), gives the whole-memory fitness exactly and its rmse to rounding"""
     from ibloc_amd.parallel import fitness_rmse_from_d2
     from ibloc_amd.registration import CloudBatch, MemGrid, RegContext, evaluate_batch, evaluate_points

@@ -1,4 +1,4 @@
-"""-m gpu: live object memory.  A memory that is appended to while resident (ibl_memgrid_build_owned / ibl_memgrid_append,
+"""-m gpu: live object memory.  A memory that is appended to while resident (ibl_memgrid_build with live = 1 / ibl_memgrid_append,
 MemoryShard(live=True).append, ObjectMemory.live_memory) holds, array for array, what a memory rebuilt from all instances holds, and
 localises to the same results bit for bit."""
 import copy

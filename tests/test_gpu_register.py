@@ -293,3 +293,20 @@ def test_ransac_survivor_list_overflow_is_redone_with_a_full_list(ctx):
         for k in ("T", "rmse", "fitness", "T_ransac", "ransac_stats"):
             assert np.array_equal(out[k][j], one[k][0]), (j, k)
         assert np.allclose(out["T"][j], np.eye(4), atol=1e-6) and out["fitness"][j] > 0.999
+
+
+def test_job_id_base_is_the_default_of_job_ids(ctx):
+    """ibl_register_jobs draws job j's RANSAC hypotheses with the id job_ids[j], or job_id_base + j without job_ids: the same four jobs (the
+    clouds of the test above, registered onto copies of themselves) with job_id_base = 7 and with job_ids = 7 + arange(4) are one and
+    the same computation, so every output agrees bit for bit"""
+    from ibloc_amd.registration import CloudBatch, register_batch
+    w = SynthWorld(4, pts_per_object=1500, E=1, D=8, seed=17, spacing=3.0)
+    ints = [ro.intensity(c) for c in w.colors]
+    det = CloudBatch.from_numpy(w.points, ints)
+    mem = CloudBatch.from_numpy(w.points, ints)
+    js = [[j, -1, -1] for j in range(4)]
+    by_base = register_batch(ctx, det, mem, js, js, 0.05, 1.5, 1.5, seed=5, job_id_base=7)
+    by_ids = register_batch(ctx, det, mem, js, js, 0.05, 1.5, 1.5, seed=5, job_ids=7 + np.arange(4, dtype=np.uint32))
+    for k in ("T", "rmse", "fitness", "means", "T_ransac", "ransac_stats"):
+        assert np.array_equal(by_base[k], by_ids[k]), k
+    assert by_base["ransac_stats"][:, 0].min() > 0          # RANSAC ran: the ids were used

@@ -135,7 +135,7 @@ rng = np.random.default_rng(9)                       # same data on every rank
 M, sizes, thr = 11, [400, 250, 0, 333], 0.05
 mem = [rng.uniform(-1, 1, size=(300, 3)) for _ in range(M)]
 det = rng.uniform(-1, 1, size=(sum(sizes), 3))
-def d2_against(points):                              # what ibl_evaluate_points returns for a shard: nearest squared distance within thr
+def d2_against(points):                              # what ibl_evaluate_batch writes to d2_out for a shard: nearest squared distance within thr
     d = ((det[:, None, :].astype(np.float32) - points[None, :, :].astype(np.float32)) ** 2).sum(-1).min(axis=1)
     d[d >= np.float32(thr * thr)] = np.inf
     return torch.from_numpy(d.astype(np.float32))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times stage B of one bench step (outlier removal, detection features, register, evaluate) on synthetic frames, without the encoder:
-the detections' embeddings come from the generator.  IBL_TIMING=1 prints the host-synchronised phases of ibl_register_batch_cached;
+the detections' embeddings come from the generator.  IBL_TIMING=1 prints the host-synchronised phases of ibl_register_jobs;
 IBLOC_LIB=path selects a lab build; IBL_COMPACT=1 keeps the memory's instance features without their fp16 operand rows.  usage: perf_register.py [frames] [memory]"""
 import os
 import sys
