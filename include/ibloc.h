@@ -54,7 +54,8 @@ int ibl_prof_read(int id, double* ms, double* units, int64_t* launches);
 #define IBL_VIT_LAYERSCALE 1      /* DINOv2 LayerScale (per-layer ls1/ls2 non-NULL)                */
 #define IBL_VIT_PRE_LN 2          /* CLIP ln_pre on the embedded tokens                            */
 #define IBL_VIT_FINAL_LN 4        /* final LayerNorm (DINOv2 / ViT layernorm, CLIP ln_post)        */
-#define IBL_VIT_QUICK_GELU 8      /* x*sigmoid(1.702x) (OpenAI CLIP); laion2b ViT-B-32 uses GELU   */
+#define IBL_VIT_QUICK_GELU 8      /* fc1 activation x*sigmoid(1.702x) (OpenAI CLIP, open_clip *-quickgelu, transformers' default
+                                     CLIPVisionConfig) in place of erf GELU (laion2b ViT-B-32)     */
 #define IBL_VIT_PROJ 16           /* CLS -> out_dim projection (CLIP visual.proj)                  */
 #define IBL_VIT_OUT_ALL_TOKENS 32 /* return every token (DATOR/TransReID local_feature=True)       */
 #define IBL_VIT_ACT_TERMS2 64     /* some block has o_terms / fc2_terms = 2: attention output / hidden layer as rows of 2 terms  */
@@ -192,11 +193,16 @@ int ibl_linear_f16(const void* x, int64_t ldx, const void* W, int64_t ldw, const
  *                (out + bias) / alpha; selected here and nowhere else ($IBL_GEMM_RESID_PRE concerns ibl_vit_forward and ibl_linear_f16)
  *            IBL_LINEAR_GELU_F16_X2 / _X3: out fp16 [rows][ldo] of 2 / 3 column blocks of n_out: [h | h / S], [h | (value - h) * S | h / S]
  *                with h = gelu(y + bias) rounded to fp16 from the fp32 `value` (S = IBL_VIT_SPLIT_SCALE): ldo >= 2 / 3 * n_out
+ *   activation is read by IBL_LINEAR_GELU_F16 / _X2 / _X3 only: IBL_ACT_GELU_ERF (0, what a zeroed descriptor asks for) is the erf form
+ *   above, IBL_ACT_QUICK_GELU gelu(v) = v * sigmoid(1.702 v) (what IBL_VIT_QUICK_GELU runs in the encoder); the rest of the epilogue is the same
  *   scale is read by IBL_LINEAR_RESID_F32 only; alpha by IBL_LINEAR_RESID_PRE_F32 and by the accumulate form of the patch scatter, where it
  *   must be a positive power of two (the kernel divides and multiplies by it and both must be exact)
  *   rows 0 returns IBL_OK without a launch.  A null x / W / out, n_out % 128, n_in % 64, a stride shorter than its row or not a
  *   multiple of 8 elements, an alpha that is no positive power of two where it is read, patches_per_crop <= 0, tokens_per_crop <=
- *   patches_per_crop, part of a crop, pos NULL without accumulate and an unknown epilogue are refused with a status before any launch. */
+ *   patches_per_crop, part of a crop, pos NULL without accumulate, an unknown epilogue, an activation other than 0 / 1 and a non-zero
+ *   activation with an epilogue that has none are refused with a status before any launch.  The field lies in what was the tail padding
+ *   of the struct (its size stays 112): zero the descriptor before filling it, a garbage tail is refused, not obeyed. */
+enum { IBL_ACT_GELU_ERF = 0, IBL_ACT_QUICK_GELU = 1 };
 typedef struct {
     const void* x;  int64_t ldx;       /* fp16 [rows][ldx]                                              */
     const void* W;  int64_t ldw;       /* fp16 [n_out][ldw]                                             */
@@ -209,6 +215,7 @@ typedef struct {
     int32_t accumulate;                /* IBL_LINEAR_PATCH_F32: 0 or 1                                  */
     int32_t tokens_per_crop, patches_per_crop;
     float alpha;
+    int32_t activation;                /* IBL_ACT_* (IBL_LINEAR_GELU_F16 / _X2 / _X3), 0 elsewhere       */
 } ibl_linear_desc;
 int ibl_linear_f16_ex(const ibl_linear_desc* desc, void* stream);
 

@@ -56,7 +56,10 @@ enum { EPI_BIAS_H16 = 0, EPI_BIAS_GELU_H16 = 1, EPI_RESID_F32 = 2, EPI_PATCH_F32
        EPI_RESID_PRE_F32 = 5,
        // EPI_BIAS_GELU_H16 writing K-extended operand rows for the next GEMM (round 4; ldo = terms * N):
        //   KX2: [h | h / S]  (fc2 weights in two terms)     KX3: [h | (value - h) * S | h / S]  (+ the hidden layer's second term)
-       EPI_BIAS_GELU_H16KX2 = 6, EPI_BIAS_GELU_H16KX3 = 7 };
+       EPI_BIAS_GELU_H16KX2 = 6, EPI_BIAS_GELU_H16KX3 = 7,
+       // internal (not in ibloc.h's enum; reached through ibl_linear_desc.activation and IBL_VIT_QUICK_GELU): epilogues 1, 6 and 7 with
+       // QuickGELU, v * sigmoid(1.702 v), in place of the erf form -- everything after the activation is the same code
+       EPI_BIAS_QGELU_H16 = 8, EPI_BIAS_QGELU_H16KX2 = 9, EPI_BIAS_QGELU_H16KX3 = 10 };
 
 struct GemmEpi {
     const float* bias;      // [N] or null
@@ -121,6 +124,21 @@ __device__ __forceinline__ f32x2 gelu_erf2(f32x2 v) {
     return (z * u) * 0.70710678118654752f + v * 0.5f;
 }
 
+// QuickGELU (OpenAI CLIP), v * sigmoid(1.702 v) = v * rcp(1 + exp2(c v)) with c = -1.702 log2(e): two packed operations and an exp2
+// and a rcp per element.  v << 0: exp2 overflows to +inf, rcp gives 0 and the result is -0 (the true value lies below the fp16
+// subnormals from v = -13 on); v >> 0: the result is v.  r is in [0, 1] and v finite, so no finite v gives a NaN.
+__device__ __forceinline__ f32x2 quick_gelu2(f32x2 v) {
+    const f32x2 a = v * -2.4554669595930157f;
+    f32x2 e;
+    e.x = __builtin_amdgcn_exp2f(a.x);
+    e.y = __builtin_amdgcn_exp2f(a.y);
+    const f32x2 d = e + 1.0f;
+    f32x2 r;
+    r.x = __builtin_amdgcn_rcpf(d.x);
+    r.y = __builtin_amdgcn_rcpf(d.y);
+    return v * r;
+}
+
 #ifdef IBL_GEMM_STAMPS     // lab builds only (tools/perf_gemm.py --stamps): phase clocks of every tile a (persistent) block walks
 // [block < 512][tile iteration < 16][4]: 0 = tile loop top, 1 = first stage landed (after the barrier), 2 = K loop done, 3 = epilogue issued
 __device__ long long ibl_gemm_stamps[512 * 16 * 4];
@@ -167,8 +185,10 @@ __global__ __launch_bounds__(T256 ? 512 : 256, T256 ? 1 : 2) void ibl_gemm_f16_t
     constexpr bool PRE = EPI == EPI_RESID_PRE_F32;
     // fp16 epilogues: MFMA row 4 fg + r of n-tile j is weight row 32 (j / 2) + 8 fg + 4 (j % 2) + r: a lane owns 8 consecutive
     // columns (one 16-byte store) of n-tile pair j / 2 and the four lane groups cover 64 contiguous bytes of the row
-    constexpr int GT = EPI == EPI_BIAS_GELU_H16KX3 ? 3 : (EPI == EPI_BIAS_GELU_H16KX2 ? 2 : 1);     // column blocks the fp16 epilogue writes
-    constexpr bool GELU = EPI == EPI_BIAS_GELU_H16 || GT > 1;
+    constexpr bool QGELU = EPI == EPI_BIAS_QGELU_H16 || EPI == EPI_BIAS_QGELU_H16KX2 || EPI == EPI_BIAS_QGELU_H16KX3;
+    constexpr int GT = (EPI == EPI_BIAS_GELU_H16KX3 || EPI == EPI_BIAS_QGELU_H16KX3) ? 3
+                       : ((EPI == EPI_BIAS_GELU_H16KX2 || EPI == EPI_BIAS_QGELU_H16KX2) ? 2 : 1);     // column blocks the fp16 epilogue writes
+    constexpr bool GELU = EPI == EPI_BIAS_GELU_H16 || GT > 1 || QGELU;
     constexpr bool PAIR = EPI == EPI_BIAS_H16 || GELU;
     constexpr int PAIR_STORES = GT * 2 * MI;          // stores per lane of a full tile's fp16 epilogue
 #define KEYW(r) (NAT ? key_act(r) : (PAIR ? key_pair(r) : key_w(r)))
@@ -614,7 +634,7 @@ __global__ __launch_bounds__(T256 ? 512 : 256, T256 ? 1 : 2) void ibl_gemm_f16_t
             _Pragma("unroll") for (int t = 0; t < 8; t += 2) {                                                                      \
                 f32x2 x = {acc[I][2 * j2 + (t >> 2)][t & 3], acc[I][2 * j2 + (t >> 2)][(t & 3) + 1]};                               \
                 x += f32x2{bb[j2][t], bb[j2][t + 1]};                                                                               \
-                if (GELU) x = gelu_erf2(x);                                                                                         \
+                if (GELU) x = QGELU ? quick_gelu2(x) : gelu_erf2(x);                                                                \
                 v[t] = x.x; v[t + 1] = x.y;                                                                                         \
             }                                                                                                                       \
             const uint4 hi4 = make_uint4(f2h_pk(v[0], v[1]), f2h_pk(v[2], v[3]), f2h_pk(v[4], v[5]), f2h_pk(v[6], v[7]));           \
@@ -1054,6 +1074,7 @@ static_assert(IBL_LINEAR_F16 == EPI_BIAS_H16 && IBL_LINEAR_GELU_F16 == EPI_BIAS_
                   IBL_LINEAR_PATCH_F32 == EPI_PATCH_F32 && IBL_LINEAR_F32 == EPI_BIAS_F32 && IBL_LINEAR_RESID_PRE_F32 == EPI_RESID_PRE_F32 &&
                   IBL_LINEAR_GELU_F16_X2 == EPI_BIAS_GELU_H16KX2 && IBL_LINEAR_GELU_F16_X3 == EPI_BIAS_GELU_H16KX3,
               "the header's epilogue numbers are the kernel's");
+static_assert(sizeof(ibl_linear_desc) == 112, "activation fills the tail padding of ibl_linear_desc: its size is part of the ABI");
 
 // a finite, normal, positive power of two: the factor EPI_RESID_PRE_F32 divides by and multiplies with must do both exactly
 static bool pow2_positive(float a) {
@@ -1070,6 +1091,10 @@ extern "C" int ibl_linear_f16_ex(const ibl_linear_desc* d, void* stream) {
     if (n_out <= 0 || n_in <= 0 || n_out % 128 != 0 || n_in % GBK != 0)
         return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: n_out (%d) must be a positive multiple of 128 and n_in (%d) of 64", n_out, n_in);
     if (epi < EPI_BIAS_H16 || epi > EPI_BIAS_GELU_H16KX3) return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: unknown epilogue %d", epi);
+    const bool gelu = epi == EPI_BIAS_GELU_H16 || epi == EPI_BIAS_GELU_H16KX2 || epi == EPI_BIAS_GELU_H16KX3;
+    if (d->activation != IBL_ACT_GELU_ERF && !(gelu && d->activation == IBL_ACT_QUICK_GELU))
+        return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: activation %d with epilogue %d (0, or 1 with a GELU epilogue)", d->activation, epi);
+    const bool quick = d->activation == IBL_ACT_QUICK_GELU;
     const int terms = epi == EPI_BIAS_GELU_H16KX3 ? 3 : (epi == EPI_BIAS_GELU_H16KX2 ? 2 : 1);
     if ((d->ldx & 7) || (d->ldw & 7) || (d->ldo & 7) || d->ldx < n_in || d->ldw < n_in || d->ldo < (int64_t)terms * n_out)
         return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: row strides must be >= the row length (%d in, %d out) and multiples of 8 elements",
@@ -1100,13 +1125,19 @@ extern "C" int ibl_linear_f16_ex(const ibl_linear_desc* d, void* stream) {
     const int rows = (int)d->rows;
     switch (epi) {
         case EPI_BIAS_H16: return launch_gemm<EPI_BIAS_H16>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
-        case EPI_BIAS_GELU_H16: return launch_gemm<EPI_BIAS_GELU_H16>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
+        case EPI_BIAS_GELU_H16:
+            return quick ? launch_gemm<EPI_BIAS_QGELU_H16>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s)
+                         : launch_gemm<EPI_BIAS_GELU_H16>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
         case EPI_RESID_F32: return launch_gemm<EPI_RESID_F32>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
         case EPI_PATCH_F32: return launch_gemm<EPI_PATCH_F32>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
         case EPI_BIAS_F32: return launch_gemm<EPI_BIAS_F32>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
         case EPI_RESID_PRE_F32: return launch_gemm<EPI_RESID_PRE_F32>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
-        case EPI_BIAS_GELU_H16KX2: return launch_gemm<EPI_BIAS_GELU_H16KX2>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
-        default: return launch_gemm<EPI_BIAS_GELU_H16KX3>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
+        case EPI_BIAS_GELU_H16KX2:
+            return quick ? launch_gemm<EPI_BIAS_QGELU_H16KX2>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s)
+                         : launch_gemm<EPI_BIAS_GELU_H16KX2>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
+        default:
+            return quick ? launch_gemm<EPI_BIAS_QGELU_H16KX3>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s)
+                         : launch_gemm<EPI_BIAS_GELU_H16KX3>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
     }
 }
 
@@ -1323,10 +1354,12 @@ extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, 
         {
             GemmEpi e{};
             e.bias = L->b_fc1; e.out = hid; e.ldo = (int64_t)f2t * d->mlp_dim; e.algo_k = D;
-            if (d->flags & IBL_VIT_QUICK_GELU)
-                return ibl_set_error(IBL_ERR_UNSUPPORTED, "ibl_vit_forward: QuickGELU not built");
             const u16* w1 = reinterpret_cast<const u16*>(ft > 1 ? L->w_fc1_x : L->w_fc1);
-            if (f2t == 3) st = launch_gemm<EPI_BIAS_GELU_H16KX3>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
+            if (d->flags & IBL_VIT_QUICK_GELU) {
+                if (f2t == 3) st = launch_gemm<EPI_BIAS_QGELU_H16KX3>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
+                else if (f2t == 2) st = launch_gemm<EPI_BIAS_QGELU_H16KX2>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
+                else st = launch_gemm<EPI_BIAS_QGELU_H16>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
+            } else if (f2t == 3) st = launch_gemm<EPI_BIAS_GELU_H16KX3>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
             else if (f2t == 2) st = launch_gemm<EPI_BIAS_GELU_H16KX2>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
             else st = launch_gemm<EPI_BIAS_GELU_H16>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
             if (st) return st;

@@ -93,9 +93,45 @@ def open_clip_visual_to_weights(sd: dict, depth: int) -> dict:
     return w
 
 
+def hf_clip_to_weights(sd: dict, depth: int) -> dict:
+    """transformers `CLIPVisionModelWithProjection.state_dict()` or `CLIPModel.state_dict()` (the text tower's keys are ignored) -> weight
+    dict.  `pre_layrnorm` is transformers' own spelling."""
+    g = lambda k: np.asarray(sd[k].float().cpu() if hasattr(sd[k], "float") else sd[k], dtype=np.float32)
+    v = "vision_model."
+    D = g(v + "embeddings.class_embedding").shape[0]
+    w = {"patch.w": g(v + "embeddings.patch_embedding.weight"), "patch.b": np.zeros(D, np.float32),
+         "cls": g(v + "embeddings.class_embedding"), "pos": g(v + "embeddings.position_embedding.weight"),
+         "ln_pre.g": g(v + "pre_layrnorm.weight"), "ln_pre.b": g(v + "pre_layrnorm.bias"),
+         "ln_f.g": g(v + "post_layernorm.weight"), "ln_f.b": g(v + "post_layernorm.bias"), "proj.w": g("visual_projection.weight")}
+    for l in range(depth):
+        p, q = v + f"encoder.layers.{l}.", f"l{l}."
+        w[q + "ln1.g"], w[q + "ln1.b"] = g(p + "layer_norm1.weight"), g(p + "layer_norm1.bias")
+        w[q + "ln2.g"], w[q + "ln2.b"] = g(p + "layer_norm2.weight"), g(p + "layer_norm2.bias")
+        for hf, mine in (("q_proj", "q"), ("k_proj", "k"), ("v_proj", "v"), ("out_proj", "o")):
+            w[q + mine + ".w"], w[q + mine + ".b"] = g(p + f"self_attn.{hf}.weight"), g(p + f"self_attn.{hf}.bias")
+        w[q + "fc1.w"], w[q + "fc1.b"] = g(p + "mlp.fc1.weight"), g(p + "mlp.fc1.bias")
+        w[q + "fc2.w"], w[q + "fc2.b"] = g(p + "mlp.fc2.weight"), g(p + "mlp.fc2.bias")
+    return w
+
+
+def clip_converter(state_dict):
+    """the converter of a CLIP vision state dict, from its key layout: `vision_model.*` is transformers', `conv1.weight` open_clip's
+    `model.visual` (OpenAI's released checkpoints use the same names)"""
+    if any(k.startswith("vision_model.") for k in state_dict):
+        return hf_clip_to_weights
+    if "conv1.weight" in state_dict:
+        return open_clip_visual_to_weights
+    raise KeyError("neither a transformers CLIP state dict (vision_model.*) nor an open_clip / OpenAI visual one (conv1.weight)")
+
+
 def load_encoder(kind: str, state_dict, device="cuda", cfg: V.VitConfig = None):
     """Build + register the encoder of `kind` ("dino" | "vit" | "clip" | "dator") from a checkpoint state dict.  cfg: another
     architecture / position-embedding rule than the checkpoint the reference loads (default: V.CONFIGS of the kind).
+
+    "clip": the state dict may be open_clip's / OpenAI's `model.visual.state_dict()` or transformers' CLIPVisionModelWithProjection /
+    CLIPModel one; the key layout picks the converter.  A state dict does not carry the activation: it is `cfg.quick_gelu`, the caller's
+    -- the default cfg (clip_b32, laion2b) runs erf GELU; OpenAI's checkpoints, open_clip's *-quickgelu models and transformers models
+    with hidden_act "quick_gelu" need V.CONFIGS["clip_b32_openai"] / "clip_b16_openai" / "clip_l14_openai".
 
     "dator": `state_dict` is a `build_FourDNet` checkpoint as the reference's `load_model('.../dator_best_tum.pth')` reads it
     (utils/embeddings.py:101-103, make_model.py:620-626) -- the dict itself or the path of the `.pth` file (loaded with
@@ -110,7 +146,7 @@ def load_encoder(kind: str, state_dict, device="cuda", cfg: V.VitConfig = None):
         set_encoder(kind, enc)
         return enc
     cfg = cfg or V.CONFIGS[_KIND_TO_CONFIG[kind]]
-    conv = {"dino": hf_dinov2_to_weights, "vit": hf_vit_to_weights, "clip": open_clip_visual_to_weights}[kind]
+    conv = clip_converter(state_dict) if kind == "clip" else {"dino": hf_dinov2_to_weights, "vit": hf_vit_to_weights}[kind]
     enc = V.VitEncoder(cfg, conv(state_dict, cfg.depth), device=device)
     set_encoder(kind, enc)
     return enc

@@ -58,7 +58,14 @@ SPLIT_SCALE = 64.0          # IBL_VIT_SPLIT_SCALE (include/ibloc.h)
 DEFAULT_PRECISION = "p2;0:3232;1:2211;2:2111"
 # per-model defaults where they differ: CLIP ViT-B/32 runs 50 tokens per crop (4 ms per 224 crops), so two-term weights in every block cost
 # 2 ms and take its worst crop of 896 from 9.7e-4 -- too close to SURVEY 8d's 1e-3 gate -- to 8.1e-4 (mean 7.1e-4 -> 6.1e-4)
-MODEL_PRECISION = {"clip_b32": "p2;*:2222;0:3232"}
+MODEL_PRECISION = {"clip_b32": "p2;*:2222;0:3232",
+                   # the OpenAI (QuickGELU) CLIP models on 896 / 896 / 224 u8 crops, mean / max (DESIGN (c) has every plan that was measured).  B/32 misses
+                   # the gate under the default plan as clip_b32 does (7.0e-4 / 1.005e-3); block 1's weights and block 2's attention weights in two terms
+                   # bring it to 6.9e-4 / 8.9e-4 for 4.27 instead of 3.90 ms per 224 crops (clip_b32's plan: 6.0e-4 / 8.4e-4 but 5.74 ms).  B/16 meets it
+                   # under the default (6.6e-4 / 7.7e-4): no entry.  L/14's 24 blocks spread the error over more of the depth (default 8.9e-4 / 1.04e-3):
+                   # two-term weights in blocks 0-3 give 8.1e-4 / 9.2e-4 for 49.8 instead of 46.5 ms
+                   "clip_b32_openai": "p2;0:3232;1:2222;2:2211",
+                   "clip_l14_openai": "p2;0:3232;1:2222;2:2222;3:2222;4:2211"}
 
 
 def parse_precision(spec):
@@ -119,6 +126,7 @@ class VitConfig:
     out_all_tokens: bool = False
     recipe: str = "dinov2"
     pos_interp: str = "hf-4.44"    # how stored position embeddings are resampled to the run grid
+    quick_gelu: bool = False       # fc1 activation x * sigmoid(1.702 x) (OpenAI CLIP) instead of erf GELU: IBL_VIT_QUICK_GELU
 
     @property
     def grid(self):
@@ -153,10 +161,21 @@ CONFIGS = {
     # open_clip ViT-B-32 laion2b_s34b_b79k (utils/embeddings.py:13-16): ln_pre, ln_post, 512-d projection
     "clip_b32": VitConfig("clip_b32", 768, 12, 12, 3072, 32, 224, 224, (7, 7), pre_ln=True, proj_dim=512,
                           ln_eps=1e-5, recipe="clip"),
+    # OpenAI CLIP ViT-B/32, ViT-B/16 and ViT-L/14 at 224 px (also open_clip's *-quickgelu models and what transformers builds from a
+    # default CLIPVisionConfig): the architecture of clip_b32 with QuickGELU.  A state dict does not say which activation its model
+    # was trained with -- the configuration does
+    "clip_b32_openai": VitConfig("clip_b32_openai", 768, 12, 12, 3072, 32, 224, 224, (7, 7), pre_ln=True, proj_dim=512,
+                                 ln_eps=1e-5, recipe="clip", quick_gelu=True),
+    "clip_b16_openai": VitConfig("clip_b16_openai", 768, 12, 12, 3072, 16, 224, 224, (14, 14), pre_ln=True, proj_dim=512,
+                                 ln_eps=1e-5, recipe="clip", quick_gelu=True),
+    "clip_l14_openai": VitConfig("clip_l14_openai", 1024, 24, 16, 4096, 14, 224, 224, (16, 16), pre_ln=True, proj_dim=768,
+                                 ln_eps=1e-5, recipe="clip", quick_gelu=True),
     # tiny configurations used by the parity tests
     "tiny_dino": VitConfig("tiny_dino", 128, 2, 2, 256, 14, 224, 224, (37, 37), layerscale=True, recipe="dinov2"),
     "tiny_clip": VitConfig("tiny_clip", 128, 2, 2, 256, 32, 224, 224, (7, 7), pre_ln=True, proj_dim=128,
                            ln_eps=1e-5, recipe="clip"),
+    "tiny_clip_q": VitConfig("tiny_clip_q", 128, 2, 2, 256, 32, 224, 224, (7, 7), pre_ln=True, proj_dim=128,
+                             ln_eps=1e-5, recipe="clip", quick_gelu=True),
 }
 
 
@@ -349,6 +368,7 @@ class VitEncoder:
         flags |= FLAG_PRE_LN if cfg.pre_ln else 0
         flags |= FLAG_FINAL_LN if cfg.final_ln else 0
         flags |= FLAG_PROJ if cfg.proj_dim else 0
+        flags |= FLAG_QUICK_GELU if cfg.quick_gelu else 0
         flags |= FLAG_OUT_ALL_TOKENS if cfg.out_all_tokens else 0
         flags |= {1: 0, 2: FLAG_ACT_TERMS2, 3: FLAG_ACT_TERMS3}[getattr(self, "_act_terms", 1)]
         nrun = cfg.depth if cfg.n_blocks_run < 0 else cfg.n_blocks_run
@@ -473,7 +493,10 @@ class LinearDesc(C.Structure):              # ibl_linear_desc (include/ibloc.h)
     _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("W", C.c_void_p), ("ldw", C.c_int64), ("bias", C.c_void_p),
                 ("scale", C.c_void_p), ("pos", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int64), ("rows", C.c_int64),
                 ("n_out", C.c_int32), ("n_in", C.c_int32), ("epilogue", C.c_int32), ("accumulate", C.c_int32),
-                ("tokens_per_crop", C.c_int32), ("patches_per_crop", C.c_int32), ("alpha", C.c_float)]
+                ("tokens_per_crop", C.c_int32), ("patches_per_crop", C.c_int32), ("alpha", C.c_float), ("activation", C.c_int32)]
+
+
+ACT_GELU_ERF, ACT_QUICK_GELU = 0, 1         # IBL_ACT_*: what LINEAR_GELU_F16 / _X2 / _X3 apply
 
 
 def linear_f16(x: torch.Tensor, W: torch.Tensor, bias=None, epilogue=LINEAR_F16, out=None, scale=None) -> torch.Tensor:
@@ -502,9 +525,9 @@ def linear_f16(x: torch.Tensor, W: torch.Tensor, bias=None, epilogue=LINEAR_F16,
 
 
 def linear_f16_ex(x: torch.Tensor, W: torch.Tensor, out: torch.Tensor, epilogue, bias=None, scale=None, pos=None, alpha=1.0,
-                  accumulate=False, tokens_per_crop=0, patches_per_crop=0) -> torch.Tensor:
+                  accumulate=False, tokens_per_crop=0, patches_per_crop=0, activation=ACT_GELU_ERF) -> torch.Tensor:
     """`ibl_linear_f16_ex`: the encoder's GEMM with any of its eight epilogues, written into `out` (include/ibloc.h says what each one
-    computes).  x (rows, n_in) fp16, W (n_out, n_in) fp16, `out` fp16 (rows, terms * n_out) for LINEAR_F16 / _GELU_F16 / _GELU_F16_X2 /
+    computes; `activation` = ACT_QUICK_GELU makes the three GELU epilogues apply x * sigmoid(1.702 x)).  x (rows, n_in) fp16, W (n_out, n_in) fp16, `out` fp16 (rows, terms * n_out) for LINEAR_F16 / _GELU_F16 / _GELU_F16_X2 /
     _X3, else fp32 (rows, n_out) -- for LINEAR_PATCH_F32 fp32 (rows / patches_per_crop * tokens_per_crop, n_out), the token rows.  All
     three may be row-strided views.  Only the dtypes and the devices are checked here: what the library cannot run it refuses (IblError)."""
     for t in (x, W, out):
@@ -516,7 +539,7 @@ def linear_f16_ex(x: torch.Tensor, W: torch.Tensor, out: torch.Tensor, epilogue,
     d = LinearDesc(x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), bias.data_ptr() if bias is not None else None,
                    scale.data_ptr() if scale is not None else None, pos.data_ptr() if pos is not None else None, out.data_ptr(),
                    out.stride(0), x.shape[0], W.shape[0], x.shape[1], int(epilogue), int(accumulate), int(tokens_per_crop),
-                   int(patches_per_crop), float(alpha))
+                   int(patches_per_crop), float(alpha), int(activation))
     _lib.check(_lib.lib.ibl_linear_f16_ex(C.byref(d), torch.cuda.current_stream().cuda_stream), "ibl_linear_f16_ex")
     return out
 
