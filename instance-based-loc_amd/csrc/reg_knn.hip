@@ -961,6 +961,42 @@ struct ListNormalConsumer {
     }
 };
 
+// Symmetric 3x3 solve, LDL^T with diagonal pivoting (Open3D solves the gradient system with Eigen's ldlt()): at each step the largest
+// remaining diagonal entry is moved to the front by a symmetric exchange, then eliminated.  x stays zero when a pivot is zero or not
+// finite (a singular system: coincident or collinear neighbours).  Cramer's rule, which stood here, lost up to 7e-4 of max|g| to
+// cancelling cofactors on dense, small neighbourhoods.  Scalars only (no indexed arrays: nothing goes to scratch); the same statements
+// as solve3_sym of oracle/oracle_reg.c.
+__device__ __forceinline__ void swap_d(double& u, double& v) { const double t = u; u = v; v = t; }
+__device__ inline bool solve3_sym(const double M[3][3], const double B[3], double x[3]) {
+    double a00 = M[0][0], a01 = M[0][1], a02 = M[0][2], a11 = M[1][1], a12 = M[1][2], a22 = M[2][2];
+    double b0 = B[0], b1 = B[1], b2 = B[2];
+    x[0] = x[1] = x[2] = 0.0;
+    int first = 0;                                   // the index exchanged with 0
+    if (fabs(a11) > fabs(a00) && fabs(a11) >= fabs(a22)) first = 1;
+    else if (fabs(a22) > fabs(a00)) first = 2;
+    if (first == 1) { swap_d(a00, a11); swap_d(a02, a12); swap_d(b0, b1); }
+    if (first == 2) { swap_d(a00, a22); swap_d(a01, a12); swap_d(b0, b2); }
+    if (a00 == 0.0 || !isfinite(a00)) return false;
+    const double l1 = a01 / a00, l2 = a02 / a00;
+    a11 -= l1 * a01; a12 -= l1 * a02; a22 -= l2 * a02;
+    b1 -= l1 * b0; b2 -= l2 * b0;
+    const bool second = fabs(a22) > fabs(a11);      // 1 and 2 exchanged
+    if (second) { swap_d(a11, a22); swap_d(a01, a02); swap_d(b1, b2); }
+    if (a11 == 0.0 || !isfinite(a11)) return false;
+    const double l = a12 / a11;
+    a22 -= l * a12;
+    b2 -= l * b1;
+    if (a22 == 0.0 || !isfinite(a22)) return false;
+    double x2 = b2 / a22;
+    double x1 = (b1 - a12 * x2) / a11;
+    double x0 = (b0 - a01 * x1 - a02 * x2) / a00;
+    if (second) swap_d(x1, x2);
+    if (first == 1) swap_d(x0, x1);
+    if (first == 2) swap_d(x0, x2);
+    x[0] = x0; x[1] = x1; x[2] = x2;
+    return true;
+}
+
 template <class Acc>
 struct GradConsumer {
     static constexpr bool WANTS_INNER = false;
@@ -1004,16 +1040,7 @@ struct GradConsumer {
                 double M[3][3] = {{a[0], a[1], a[2]}, {a[1], a[3], a[4]}, {a[2], a[4], a[5]}};
                 for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) M[r][c] += wgt * nt[r] * wgt * nt[c];
                 const double B[3] = {a[6], a[7], a[8]};
-                const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
-                                   M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-                if (det != 0.0 && isfinite(det)) {
-                    gx[0] = (B[0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (B[1] * M[2][2] - M[1][2] * B[2]) +
-                             M[0][2] * (B[1] * M[2][1] - M[1][1] * B[2])) / det;
-                    gx[1] = (M[0][0] * (B[1] * M[2][2] - M[1][2] * B[2]) - B[0] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
-                             M[0][2] * (M[1][0] * B[2] - B[1] * M[2][0])) / det;
-                    gx[2] = (M[0][0] * (M[1][1] * B[2] - B[1] * M[2][1]) - M[0][1] * (M[1][0] * B[2] - B[1] * M[2][0]) +
-                             B[0] * (M[1][0] * M[2][1] - M[1][1] * M[2][0])) / det;
-                }
+                solve3_sym(M, B, gx);
             }
             grad[qi] = make_float4((float)gx[0], (float)gx[1], (float)gx[2], 0.0f);
         }

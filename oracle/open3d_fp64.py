@@ -1,8 +1,8 @@
 """ORACLE (test infrastructure; never imported by the product path).
 
 An INDEPENDENT fp64 restatement of the Open3D 0.17.0 stages the reference calls around its registration --
-`remove_radius_outlier` (object_memory/object_memory.py:994-995), `estimate_normals` (utils/fpfh_register.py:91-92), the colour
-gradients and one Gauss-Newton step of `registration_colored_icp` (utils/fpfh_register.py:132-135) and `evaluate_registration`
+`remove_radius_outlier` (object_memory/object_memory.py:994-995), `estimate_normals` and `compute_fpfh_feature`
+(utils/fpfh_register.py:91-97), the colour gradients and one Gauss-Newton step of `registration_colored_icp` (utils/fpfh_register.py:132-135) and `evaluate_registration`
 (utils/fpfh_register.py:146-148) -- written on scipy's cKDTree and numpy only.  It shares no code and none of the conventions of
 oracle/oracle_reg.c and the device (those work on fp32 coordinates with an fp32 fmaf distance, a uniform grid, fixed summation orders
 and a fast analytic eigen solver): here the coordinates, the distances and every reduction are float64, neighbours come from a kd-tree,
@@ -87,6 +87,68 @@ def color_gradients(points, normals_, intensity, radius, max_nn=30):
         A = np.concatenate([proj - p[i], (nn - 1) * nrm[i][None, :]], axis=0)
         b = np.concatenate([it[idx[i, 1:nn]] - it[i], [0.0]])
         out[i] = np.linalg.lstsq(A, b, rcond=None)[0]
+    return out
+
+
+def _pair_features(p1, n1, p2, n2):
+    """ComputePairFeatures of `compute_fpfh_feature` for arrays of pairs (..., 3): the Darboux frame at the point whose normal makes the
+    smaller angle with the connecting line -> (atan2 angle, v . n_other, n_first . d / |d|), all zero for coincident points or a normal
+    along the line"""
+    d = p2 - p1
+    dist = np.sqrt(np.sum(d * d, axis=-1))
+    safe = np.where(dist > 0, dist, 1.0)
+    a1 = np.sum(n1 * d, axis=-1) / safe
+    a2 = np.sum(n2 * d, axis=-1) / safe
+    swap = np.arccos(np.minimum(np.abs(a1), 1.0)) > np.arccos(np.minimum(np.abs(a2), 1.0))
+    na = np.where(swap[..., None], n2, n1)
+    nb = np.where(swap[..., None], n1, n2)
+    dd = np.where(swap[..., None], -d, d)
+    f2 = np.where(swap, -a2, a1)
+    v = np.cross(dd, na)
+    vn = np.sqrt(np.sum(v * v, axis=-1))
+    ok = (dist > 0) & (vn > 0)
+    v = v / np.where(vn > 0, vn, 1.0)[..., None]
+    w = np.cross(na, v)
+    f1 = np.sum(v * nb, axis=-1)
+    f0 = np.arctan2(np.sum(w * nb, axis=-1), np.sum(na * nb, axis=-1))
+    z = np.zeros_like(f0)
+    return np.where(ok, f0, z), np.where(ok, f1, z), np.where(ok, f2, z)
+
+
+def fpfh(points, normals_, radius, max_nn=100):
+    """compute_fpfh_feature(KDTreeSearchParamHybrid(radius, max_nn)): per point with more than one neighbour the SPFH -- three 11-bin
+    histograms of the pair features with every neighbour but the first (the point itself), each pair counting 100 / (k - 1) -- and
+    FPFH = 100 * (sum over those neighbours of SPFH(neighbour) / d2, each histogram normalised by its own sum) + SPFH(point);
+    neighbours at distance zero add nothing to the weighted sum; zero rows for points with k <= 1.  -> (N, 33) float64."""
+    p = np.asarray(points, dtype=np.float64)
+    nrm = np.asarray(normals_, dtype=np.float64)
+    n = len(p)
+    if n == 0:
+        return np.zeros((0, 33))
+    idx, cnt, d2 = hybrid_neighbours(p, radius, max_nn)
+    nb = idx[:, 1:]                                              # the first entry is the query (or a point coincident with it)
+    used = nb >= 0
+    j = np.maximum(nb, 0)
+    f0, f1, f2 = _pair_features(p[:, None, :], nrm[:, None, :], p[j], nrm[j])
+    bins = np.stack([np.floor(11 * (f0 + np.pi) / (2 * np.pi)), 11 + np.floor(11 * (f1 + 1.0) * 0.5), 22 + np.floor(11 * (f2 + 1.0) * 0.5)], 0)
+    lo = np.array([0, 11, 22])[:, None, None]
+    bins = np.clip(bins, lo, lo + 10).astype(np.int64)
+    spfh = np.zeros((n, 33))
+    rows = np.broadcast_to(np.arange(n)[:, None], nb.shape)
+    inc = 100.0 / np.maximum(cnt - 1, 1)
+    for h in range(3):
+        np.add.at(spfh, (rows[used], bins[h][used]), 1.0)
+    spfh *= inc[:, None]
+    spfh[cnt <= 1] = 0.0
+    dist = d2[:, 1:]
+    w = np.where(used & (dist > 0), 1.0 / np.where(dist > 0, dist, 1.0), 0.0)        # (inf padding -> weight 0)
+    acc = np.einsum("nk,nkb->nb", w, spfh[j])
+    out = np.zeros((n, 33))
+    for h in range(3):
+        s = acc[:, 11 * h:11 * h + 11].sum(axis=1)
+        out[:, 11 * h:11 * h + 11] = acc[:, 11 * h:11 * h + 11] * np.where(s != 0, 100.0 / np.where(s != 0, s, 1.0), 0.0)[:, None]
+    out += spfh
+    out[cnt <= 1] = 0.0
     return out
 
 

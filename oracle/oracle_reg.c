@@ -745,6 +745,43 @@ static void matmul4(const double A[16], const double B[16], double C[16]) {
     memcpy(C, t, sizeof(t));
 }
 
+/* Symmetric 3x3 solve, LDL^T with diagonal pivoting: at each step the largest remaining diagonal entry is moved to the front by a
+ * symmetric exchange, then eliminated.  x stays zero and 0 is returned when a pivot is zero or not finite (a singular system: coincident
+ * or collinear neighbours).  Written on scalars, the same statements as solve3_sym of csrc/reg_knn.hip:
+ * the device's comparison with this oracle cannot see a slip made in both, so the FORMULA is held by tests/test_feature_model.py, which
+ * compares this copy with the least-squares restatement of oracle/open3d_fp64.py. */
+static int solve3_sym(double M[3][3], const double B[3], double x[3]) {
+    double a00 = M[0][0], a01 = M[0][1], a02 = M[0][2], a11 = M[1][1], a12 = M[1][2], a22 = M[2][2];
+    double b0 = B[0], b1 = B[1], b2 = B[2], t;
+    x[0] = x[1] = x[2] = 0.0;
+#define SWAP3(u, v) do { t = u; u = v; v = t; } while (0)
+    int first = 0;                                   /* the index exchanged with 0 */
+    if (fabs(a11) > fabs(a00) && fabs(a11) >= fabs(a22)) first = 1;
+    else if (fabs(a22) > fabs(a00)) first = 2;
+    if (first == 1) { SWAP3(a00, a11); SWAP3(a02, a12); SWAP3(b0, b1); }
+    if (first == 2) { SWAP3(a00, a22); SWAP3(a01, a12); SWAP3(b0, b2); }
+    if (a00 == 0.0 || !isfinite(a00)) return 0;
+    const double l1 = a01 / a00, l2 = a02 / a00;
+    a11 -= l1 * a01; a12 -= l1 * a02; a22 -= l2 * a02;
+    b1 -= l1 * b0; b2 -= l2 * b0;
+    const int second = fabs(a22) > fabs(a11);       /* 1 and 2 exchanged */
+    if (second) { SWAP3(a11, a22); SWAP3(a01, a02); SWAP3(b1, b2); }
+    if (a11 == 0.0 || !isfinite(a11)) return 0;
+    const double l = a12 / a11;
+    a22 -= l * a12;
+    b2 -= l * b1;
+    if (a22 == 0.0 || !isfinite(a22)) return 0;
+    double x2 = b2 / a22;
+    double x1 = (b1 - a12 * x2) / a11;
+    double x0 = (b0 - a01 * x1 - a02 * x2) / a00;
+    if (second) SWAP3(x1, x2);
+    if (first == 1) SWAP3(x0, x1);
+    if (first == 2) SWAP3(x0, x2);
+#undef SWAP3
+    x[0] = x0; x[1] = x1; x[2] = x2;
+    return 1;
+}
+
 /* InitializePointCloudForColoredICP: per target point colour gradient, hybrid (2 * max_dist, 30 nn) */
 void oracle_color_gradient(const float* pts, const float* normals, const float* intensity, int n, double radius, int max_nn,
                            float* grad /* n x 3 */) {
@@ -778,17 +815,9 @@ void oracle_color_gradient(const float* pts, const float* normals, const float* 
                 double wgt = (double)(k - 1);
                 for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) AtA[r][c] += wgt * nt[r] * wgt * nt[c];
                 (void)rows;
-                /* solve the 3x3 SPD system (Cramer) */
-                double det = AtA[0][0] * (AtA[1][1] * AtA[2][2] - AtA[1][2] * AtA[2][1]) - AtA[0][1] * (AtA[1][0] * AtA[2][2] - AtA[1][2] * AtA[2][0]) +
-                             AtA[0][2] * (AtA[1][0] * AtA[2][1] - AtA[1][1] * AtA[2][0]);
-                if (det != 0.0 && isfinite(det)) {
-                    gx[0] = (Atb[0] * (AtA[1][1] * AtA[2][2] - AtA[1][2] * AtA[2][1]) - AtA[0][1] * (Atb[1] * AtA[2][2] - AtA[1][2] * Atb[2]) +
-                             AtA[0][2] * (Atb[1] * AtA[2][1] - AtA[1][1] * Atb[2])) / det;
-                    gx[1] = (AtA[0][0] * (Atb[1] * AtA[2][2] - AtA[1][2] * Atb[2]) - Atb[0] * (AtA[1][0] * AtA[2][2] - AtA[1][2] * AtA[2][0]) +
-                             AtA[0][2] * (AtA[1][0] * Atb[2] - Atb[1] * AtA[2][0])) / det;
-                    gx[2] = (AtA[0][0] * (AtA[1][1] * Atb[2] - Atb[1] * AtA[2][1]) - AtA[0][1] * (AtA[1][0] * Atb[2] - Atb[1] * AtA[2][0]) +
-                             Atb[0] * (AtA[1][0] * AtA[2][1] - AtA[1][1] * AtA[2][0])) / det;
-                }
+                /* the symmetric 3x3 system by LDL^T with diagonal pivoting (Open3D: Eigen's ldlt().solve()); Cramer's rule lost
+                 * up to 7e-4 of max|g| to cancelling cofactors on dense, small neighbourhoods */
+                solve3_sym(AtA, Atb, gx);
             }
             grad[3 * i] = (float)gx[0]; grad[3 * i + 1] = (float)gx[1]; grad[3 * i + 2] = (float)gx[2];
         }

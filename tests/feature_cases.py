@@ -1,0 +1,257 @@
+"""Deterministic clouds for the neighbourhood kernels and their consumers (csrc/reg_knn.hip: tile search, grid-walk fallback, normals,
+SPFH/FPFH, colour gradients, radius counts), shared by tests/test_feature_model.py (CPU: the two references alone show that every cloud
+is what it claims and that holding EVERY row is fair) and tests/test_gpu_features.py (GPU: every row of every output against the oracle,
+and which path served the queries).
+
+A case is a dict
+    name        its key in CASES
+    pts         (n, 3) float32
+    intensity   (n,) float32: a smooth field plus 1 % noise (uniform noise alone on a 1 cm clump is a gradient of about 100)
+    tag         what the cloud is there for
+    random      True when the coordinates are continuous random numbers (the fp32 rule and the fp64 kd-tree must then select the
+                same neighbour sets on every row); False for clouds with exact ties or coincident points, decided by index
+    degenerate  True for clouds whose normals are not determined by the data (a line, coincident points)
+All searches use the parameters of the product at voxel 0.05: normals (0.1, 30), features (0.25, 100), gradients (0.15, 30), radius
+outliers (0.05, 8)."""
+import re
+
+import numpy as np
+
+from ibloc_amd.synth import SynthWorld
+
+VOXEL = 0.05
+NORMAL = (0.1, 30)           # (radius, max_nn) of the normal search
+FEATURE = (0.25, 100)        # ... of the SPFH / FPFH search
+GRAD = (0.15, 30)            # ... of the colour-gradient search (grad_radius=0.15)
+OUTLIER = (0.05, 8)          # radius, nb_points of the radius-outlier filter
+KNN_BINS = 256               # d2 bins over [0, r^2) of the selection (csrc/reg_knn.hip KNN_BINS)
+KNN_CAPB = 256               # entries the boundary-bin list holds (KNN_CAPB): more and the query takes the re-scanning slow path
+ST_KNN_SLOWPATH = 2          # status bit IBL_ST_KNN_SLOWPATH
+
+TOL_NORMAL = 2.0 ** -22      # two roundings of a value <= 1 to fp32 (both sides solve in double from identical fp32 points)
+TOL_FPFH = 2.0 ** -14        # four fp32 ulps of a value <= 200 (integer histograms, weighted sums in double on both sides)
+TOL_GRAD = 1e-4              # x max(1, max|g| of the cloud): the tolerance the suite already uses for gradients
+
+_cache = {}
+
+
+def _memo(fn):
+    def wrapped():
+        if fn.__name__ not in _cache:
+            _cache[fn.__name__] = fn()
+        return _cache[fn.__name__]
+    wrapped.__name__ = fn.__name__
+    wrapped.__doc__ = fn.__doc__
+    return wrapped
+
+
+def smooth_intensity(pts, seed):
+    """a smooth field of the position (gradients of order 1 per metre) + 1 % uniform noise, float32"""
+    p = np.asarray(pts, np.float64)
+    p = p - (p.mean(0) if len(p) else 0.0)
+    f = 0.5 + 0.25 * np.sin(2.0 * p[:, 0] + 0.5) + 0.15 * np.cos(3.0 * p[:, 1]) + 0.3 * p[:, 2] + 0.1 * p[:, 0] * p[:, 1]
+    return (f + 0.01 * np.random.default_rng(seed).uniform(-1.0, 1.0, size=len(p))).astype(np.float32)
+
+
+def make_case(name, pts, tag, seed, random=True, degenerate=False):
+    pts = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+    return dict(name=name, pts=pts, intensity=smooth_intensity(pts, seed), tag=tag, random=random, degenerate=degenerate)
+
+
+def _object(seed, n, k=0, m=1):
+    w = SynthWorld(m, pts_per_object=n, E=1, D=8, seed=seed)
+    p = w.points[k]
+    return p - p.mean(0)
+
+
+@_memo
+def uniform():
+    return make_case("uniform", _object(21, 1500), "one object at an even density: every query answered from its staged cube", 1)
+
+
+CLUMP_PLANE, CLUMP_N, CLUMP_HALO = 1000, 2000, 60
+
+
+@_memo
+def clump():
+    rng = np.random.default_rng(22)
+    plane = np.concatenate([rng.uniform(-0.5, 0.5, size=(CLUMP_PLANE, 2)), 0.002 * rng.normal(size=(CLUMP_PLANE, 1))], 1)
+    dense = rng.normal(size=(CLUMP_N, 3)) * [0.012, 0.012, 0.004] + [0.11, -0.07, 0.0]
+    halo = rng.uniform([-0.5, -0.5, 0.0], [0.5, 0.5, 0.6], size=(CLUMP_HALO, 3))
+    pts = np.concatenate([plane, dense, halo])[rng.permutation(CLUMP_PLANE + CLUMP_N + CLUMP_HALO)]
+    return make_case("clump", pts, "the plane sets the mean density the cells are sized from: the clump's tile exceeds the candidate cap at "
+                 "every reach and does not stage; halo points need neighbours beyond their cube and have k < 3, < 4, <= 1, < max_nn", 2)
+
+
+def clump_is_dense(c):
+    """mask of the clump's own points (within 5 sigma of its centre: no plane or halo point of this seed is that close in z AND xy)"""
+    d = (c["pts"].astype(np.float64) - [0.11, -0.07, 0.0]) / [0.012, 0.012, 0.004]
+    return (d * d).sum(1) < 25.0
+
+
+BOUNDARY_INNER, BOUNDARY_SPHERE, BOUNDARY_FAR = 10, 1500, 400
+BOUNDARY_R = 0.0502         # not 0.05: 0.05^2 is exactly the edge between bins 63 and 64 of the r = 0.1 search, where the rounding of
+                            # d2 splits the sphere over two bins (81 and 1 419 points measured); 0.0502^2 lies mid-bin for all three radii
+
+
+SPARSE_PLANE, SPARSE_HALO = 2000, 40
+
+
+@_memo
+def sparse():
+    """a dense, even plane (2 000 points on 0.4 x 0.4 m: cells of 2 - 3 cm, no staging cube near a candidate cap) with 40 isolated points
+    6 - 20 cm above it: a staging cube of three cells around such a point's tile does not reach the plane, its neighbours lie beyond the
+    cube's cover and inside the search radius, so it joins the fallback list.  (The plane and halo of `clump` do NOT do this: at its
+    low mean density three cells reach past both search radii, every cube proves its queries, fallback = 0 measured.)"""
+    rng = np.random.default_rng(29)
+    plane = np.concatenate([rng.uniform(-0.2, 0.2, size=(SPARSE_PLANE, 2)), 0.002 * rng.normal(size=(SPARSE_PLANE, 1))], 1)
+    halo = np.concatenate([rng.uniform(-0.2, 0.2, size=(SPARSE_HALO, 2)), rng.uniform(0.06, 0.2, size=(SPARSE_HALO, 1))], 1)
+    return make_case("sparse", np.concatenate([plane, halo])[rng.permutation(SPARSE_PLANE + SPARSE_HALO)], "isolated points over a dense "
+                     "plane: queries whose k-th neighbour lies beyond their cube's cover join the fallback list although every tile stages", 8)
+
+
+@_memo
+def boundary():
+    """row 0 is the centre.  11 interior points < k = 30 and 100, so the k-th neighbour of the centre is a sphere point for both searches,
+    and the sphere points share one d2 bin of width r^2 / 256"""
+    rng = np.random.default_rng(23)
+    v = rng.normal(size=(BOUNDARY_SPHERE, 3))
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    inner = rng.uniform(-1, 1, size=(BOUNDARY_INNER, 3))
+    inner *= (rng.uniform(0.001, 0.005, size=(BOUNDARY_INNER, 1)) / np.linalg.norm(inner, axis=1, keepdims=True))
+    f = rng.normal(size=(BOUNDARY_FAR, 3))
+    f *= (rng.uniform(0.07, 0.25, size=(BOUNDARY_FAR, 1)) / np.linalg.norm(f, axis=1, keepdims=True))
+    pts = np.concatenate([np.zeros((1, 3)), inner, v * BOUNDARY_R, f])
+    return make_case("boundary", pts, "the centre's boundary d2 bin holds more than KNN_CAPB entries for k = 30 and k = 100: the re-scanning "
+                 "slow path of hybrid_select", 3, random=False)          # (1 500 near-ties around the centre: its set is decided by rounding)
+
+
+def _lattice(n, pitch):
+    g = np.stack(np.meshgrid(np.arange(n), np.arange(n), indexing="ij"), -1).reshape(-1, 2) * pitch
+    return g
+
+
+@_memo
+def lattice():
+    g = _lattice(40, 0.011)
+    return make_case("lattice", np.concatenate([g, np.zeros((len(g), 1))], 1), "an exact plane: equal distances decided by index, equal normals, "
+                 "theta on a bin boundary for every pair", 4, random=False)
+
+
+@_memo
+def far():
+    rng = np.random.default_rng(25)
+    g = _lattice(40, 0.011)
+    return make_case("far", np.concatenate([g, 0.002 * rng.normal(size=(len(g), 1))], 1) + [211.5, -187.25, 3.0],
+                 "a noisy plane 280 m from the origin: fp32 coordinates with 1.5e-5 m spacing", 5)
+
+
+@_memo
+def blob():
+    rng = np.random.default_rng(26)
+    return make_case("blob", rng.uniform(-0.05, 0.05, size=(1500, 3)), "more than 100 points inside every normal radius: the fused path takes "
+                 "the normals from the 128-bit mask of the feature list", 6)
+
+
+@_memo
+def two_objects():
+    a, b = _object(27, 1000, 0, 2), _object(27, 1000, 1, 2)
+    return make_case("two_objects", np.concatenate([a + [0.3, 0.0, 0.0], b]), "two objects 0.3 m apart in one segment, like a length-2 "
+                 "assignment: neighbourhoods span both", 7)
+
+
+def _tiny(n, seed):
+    return np.random.default_rng(seed).uniform(-0.03, 0.03, size=(n, 3))
+
+
+def _patch(n, seed):
+    """a noisy plane patch of 12 cm (40 points thinned from an object are mostly isolated, and their 3-point normals ill-determined)"""
+    rng = np.random.default_rng(seed)
+    return np.concatenate([rng.uniform(-0.06, 0.06, size=(n, 2)), 0.002 * rng.normal(size=(n, 1))], 1)
+
+
+@_memo
+def tiny():
+    """0, 1, 2, 3 and 40 points, 50 coincident points and a 200-point line.  The line runs along x at a pitch of 2^-8 m: every
+    coordinate, moment and distance is exact, its covariance is exactly diag(c, 0, 0) on both sides (normal (0, 0, 1) by the solver's
+    rule for a diagonal matrix) and its gradient system is exactly singular (zero gradient)"""
+    line = np.zeros((200, 3))
+    line[:, 0] = np.arange(200) / 256.0
+    return [make_case("empty", np.zeros((0, 3)), "no point", 10),
+            make_case("one", _tiny(1, 11), "k = 1: normal (0, 0, 1), zero FPFH, zero gradient", 11),
+            make_case("two", _tiny(2, 12), "k = 2: normal (0, 0, 1), one pair, zero gradient", 12),
+            make_case("three", _tiny(3, 13), "k = 3: the first count with a solved normal; zero gradient (k < 4)", 13),
+            make_case("forty", _patch(40, 14), "fewer points than either max_nn", 14),
+            make_case("duplicates", np.tile([[0.125, -0.25, 0.5]], (50, 1)), "50 coincident points: all distances zero, zero covariance", 15,
+                  random=False, degenerate=True),
+            make_case("line", line, "200 collinear points: a covariance of rank 1, ties left and right", 16, random=False, degenerate=True)]
+
+
+def all_cases():
+    """every case, in the order of the one-batch runs"""
+    return [uniform(), clump(), sparse(), boundary(), lattice(), far(), blob(), two_objects()] + tiny()
+
+
+CASES = {"uniform": uniform, "clump": clump, "sparse": sparse, "boundary": boundary, "lattice": lattice, "far": far, "blob": blob,
+         "two_objects": two_objects}
+
+
+def dist2_f32(q, pts):
+    """the fp32 distance rule of the device and the C oracle, fmaf(dz, dz, fmaf(dy, dy, dx * dx)), for one query against (n, 3) points.
+    (The product of two fp32 values is exact in double and a sum of two doubles of this size is rounded once more by at most 2^-29 of an
+    fp32 ulp: the emulation can differ from a hardware fma only where the exact sum lies that close to a rounding boundary.)"""
+    d = (np.asarray(q, np.float32)[None, :] - np.asarray(pts, np.float32)).astype(np.float32).astype(np.float64)
+    t = (d[:, 0] * d[:, 0]).astype(np.float32).astype(np.float64)
+    t = (d[:, 1] * d[:, 1] + t).astype(np.float32).astype(np.float64)
+    return (d[:, 2] * d[:, 2] + t).astype(np.float32)
+
+
+def boundary_bin_population(pts, row, radius, max_nn):
+    """how many in-radius candidates of query `row` share the d2 bin of its max_nn-th neighbour (bins as hybrid_select forms them:
+    (int)(d2 * (256.f / r2)) in fp32) -> (population of that bin, candidates in the bins below it)"""
+    r2 = np.float32(radius * radius)
+    d2 = dist2_f32(pts[row], pts)
+    d2 = d2[d2 < r2]
+    assert len(d2) > max_nn
+    bins = np.minimum((d2 * (np.float32(KNN_BINS) / r2)).astype(np.float32).astype(np.int64), KNN_BINS - 1)
+    kth = bins[np.argsort(d2, kind="stable")[max_nn - 1]]
+    return int(np.sum(bins == kth)), int(np.sum(bins < kth))
+
+
+def rows_over(err, tol):
+    """per-row errors against a tolerance -> (worst row, number of rows that are NOT within it).  A row whose error is NaN is not within
+    any tolerance: it is counted, and it is the worst row."""
+    err = np.asarray(err, np.float64)
+    over = ~(err <= tol)
+    nan = np.isnan(err)
+    worst = int(np.argmax(nan)) if nan.any() else int(np.argmax(err))
+    return worst, int(over.sum())
+
+
+def reference(case):
+    """the C oracle's answers that do not depend on the device, computed once per case: counts of the three searches, normals, the
+    radius-outlier mask -> dict cnt_normal, cnt_feature, cnt_grad, normals, keep"""
+    from oracle import reg_oracle as ro
+    key = "ref:" + case["name"]
+    if key not in _cache:
+        p = case["pts"]
+        if len(p) == 0:
+            z = np.zeros(0, np.int32)
+            _cache[key] = dict(cnt_normal=z, cnt_feature=z, cnt_grad=z, normals=np.zeros((0, 3), np.float32), keep=np.zeros(0, bool))
+        else:
+            _cache[key] = dict(cnt_normal=ro.hybrid_sets(p, *NORMAL)[1], cnt_feature=ro.hybrid_sets(p, *FEATURE)[1],
+                               cnt_grad=ro.hybrid_sets(p, *GRAD)[1], normals=ro.normals(p, *NORMAL), keep=ro.radius_outlier(p, *OUTLIER))
+    return _cache[key]
+
+
+_KNN_LINE = re.compile(r"\[knn\] r=([0-9.]+) k=(\d+) ts=(\d+) tiles=(\d+) queries=(\d+) fallback=(\d+)")
+
+
+def parse_knn_debug(stderr_text):
+    """the lines `launch_knn` prints with the switch knn_debug=1, `[knn] r=… k=… ts=… tiles=… queries=… fallback=…`, one per tile search,
+    in call order -> list of dicts r (float), k, ts, tiles, queries, fallback (ints)"""
+    out = []
+    for m in _KNN_LINE.finditer(stderr_text):
+        r, k, ts, tiles, queries, fallback = m.groups()
+        out.append(dict(r=float(r), k=int(k), ts=int(ts), tiles=int(tiles), queries=int(queries), fallback=int(fallback)))
+    return out

@@ -1,13 +1,58 @@
-"""-m gpu: grids, hybrid neighbourhoods, normals, FPFH and radius-outlier masks vs the C oracle."""
+"""-m gpu: grids, hybrid neighbourhoods, normals, FPFH, colour gradients and radius-outlier masks vs the C oracle (csrc/reg_knn.hip).
+
+EVERY ROW.  The clouds of tests/feature_cases.py (tests/test_feature_model.py shows with the references alone what each is there for,
+and that the two references agree on every row where their neighbour sets do) go through `normals_fpfh_batch` and
+`instance_features_batch` under the default switches and under knn_noguess, feat_unfused, spfh_f64 and spfh_qcap=8, each compared with
+the ORACLE, no row left out:
+    radius-outlier mask   equal
+    normals               every component within 2^-22 of ro.normals, sign included (both sides solve in double from identical fp32
+                          points: one rounding of a value <= 1 to fp32 each); exactly (0, 0, 1) with fewer than 3 neighbours
+    FPFH                  every entry within 2^-14 of ro.fpfh(cloud, DEVICE normals) (integer histograms, weighted sums in double on
+                          both sides, values <= 200 where an fp32 ulp is 2^-16; one pair in a wrong bin of a NEIGHBOUR's histogram moves
+                          an entry by about 1e-2); exactly zero with k <= 1
+    gradients             every row within 1e-4 x max(1, max|g| of the cloud) of ro.color_gradient(cloud, DEVICE normals); exactly zero
+                          with fewer than 4 neighbours
+The oracle is given the device's normals so that a finding in the normals does not cascade into the other two.
+
+PATHS, observed with knn_debug=1 (`[knn] ... fallback=` per tile search) and ctx.status():
+    staged tile              uniform alone: fallback == 0 in every search, status 0
+    tile that cannot stage   clump alone: the 2 000 points of the clump exceed the 1 600 / 1 024-candidate cap at every reach: fallback >=
+                             the clump in the k = 100 search, 0 < fallback < queries in the k = 30 searches
+    sparse-spot fallback     sparse alone (isolated points over a dense plane): no tile near a cap, still 0 < fallback <= 80: queries
+                             whose cube cannot show their k nearest
+    boundary-bin slow path   boundary alone: status bit 1 (IBL_ST_KNN_SLOWPATH) set, clear after status(clear=True)
+
+Which instantiations the public calls reach (read off reg_api.hip and launch_knn): every search of `normals_fpfh_batch`,
+`instance_features_batch` and the registration runs on a grid of ibl_build_tile_grid, so launch_knn always takes its tile branch:
+ibl_knn_tile_kernel + ibl_knn_list_kernel.  `ibl_knn_query_kernel` (grids without tiles) is launched only when n_tiles == 0, which needs
+n_seg == 0, and those calls return before any launch: NOT reachable.  Tiles of 2^3 cells are built for the 100-neighbour searches only,
+whose factories (SpfhFactory, ListNormalFactory) are both WIDE and take the PACKED 1 600-candidate tile; the unpacked
+`ibl_knn_tile_kernel<2, 2560, Factory>` is instantiated for NormalFactory and GradFactory, which only ever see tiles of 4^3 cells: NOT
+reachable.  Reached: <4, 1024, NormalFactory> (feat_unfused), <4, 1024, GradFactory>, <2, 1600, SpfhFactory, packed> (feat_unfused),
+<2, 1600, ListNormalFactory, packed> (default), ibl_knn_list_kernel of the four factories, ibl_radius_count_kernel.
+
+Measured on an MI355X: on every cloud, under every switch and through both calls the worst row of normals, FPFH and gradients differs
+from the oracle by 0 (the fp32 outputs are equal bit for bit), and the radius-outlier masks are equal.  With Cramer's rule in the 3 x 3
+solve of the gradients, on both sides, the device missed the fp64 least-squares restatement on `clump` by 5.3e-4 x max|g| (44 rows over
+1e-4 x max|g|); with the LDL^T solve by 3.4e-8.
+fallback of queries per search (r, k, ts):  (0.1, 30, 4)   (0.15, 30, 4)   (0.25, 100, 2)
+    uniform   1 500 queries                      0              0               0           status 0
+    clump     3 060                          2 156          2 172           2 304           status 2 (dense first bins inside the clump)
+    sparse    2 040                             23             31              19           status 0
+    boundary  1 911                          1 743          1 826           1 726           status 2
+"""
 import numpy as np
 import pytest
 import torch
 
 from ibloc_amd.synth import SynthWorld
 from oracle import reg_oracle as ro
+from tests import feature_cases as fc
 
 pytestmark = pytest.mark.gpu
 
+SWITCHES = {"default": {}, "knn_noguess": dict(knn_noguess=1), "feat_unfused": dict(feat_unfused=1), "spfh_f64": dict(spfh_f64=1),
+            "spfh_qcap": dict(spfh_qcap=8)}
 
 @pytest.fixture(scope="module")
 def ctx():
@@ -26,6 +71,87 @@ def clouds(sizes, seed):
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# every row against the oracle
+# ------------------------------------------------------------------------------------------------
+_oracle_rows = {}
+
+
+def oracle_given_normals(case, nrm):
+    """ro.fpfh and ro.color_gradient of the case with the DEVICE's normals, computed once per distinct set of normals"""
+    key = (case["name"], nrm.tobytes())
+    if key not in _oracle_rows:
+        p = case["pts"]
+        _oracle_rows[key] = (ro.fpfh(p, nrm, *fc.FEATURE), ro.color_gradient(p, nrm, case["intensity"], *fc.GRAD))
+    return _oracle_rows[key]
+
+
+def run_calls(ctx, cases, grad=True, **switches):
+    """the cases as ONE batch through both public calls -> per case dict(a=(normals, fpfh) of normals_fpfh_batch, b=(normals, fpfh in
+    natural bin order, gradients) of instance_features_batch), and the status word (cleared)"""
+    from ibloc_amd.registration import FEAT_ORDER, CloudBatch, instance_features_batch, normals_fpfh_batch
+    b = CloudBatch.from_numpy([c["pts"] for c in cases], [c["intensity"] for c in cases])
+    with ctx.diag(**switches):
+        nrm, fpfh = normals_fpfh_batch(ctx, b, fc.NORMAL[0], fc.NORMAL[1], fc.FEATURE[0], fc.FEATURE[1])
+        feat = instance_features_batch(ctx, b, fc.VOXEL, grad_radius=fc.GRAD[0] if grad else 0.0)
+    torch.cuda.synchronize()
+    status = ctx.status(clear=True)
+    n = b.n
+    nrm, fpfh = nrm.cpu().numpy()[:, :3], fpfh.cpu().numpy()
+    nb = feat.normals[:n].cpu().numpy()[:, :3]
+    fb = np.empty((n, 33), np.float32)
+    fb[:, FEAT_ORDER] = feat.fpfh[:n].cpu().numpy()                      # resident rows are stored in matching order
+    gb = feat.grad[:n].cpu().numpy()[:, :3] if grad else None
+    off = b.seg_off_host
+    out = []
+    for i in range(len(cases)):
+        lo, hi = off[i], off[i + 1]
+        out.append(dict(a=(nrm[lo:hi], fpfh[lo:hi], None), b=(nb[lo:hi], fb[lo:hi], None if gb is None else gb[lo:hi])))
+    return out, status
+
+
+def compare_rows(label, case, nrm, fpfh, grad):
+    """one case's device rows against the oracle; prints the worst row of each quantity, returns the list of what missed"""
+    n = len(case["pts"])
+    assert nrm.shape == (n, 3) and fpfh.shape == (n, 33)
+    if n == 0:
+        return []
+    ref = fc.reference(case)
+    missed = []
+    for name, rows in (("normals", nrm), ("fpfh", fpfh), ("gradient", grad)):
+        if rows is not None and not np.isfinite(rows).all():
+            missed.append((label, case["name"], name, "rows that are not finite", int((~np.isfinite(rows).all(1)).sum())))
+
+    def worst(name, err, tol, extra=""):
+        w, over = fc.rows_over(err, tol)           # (a NaN row counts as over)
+        print(f"{label} {case['name']:>11s} {name:8s} worst row {w:5d} err {err[w]:.3e} (tol {tol:.3e}) rows over {over}{extra}")
+        if over:
+            missed.append((label, case["name"], name, w, float(err[w]), over))
+
+    worst("normals", np.abs(nrm.astype(np.float64) - ref["normals"]).max(1), fc.TOL_NORMAL)
+    few = ref["cnt_normal"] < 3
+    if not np.array_equal(nrm[few], np.tile(np.float32([0, 0, 1]), (int(few.sum()), 1))):
+        missed.append((label, case["name"], "normals of rows with k < 3 are not (0, 0, 1)"))
+    ef, eg = oracle_given_normals(case, np.ascontiguousarray(nrm))
+    worst("fpfh", np.abs(fpfh.astype(np.float64) - ef).max(1), fc.TOL_FPFH)
+    if fpfh[ref["cnt_feature"] <= 1].any():
+        missed.append((label, case["name"], "FPFH of rows with k <= 1 is not zero"))
+    if grad is not None:
+        scale = max(1.0, float(np.abs(eg).max()))
+        worst("gradient", np.abs(grad.astype(np.float64) - eg).max(1), fc.TOL_GRAD * scale, f" max|g| {np.abs(eg).max():.3e}")
+        if grad[ref["cnt_grad"] < 4].any():
+            missed.append((label, case["name"], "gradients of rows with k < 4 are not zero"))
+    return missed
+
+
+def compare_run(label, cases, out):
+    missed = []
+    for case, o in zip(cases, out):
+        missed += compare_rows(label + "/normals_fpfh_batch     ", case, *o["a"])
+        missed += compare_rows(label + "/instance_features_batch", case, *o["b"])
+    return missed
+
+
 def test_radius_outlier_bit_exact(ctx):
     from ibloc_amd.registration import CloudBatch, radius_outlier_batch
     cs = clouds([3000, 1, 0, 2500, 700], 3)
@@ -40,46 +166,115 @@ def test_radius_outlier_bit_exact(ctx):
     assert keep.sum() > 0 and (~keep).sum() >= 30
 
 
-def test_normals_and_fpfh_vs_oracle(ctx):
-    from ibloc_amd.registration import CloudBatch, normals_fpfh_batch
-    cs = clouds([4000, 2500, 3, 0, 1500], 5)
-    # a concatenation of two objects, like a length-2 assignment (neighbourhoods may span both)
-    cs.append(np.concatenate([cs[0][:1500] + np.float32([0.4, 0, 0]), cs[1][:1500]]))
-    b = CloudBatch.from_numpy(cs)
-    nrm, fpfh = normals_fpfh_batch(ctx, b, 0.1, 30, 0.25, 100)
-    torch.cuda.synchronize()
-    assert ctx.status() == 0
-    nrm, fpfh = nrm.cpu().numpy(), fpfh.cpu().numpy()
+@pytest.mark.parametrize("switch", list(SWITCHES))
+def test_every_row_of_every_cloud_equals_the_oracle(ctx, switch):
+    """all clouds of tests/feature_cases.py in one batch, through both calls, under one switch"""
+    cases = fc.all_cases()
+    out, status = run_calls(ctx, cases, **SWITCHES[switch])
+    missed = compare_run(switch, cases, out)
+    assert not missed, missed
+    assert status & ~fc.ST_KNN_SLOWPATH == 0 and status & fc.ST_KNN_SLOWPATH          # (the batch holds `boundary`)
+
+
+def test_radius_outlier_mask_of_every_cloud_equals_the_oracle(ctx):
+    from ibloc_amd.registration import CloudBatch, radius_outlier_batch
+    cases = fc.all_cases()
+    b = CloudBatch.from_numpy([c["pts"] for c in cases])
+    keep = radius_outlier_batch(ctx, b, *fc.OUTLIER).cpu().numpy().astype(bool)
     off = b.seg_off_host
-    for i, c in enumerate(cs):
-        if len(c) == 0:
-            continue
-        en = ro.normals(c, 0.1, 30)
-        gn = nrm[off[i]:off[i + 1], :3]
-        # same neighbour sets + same solver in double: identical up to fp32 rounding, sign included
-        err = np.abs(gn - en).max(1)
-        assert np.mean(err < 1e-5) > 0.999, f"cloud {i}: {np.mean(err < 1e-5)}"
-        ef = ro.fpfh(c, en, 0.25, 100)
-        gf = fpfh[off[i]:off[i + 1]]
-        row = np.abs(gf - ef).max(1)
-        ok = row < 2e-3
-        assert np.mean(ok) > 0.995, f"cloud {i}: fpfh rows within tol {np.mean(ok)}"
+    for i, c in enumerate(cases):
+        exp = fc.reference(c)["keep"]
+        got = keep[off[i]:off[i + 1]]
+        print(f"{c['name']:>11s}: kept {int(got.sum())} of {len(got)}, oracle {int(exp.sum())}, rows that differ {int((got != exp).sum())}")
+        assert np.array_equal(got, exp), c["name"]
+    kept = {c["name"]: int(fc.reference(c)["keep"].sum()) for c in cases}
+    assert 0 < kept["clump"] < len(fc.clump()["pts"]) and kept["one"] == 0 and kept["duplicates"] == 50
+
+
+def knn_records(ctx, capfd, case, **switches):
+    """the case ALONE through both calls with knn_debug=1 -> (device rows, status, one record per tile search in call order)"""
+    capfd.readouterr()
+    out, status = run_calls(ctx, [case], knn_debug=1, **switches)
+    recs = fc.parse_knn_debug(capfd.readouterr().err)
+    for r in recs:
+        print(f"{case['name']} {switches or 'default'}: {r}")
+    # default: the fused feature search (twice) and the gradient search; feat_unfused: normals + SPFH (twice) and the gradient search
+    expect = [(100, 2), (100, 2), (30, 4)] if not switches.get("feat_unfused") else [(30, 4), (100, 2), (30, 4), (100, 2), (30, 4)]
+    assert [(r["k"], r["ts"]) for r in recs] == expect
+    assert all(r["queries"] == len(case["pts"]) for r in recs)
+    return out, status, recs
+
+
+@pytest.mark.parametrize("switch", ["default", "feat_unfused"])
+def test_uniform_alone_is_answered_from_the_staged_cubes(ctx, capfd, switch):
+    case = fc.uniform()
+    out, status, recs = knn_records(ctx, capfd, case, **SWITCHES[switch])
+    assert [r["fallback"] for r in recs] == [0] * len(recs)
+    assert status == 0
+    missed = compare_run(switch, [case], out)
+    assert not missed, missed
+
+
+@pytest.mark.parametrize("switch", list(SWITCHES))
+def test_clump_alone_its_tile_does_not_stage(ctx, capfd, switch):
+    case = fc.clump()
+    out, status, recs = knn_records(ctx, capfd, case, **SWITCHES[switch])
+    for r in recs:
+        if r["k"] == 100:
+            assert fc.CLUMP_N <= r["fallback"] <= r["queries"], r
+        else:
+            assert 0 < r["fallback"] < r["queries"], r
+    assert status & ~fc.ST_KNN_SLOWPATH == 0          # (a query inside the clump has hundreds of candidates in its first d2 bin: bit 1 is set)
+    missed = compare_run(switch, [case], out)
+    assert not missed, missed
+
+
+@pytest.mark.parametrize("switch", ["default", "feat_unfused"])
+def test_sparse_alone_queries_beyond_their_cubes_cover_join_the_fallback(ctx, capfd, switch):
+    case = fc.sparse()
+    out, status, recs = knn_records(ctx, capfd, case, **SWITCHES[switch])
+    for r in recs:
+        assert 0 < r["fallback"] <= 2 * fc.SPARSE_HALO, r          # (the isolated points, and a few of the plane's next to them)
+    assert status == 0
+    missed = compare_run(switch, [case], out)
+    assert not missed, missed
+
+
+@pytest.mark.parametrize("switch", list(SWITCHES))
+def test_boundary_alone_takes_the_slow_path_and_flags_it(ctx, capfd, switch):
+    case = fc.boundary()
+    ctx.status(clear=True)
+    out, status, recs = knn_records(ctx, capfd, case, **SWITCHES[switch])
+    assert status == fc.ST_KNN_SLOWPATH
+    assert ctx.status(clear=False) == 0                                        # run_calls read it with clear=True
+    assert all(r["fallback"] >= 1 for r in recs)                               # (the centre at least)
+    missed = compare_run(switch, [case], out)
+    assert not missed, missed
+
+
+def test_normals_and_fpfh_vs_oracle(ctx):
+    """objects of 4 000, 2 500, 3, 0 and 1 500 points and a concatenation of two objects, like a length-2 assignment (neighbourhoods may
+    span both): every row of both calls against the oracle"""
+    cs = clouds([4000, 2500, 3, 0, 1500], 5)
+    cs.append(np.concatenate([cs[0][:1500] + np.float32([0.4, 0, 0]), cs[1][:1500]]))
+    cases = [fc.make_case("object%d" % i, c, "object cloud", 40 + i) for i, c in enumerate(cs)]
+    out, status = run_calls(ctx, cases)
+    assert status == 0
+    missed = compare_run("objects", cases, out)
+    assert not missed, missed
 
 
 def test_knn_slow_path_matches_fast_path(ctx):
-    """many equidistant candidates (points on a sphere around the query) overflow the 256-entry boundary list"""
-    from ibloc_amd.registration import CloudBatch, normals_fpfh_batch
-    rng = np.random.default_rng(2)
-    v = rng.normal(size=(3000, 3))
-    v /= np.linalg.norm(v, axis=1, keepdims=True)
-    pts = np.concatenate([np.zeros((1, 3)), v * 0.05, rng.normal(size=(500, 3)) * 0.01]).astype(np.float32)
-    b = CloudBatch.from_numpy([pts])
-    nrm, fpfh = normals_fpfh_batch(ctx, b, 0.1, 30, 0.25, 100)
-    torch.cuda.synchronize()
-    en = ro.normals(pts, 0.1, 30)
-    ef = ro.fpfh(pts, en, 0.25, 100)
-    assert np.mean(np.abs(nrm.cpu().numpy()[:, :3] - en).max(1) < 1e-5) > 0.99
-    assert np.mean(np.abs(fpfh.cpu().numpy() - ef).max(1) < 2e-3) > 0.99
+    """many equidistant candidates (points on a sphere around the query) overflow the 256-entry boundary list: the slow path is TAKEN
+    (status bit 1; the cloud this test had before kept 500 interior points, more than either k, and never reached the sphere) and every
+    row equals the oracle, under the one-pass and under the two-pass selection"""
+    case = fc.boundary()
+    ctx.status(clear=True)
+    for switch in ("default", "knn_noguess"):
+        out, status = run_calls(ctx, [case], **SWITCHES[switch])
+        assert status == fc.ST_KNN_SLOWPATH
+        missed = compare_run(switch, [case], out)
+        assert not missed, missed
 
 
 def test_fused_normals_and_feature_search_equals_the_two_searches(ctx):
