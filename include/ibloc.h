@@ -227,8 +227,18 @@ int ibl_linear_f16_ex(const ibl_linear_desc* desc, void* stream);
  *       (S = IBL_VIT_SPLIT_SCALE, value = the fp32 result a was rounded from: the K-extended operand rows of the output projection)
  *   cls_only 1: only token 0 of every crop is a query (the encoder's last block); the other rows of out are not written
  *   dim == 64 * heads, 0 <= n_tokens <= 272, terms 1..3; batch or n_tokens 0 returns IBL_OK without a launch.  Everything else is
- *   refused with a status before anything is launched. */
+ *   refused with a status before anything is launched.  Longer rows run through ibl_attention_stream_f16 below. */
 int ibl_attention_f16(const void* qkv, void* out, int batch, int n_tokens, int dim, int heads, int cls_only, int terms, void* stream);
+
+/* The same product for rows of any length up to IBL_ATT_STREAM_MAX_TOKENS: keys and values pass through LDS in chunks of 128 under an fp32
+ * online softmax, one workgroup per (crop, head, block of 64 queries) -- the kernel ibl_vit_forward runs where n_tokens > 272 (CLIP
+ * ViT-L/14@336: 577 tokens, DINOv2 at 448 / 518 px: 1025 / 1370).  Arguments, layouts, alignment and refusals as for
+ * ibl_attention_f16, except 0 <= n_tokens <= IBL_ATT_STREAM_MAX_TOKENS; short rows are accepted too (the two entries agree within the
+ * rounding of either, not bit for bit).  No atomics: a crop's rows do not depend on the batch it runs in, and cls_only row 0 is the
+ * row 0 of the full run bit for bit. */
+#define IBL_ATT_STREAM_MAX_TOKENS 8192
+int ibl_attention_stream_f16(const void* qkv, void* out, int batch, int n_tokens, int dim, int heads, int cls_only, int terms,
+                             void* stream);
 
 /* The encoder's LayerNorm on its own: out[r] = (x[r] - mean) / sqrt(var + eps) * gamma + beta over `dim` columns, biased variance
  * from a second pass over the centred row (torch.nn.LayerNorm as the reference's encoders call it).  The kernel and the launch are

@@ -1066,6 +1066,204 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void ibl_attention_kernel(const u16
 }
 
 // ------------------------------------------------------------------------------------------------
+// Streaming attention (T beyond the resident kernel's 272): one workgroup (4 waves) per (block of 64 queries, crop * head); a wave
+// owns one tile of 16 queries and walks ALL keys in chunks of 128 that pass through LDS (K rows padded to 144 B, V^T rows to 272 B: the
+// resident kernel's layouts, one chunk wide).  fp32 online softmax: running maximum m, running sum l of the unrounded p (kept as the
+// lane's partial over its own keys and reduced once at the end), O rescaled by exp2((m_old - m_new) c2) at every chunk -- no deferred
+// rescale.  p is rounded to fp16 only as the MFMA operand of P V; 1 / l is applied once in fp32 and the TERMS blocks derive from the
+// one fp16 rounding as in the resident kernel.  No atomics, the key order of every reduction is fixed: a crop's result does not
+// depend on its batch, and cls_only (query tile 0 alone, walked by wave 0 exactly as in the full run) is bit-identical to row 0 of the
+// full run.  The next chunk's global loads are issued before the compute on the current one and written to LDS after the barrier.
+// ------------------------------------------------------------------------------------------------
+#define ATT_S_THREADS 256
+#define ATT_S_KV 128         // keys per chunk
+#define ATT_S_QB 64          // queries per workgroup (16 per wave)
+template <int TERMS>
+__global__ __launch_bounds__(ATT_S_THREADS, 3) void ibl_attention_stream_kernel(const u16* __restrict__ qkv, u16* __restrict__ out, int T,
+                                                                                  int D, int heads, float scale, int cls_only) {
+    constexpr int KV = ATT_S_KV, NT = KV / 16, NS = NT / 2;
+    constexpr int KROW = 144;               // bytes per K row (64 fp16 + 16 B pad)
+    constexpr int VROW = KV * 2 + 16;       // bytes per V^T row
+    constexpr int KL = KV * 8 / ATT_S_THREADS;          // uint4 of K per thread and chunk
+    constexpr int VL = (KV / 2) * 8 / ATT_S_THREADS;    // (key pair, 8-wide d chunk) tasks of V per thread and chunk
+    __shared__ __attribute__((aligned(16))) unsigned char sK[KV * KROW];
+    __shared__ __attribute__((aligned(16))) unsigned char sV[64 * VROW];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nq = cls_only ? 1 : T;                    // rows that are queries
+    const int nqb = (nq + ATT_S_QB - 1) / ATT_S_QB;     // the query blocks of a (crop, head) are neighbours in the grid: they share K and V in L2
+    const int bh = blockIdx.x / nqb, qb = blockIdx.x % nqb;
+    const int b = bh / heads, h = bh % heads;
+    const int64_t tok0 = (int64_t)b * T;
+    const int64_t ld = 3 * (int64_t)D;
+    const u16* qbase = qkv + tok0 * ld + h * 64;
+    const u16* kbase = qbase + D;
+    const u16* vbase = qbase + 2 * D;
+
+    const int fr = lane & 15, fg = lane >> 4;
+    const int qt = qb * (ATT_S_QB / 16) + wave;
+    const bool active = qt * 16 < nq;                   // wave-uniform; an idle wave still stages and meets the barriers
+    int qrow = qt * 16 + fr;
+    if (qrow >= T) qrow = T - 1;
+    const u16* qp = qbase + (int64_t)qrow * ld + fg * 8;
+    const h16x8 qf0 = *reinterpret_cast<const h16x8*>(qp);
+    const h16x8 qf1 = *reinterpret_cast<const h16x8*>(qp + 32);
+
+    uint4 kreg[KL], vreg[VL][2];
+    // a chunk's rows from global memory into registers (zero at and beyond T: a masked key has p = 0, its V must not be NaN bytes)
+    auto load_chunk = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < KL; ++i) {
+            const int c = tid + i * ATT_S_THREADS, key = k0 + (c >> 3), c16 = c & 7;
+            kreg[i] = make_uint4(0, 0, 0, 0);
+            if (key < T) kreg[i] = *reinterpret_cast<const uint4*>(kbase + (int64_t)key * ld + c16 * 8);
+        }
+#pragma unroll
+        for (int i = 0; i < VL; ++i) {
+            const int c = tid + i * ATT_S_THREADS, key = k0 + (c % (KV / 2)) * 2, dch = c / (KV / 2);
+            vreg[i][0] = make_uint4(0, 0, 0, 0);
+            vreg[i][1] = make_uint4(0, 0, 0, 0);
+            if (key < T) vreg[i][0] = *reinterpret_cast<const uint4*>(vbase + (int64_t)key * ld + dch * 8);
+            if (key + 1 < T) vreg[i][1] = *reinterpret_cast<const uint4*>(vbase + (int64_t)(key + 1) * ld + dch * 8);
+        }
+    };
+    // registers -> LDS: K rows as they are, V transposed as packed dwords V^T[d][key .. key + 1]
+    auto store_chunk = [&]() {
+#pragma unroll
+        for (int i = 0; i < KL; ++i) {
+            const int c = tid + i * ATT_S_THREADS;
+            *reinterpret_cast<uint4*>(sK + (c >> 3) * KROW + (c & 7) * 16) = kreg[i];
+        }
+#pragma unroll
+        for (int i = 0; i < VL; ++i) {
+            const int c = tid + i * ATT_S_THREADS, key = (c % (KV / 2)) * 2, dch = c / (KV / 2);
+            const unsigned int a[4] = {vreg[i][0].x, vreg[i][0].y, vreg[i][0].z, vreg[i][0].w};
+            const unsigned int d[4] = {vreg[i][1].x, vreg[i][1].y, vreg[i][1].z, vreg[i][1].w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                *reinterpret_cast<unsigned int*>(sV + (dch * 8 + 2 * j) * VROW + key * 2) = (a[j] & 0xFFFFu) | (d[j] << 16);
+                *reinterpret_cast<unsigned int*>(sV + (dch * 8 + 2 * j + 1) * VROW + key * 2) = (a[j] >> 16) | (d[j] & 0xFFFF0000u);
+            }
+        }
+    };
+
+    const float c2 = scale * 1.4426950408889634f;       // exp(scale (s - m)) = exp2(s c2 - m c2)
+    float m = -INFINITY, l = 0.f;                       // l: this lane's share (keys 16 t + 4 fg + r of every chunk) of the row sum
+    f32x4 o[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    load_chunk(0);
+    store_chunk();
+    __syncthreads();
+    for (int k0 = 0; k0 < T; k0 += KV) {
+        const bool more = k0 + KV < T;
+        if (more) load_chunk(k0 + KV);
+        if (active) {
+            // S^T tiles of the chunk: sc[t][r] = S[q = fr][key = k0 + 16 t + 4 fg + r]
+            f32x4 sc[NT];
+            float mx = -INFINITY;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const unsigned char* kp = sK + (t * 16 + fr) * KROW + fg * 16;
+                const h16x8 kf0 = *reinterpret_cast<const h16x8*>(kp);
+                const h16x8 kf1 = *reinterpret_cast<const h16x8*>(kp + 64);
+                f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
+                a = IBL_MFMA(kf0, qf0, a, 0, 0, 0);
+                a = IBL_MFMA(kf1, qf1, a, 0, 0, 0);
+                if (k0 + t * 16 + 16 > T) {             // only the last chunk's tiles that reach past T
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (k0 + t * 16 + fg * 4 + r >= T) a[r] = -INFINITY;
+                }
+                mx = fmaxf(mx, fmaxf(fmaxf(a[0], a[1]), fmaxf(a[2], a[3])));
+                sc[t] = a;
+                asm volatile("" ::: "memory");          // keep the K fragments of later tiles from all being read first
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            // every chunk holds a key below T (the first one key 0), so mn is finite from the first chunk on; m = -inf gives alpha = 0
+            const float mn = fmaxf(m, mx);
+            const float alpha = __builtin_amdgcn_exp2f((m - mn) * c2);
+            const float mc = -mn * c2;
+            m = mn;
+            float sum = 0.f;
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float p = __builtin_amdgcn_exp2f(fmaf(sc[t][r], c2, mc));
+                    sc[t][r] = p;
+                    sum += p;
+                }
+            l = fmaf(l, alpha, sum);
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;      // the lane's 16 values all belong to query fr
+            // O += P V with the resident kernel's key permutation: A element j of lane (fr, g), k-step s, is key 32 s + 4 g + j
+            // (j < 4, tile 2 s) or 32 s + 16 + 4 g + (j - 4) (tile 2 s + 1); V^T rows are read with the same permutation
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                h16x8 pf;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    pf[j] = (_Float16)sc[2 * s][j];
+                    pf[4 + j] = (_Float16)sc[2 * s + 1][j];
+                }
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt) {
+                    const unsigned char* vp = sV + (dt * 16 + fr) * VROW + (32 * s + 4 * fg) * 2;
+                    const uint2 lo = *reinterpret_cast<const uint2*>(vp);
+                    const uint2 hi = *reinterpret_cast<const uint2*>(vp + 32);
+                    uint4 packed = make_uint4(lo.x, lo.y, hi.x, hi.y);
+                    const h16x8 vf = *reinterpret_cast<const h16x8*>(&packed);
+                    o[dt] = IBL_MFMA(vf, pf, o[dt], 0, 0, 0);       // O^T tile: rows = d, columns = q
+                }
+                asm volatile("" ::: "memory");
+            }
+        }
+        if (more) {
+            __syncthreads();        // every wave has read the current chunk
+            store_chunk();
+            __syncthreads();
+        }
+    }
+
+    const int qg = qt * 16 + fr;
+    l += __shfl_xor(l, 16, 64);     // the four lane groups of a query, in a fixed order
+    l += __shfl_xor(l, 32, 64);
+    if (active && qg < nq) {
+        const float inv = 1.0f / l;
+        u16* orow = out + (tok0 + qg) * (int64_t)(TERMS * D) + h * 64 + 4 * fg;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            float v[4];
+            unsigned short h4[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { v[r] = o[dt][r] * inv; h4[r] = f2h(v[r]); }
+            uint2 pk;
+            pk.x = (unsigned)h4[0] | ((unsigned)h4[1] << 16);
+            pk.y = (unsigned)h4[2] | ((unsigned)h4[3] << 16);
+            *reinterpret_cast<uint2*>(orow + dt * 16) = pk;
+            if (TERMS > 1) {
+                unsigned short l4[4], s4[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float hf = h2f(h4[r]);
+                    s4[r] = f2h(hf * (1.0f / IBL_VIT_SPLIT_SCALE));
+                    l4[r] = f2h((v[r] - hf) * IBL_VIT_SPLIT_SCALE);
+                }
+                if (TERMS == 3)
+                    *reinterpret_cast<uint2*>(orow + D + dt * 16) = make_uint2((unsigned)l4[0] | ((unsigned)l4[1] << 16), (unsigned)l4[2] | ((unsigned)l4[3] << 16));
+                *reinterpret_cast<uint2*>(orow + (TERMS - 1) * D + dt * 16) =
+                    make_uint2((unsigned)s4[0] | ((unsigned)s4[1] << 16), (unsigned)s4[2] | ((unsigned)s4[3] << 16));
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // C-ABI
 // ------------------------------------------------------------------------------------------------
 static inline int64_t rows_pad(int64_t r) { return ibl_align_up(r, 128); }
@@ -1168,7 +1366,26 @@ extern "C" int64_t ibl_vit_workspace_bytes(const ibl_vit_desc* d, int batch) {
     return bytes + 9 * 256;
 }
 
+// any 1 <= T <= IBL_ATT_STREAM_MAX_TOKENS; the caller has checked that the grid fits
+static int run_attention_stream(const u16* qkv, u16* out, int B, int T, int D, int heads, int cls_only, hipStream_t s, int terms) {
+    const float scale = 0.125f;   // 1/sqrt(64)
+    const int nqb = ((cls_only ? 1 : T) + ATT_S_QB - 1) / ATT_S_QB;
+    const int64_t wgs = (int64_t)B * heads * nqb;
+    if (wgs > 0x7fffffff) return ibl_set_error(IBL_ERR_ARG, "attention: batch * heads * query blocks exceeds the grid");
+    dim3 grid((unsigned)wgs), block(ATT_S_THREADS);
+    if (terms == 3) hipLaunchKernelGGL((ibl_attention_stream_kernel<3>), grid, block, 0, s, qkv, out, T, D, heads, scale, cls_only);
+    else if (terms == 2) hipLaunchKernelGGL((ibl_attention_stream_kernel<2>), grid, block, 0, s, qkv, out, T, D, heads, scale, cls_only);
+    else hipLaunchKernelGGL((ibl_attention_stream_kernel<1>), grid, block, 0, s, qkv, out, T, D, heads, scale, cls_only);
+    IBL_LAUNCH_CHECK();
+    return IBL_OK;
+}
+
 static int run_attention(const u16* qkv, u16* out, int B, int T, int D, int heads, int cls_only, hipStream_t s, int terms = 1) {
+    if (T > 272) {      // beyond the resident kernel's widest tier: keys and values stream through LDS
+        if (T > IBL_ATT_STREAM_MAX_TOKENS)
+            return ibl_set_error(IBL_ERR_UNSUPPORTED, "attention: n_tokens %d > %d not supported", T, IBL_ATT_STREAM_MAX_TOKENS);
+        return run_attention_stream(qkv, out, B, T, D, heads, cls_only, s, terms);
+    }
     const float scale = 0.125f;   // 1/sqrt(64)
     const int nt = (T + 15) / 16;
     dim3 grid(B * heads), block(ATT_THREADS);
@@ -1210,6 +1427,26 @@ extern "C" int ibl_attention_f16(const void* qkv, void* out, int batch, int n_to
         return ibl_set_error(IBL_ERR_ARG, "ibl_attention_f16: qkv must be 16-byte and out 8-byte aligned");
     return run_attention(reinterpret_cast<const u16*>(qkv), reinterpret_cast<u16*>(out), batch, n_tokens, dim, heads, cls_only,
                          reinterpret_cast<hipStream_t>(stream), terms);
+}
+
+extern "C" int ibl_attention_stream_f16(const void* qkv, void* out, int batch, int n_tokens, int dim, int heads, int cls_only, int terms,
+                                        void* stream) {
+    if (batch < 0 || n_tokens < 0)
+        return ibl_set_error(IBL_ERR_ARG, "ibl_attention_stream_f16: negative batch (%d) or n_tokens (%d)", batch, n_tokens);
+    if (terms < 1 || terms > 3) return ibl_set_error(IBL_ERR_ARG, "ibl_attention_stream_f16: terms %d outside 1..3", terms);
+    if (cls_only != 0 && cls_only != 1) return ibl_set_error(IBL_ERR_ARG, "ibl_attention_stream_f16: cls_only must be 0 or 1");
+    if (heads <= 0 || dim != heads * 64)
+        return ibl_set_error(IBL_ERR_UNSUPPORTED, "ibl_attention_stream_f16: dim (%d) must be 64 * heads (%d): head_dim is 64", dim, heads);
+    if (n_tokens > IBL_ATT_STREAM_MAX_TOKENS)
+        return ibl_set_error(IBL_ERR_UNSUPPORTED, "ibl_attention_stream_f16: n_tokens %d > %d not supported", n_tokens, IBL_ATT_STREAM_MAX_TOKENS);
+    if ((int64_t)batch * heads * ((n_tokens + ATT_S_QB - 1) / ATT_S_QB) > 0x7fffffff)
+        return ibl_set_error(IBL_ERR_ARG, "ibl_attention_stream_f16: batch * heads * query blocks exceeds the grid");
+    if (batch == 0 || n_tokens == 0) return IBL_OK;
+    if (!qkv || !out) return ibl_set_error(IBL_ERR_ARG, "ibl_attention_stream_f16: null pointer");
+    if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 7))
+        return ibl_set_error(IBL_ERR_ARG, "ibl_attention_stream_f16: qkv must be 16-byte and out 8-byte aligned");
+    return run_attention_stream(reinterpret_cast<const u16*>(qkv), reinterpret_cast<u16*>(out), batch, n_tokens, dim, heads, cls_only,
+                                reinterpret_cast<hipStream_t>(stream), terms);
 }
 
 extern "C" int ibl_layernorm_f32(const float* x, int64_t ld_x, int64_t n_rows, int dim, const float* gamma, const float* beta, float eps,

@@ -100,6 +100,11 @@ RECIPES = {
     "dinov2": PreprocessRecipe("dinov2", 224, 224, "shortest", 256, BICUBIC, True, IMAGENET_MEAN, IMAGENET_STD),
     "vit": PreprocessRecipe("vit", 224, 224, "exact", 0, BILINEAR, True, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)),
     "clip": PreprocessRecipe("clip", 224, 224, "shortest", 224, BICUBIC, True, CLIP_MEAN, CLIP_STD, "round"),
+    # the high-resolution encoders: OpenAI's preprocessing of ViT-L/14@336; DINOv2 at 448 and 518 px with the HF processor's 256 / 224
+    # ratio between the resized shortest edge and the crop
+    "clip_336": PreprocessRecipe("clip_336", 336, 336, "shortest", 336, BICUBIC, True, CLIP_MEAN, CLIP_STD, "round"),
+    "dinov2_448": PreprocessRecipe("dinov2_448", 448, 448, "shortest", 512, BICUBIC, True, IMAGENET_MEAN, IMAGENET_STD),
+    "dinov2_518": PreprocessRecipe("dinov2_518", 518, 518, "shortest", 592, BICUBIC, True, IMAGENET_MEAN, IMAGENET_STD),
     "dator_rgb": PreprocessRecipe("dator_rgb", 256, 128, "exact", 0, BILINEAR, False, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)),
 }
 

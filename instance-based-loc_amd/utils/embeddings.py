@@ -131,7 +131,9 @@ def load_encoder(kind: str, state_dict, device="cuda", cfg: V.VitConfig = None):
     "clip": the state dict may be open_clip's / OpenAI's `model.visual.state_dict()` or transformers' CLIPVisionModelWithProjection /
     CLIPModel one; the key layout picks the converter.  A state dict does not carry the activation: it is `cfg.quick_gelu`, the caller's
     -- the default cfg (clip_b32, laion2b) runs erf GELU; OpenAI's checkpoints, open_clip's *-quickgelu models and transformers models
-    with hidden_act "quick_gelu" need V.CONFIGS["clip_b32_openai"] / "clip_b16_openai" / "clip_l14_openai".
+    with hidden_act "quick_gelu" need V.CONFIGS["clip_b32_openai"] / "clip_b16_openai" / "clip_l14_openai" / "clip_l14_336_openai".
+    cfg may also be the name of a configuration: "clip_l14_336_openai" (577 tokens, its 24 x 24 position table as stored),
+    "dinov2_vitb14_448" or "dinov2_vitb14_518" (the 37 x 37 table as stored) run the same checkpoints' towers at their high resolutions.
 
     "dator": `state_dict` is a `build_FourDNet` checkpoint as the reference's `load_model('.../dator_best_tum.pth')` reads it
     (utils/embeddings.py:101-103, make_model.py:620-626) -- the dict itself or the path of the `.pth` file (loaded with
@@ -145,6 +147,8 @@ def load_encoder(kind: str, state_dict, device="cuda", cfg: V.VitConfig = None):
         enc = D.DatorEncoder(rw, dw, hw, device=device)
         set_encoder(kind, enc)
         return enc
+    if isinstance(cfg, str):
+        cfg = V.CONFIGS[cfg]
     cfg = cfg or V.CONFIGS[_KIND_TO_CONFIG[kind]]
     conv = clip_converter(state_dict) if kind == "clip" else {"dino": hf_dinov2_to_weights, "vit": hf_vit_to_weights}[kind]
     enc = V.VitEncoder(cfg, conv(state_dict, cfg.depth), device=device)

@@ -170,8 +170,18 @@ CONFIGS = {
                                  ln_eps=1e-5, recipe="clip", quick_gelu=True),
     "clip_l14_openai": VitConfig("clip_l14_openai", 1024, 24, 16, 4096, 14, 224, 224, (16, 16), pre_ln=True, proj_dim=768,
                                  ln_eps=1e-5, recipe="clip", quick_gelu=True),
+    # the same towers at their high input resolutions: more than 272 tokens per crop, so the attention streams its keys
+    # (ibl_attention_stream_kernel).  OpenAI CLIP ViT-L/14@336 (577 tokens, its 24 x 24 table as stored); facebook/dinov2-base at 448 px
+    # (1 025 tokens, table resampled) and at the 518 px its checkpoints are trained at (1 370 tokens, the 37 x 37 table as stored)
+    "clip_l14_336_openai": VitConfig("clip_l14_336_openai", 1024, 24, 16, 4096, 14, 336, 336, (24, 24), pre_ln=True, proj_dim=768,
+                                     ln_eps=1e-5, recipe="clip_336", quick_gelu=True),
+    "dinov2_vitb14_448": VitConfig("dinov2_vitb14_448", 768, 12, 12, 3072, 14, 448, 448, (37, 37), layerscale=True,
+                                   recipe="dinov2_448"),
+    "dinov2_vitb14_518": VitConfig("dinov2_vitb14_518", 768, 12, 12, 3072, 14, 518, 518, (37, 37), layerscale=True,
+                                   recipe="dinov2_518"),
     # tiny configurations used by the parity tests
     "tiny_dino": VitConfig("tiny_dino", 128, 2, 2, 256, 14, 224, 224, (37, 37), layerscale=True, recipe="dinov2"),
+    "tiny_dino_518": VitConfig("tiny_dino_518", 128, 2, 2, 256, 14, 518, 518, (37, 37), layerscale=True, recipe="dinov2_518"),
     "tiny_clip": VitConfig("tiny_clip", 128, 2, 2, 256, 32, 224, 224, (7, 7), pre_ln=True, proj_dim=128,
                            ln_eps=1e-5, recipe="clip"),
     "tiny_clip_q": VitConfig("tiny_clip_q", 128, 2, 2, 256, 32, 224, 224, (7, 7), pre_ln=True, proj_dim=128,
@@ -557,6 +567,21 @@ def attention_f16(qkv: torch.Tensor, heads: int, cls_only: bool = False, terms: 
     st = _lib.lib.ibl_attention_f16(qkv.data_ptr(), out.data_ptr(), batch, n_tokens, dim, heads, int(cls_only), terms,
                                      torch.cuda.current_stream().cuda_stream)
     _lib.check(st, "ibl_attention_f16")
+    return out
+
+
+def attention_stream_f16(qkv: torch.Tensor, heads: int, cls_only: bool = False, terms: int = 1, out=None) -> torch.Tensor:
+    """softmax(q k^T / 8) v per (crop, head) through `ibl_attention_stream_f16`: the kernel the encoder runs beyond 272 tokens (keys and
+    values stream through LDS under an fp32 online softmax), on its own.  Arguments and result as for `attention_f16`; n_tokens may be
+    anything up to 8192, short rows included.  Shapes the kernel cannot run are refused by the library: IblError."""
+    assert qkv.dtype == torch.float16 and qkv.is_cuda and qkv.dim() == 3 and qkv.is_contiguous() and qkv.shape[2] % 3 == 0
+    batch, n_tokens, dim = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
+    if out is None:
+        out = torch.empty((batch, n_tokens, max(int(terms), 0) * dim), device=qkv.device, dtype=torch.float16)
+    assert out.dtype == torch.float16 and out.is_cuda and out.is_contiguous() and out.shape == (batch, n_tokens, terms * dim)
+    st = _lib.lib.ibl_attention_stream_f16(qkv.data_ptr(), out.data_ptr(), batch, n_tokens, dim, heads, int(cls_only), terms,
+                                            torch.cuda.current_stream().cuda_stream)
+    _lib.check(st, "ibl_attention_stream_f16")
     return out
 
 
