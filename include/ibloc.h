@@ -20,8 +20,8 @@
  *     never synchronise.  Functions that return HOST results synchronise the stream -- how often is stated per function:
  *     ibl_radius_outlier_batch 1 (grid table size), ibl_instance_features_batch 2 (bounding boxes; end),
  *     ibl_register_jobs 2-4 (one per group of RANSAC rounds -- most calls need one -- plus the results; one more when
- *     instances of a job lie within the influence radius of each other), ibl_evaluate_batch 1, ibl_memgrid_build / _append 2
- *     (cell count; end).  Plan tables are staged through pinned host memory of the registration context, so uploads never wait.
+ *     instances of a job lie within the influence radius of each other), ibl_evaluate_batch 1, ibl_memgrid_build / _append / _remove 2
+ *     (cell count; end; one more when the call has to reallocate the other point buffer).  Plan tables are staged through pinned host memory of the registration context, so uploads never wait.
  *   - plain C types only; no torch types in any signature.
  */
 #ifndef IBLOC_H
@@ -590,7 +590,7 @@ int ibl_dbscan_batch(ibl_reg_ctx* ctx, const double* points, const int32_t* grp_
 /* Persistent spatial hash over ALL memory points (world frame), built once per memory upload.  Replaces the
  * KD-tree Open3D rebuilds over `all_memory_pcd` on every evaluate_registration call (utils/fpfh_register.py:146-148
  * <- object_memory/object_memory.py:1104).  cell >= 2 * threshold keeps a query to <= 8 cells.
- *   The grid owns its device arrays (hipMalloc: 16 bytes per point, 12 per occupied cell, 12 per table slot); ctx's arena is
+ *   The grid owns its device arrays (hipMalloc: 16 bytes per point -- 20 in a live grid, see ibl_memgrid_remove --, 12 per occupied cell, 12 per table slot); ctx's arena is
  *   scratch only (40 bytes per point + the sort's, released on return).  live == 0: the grid is immutable and reserve_points must
  *   be 0 (else IBL_ERR_ARG); live != 0: a grid for a memory that grows while it is resident, see ibl_memgrid_append.  A failed
  *   build frees what it allocated; a cell table found full is IBL_ERR_OVERFLOW.
@@ -619,6 +619,37 @@ int ibl_memgrid_destroy(ibl_memgrid* grid);
 int ibl_memgrid_append(ibl_reg_ctx* ctx, ibl_memgrid* grid, const float* new_pts4, int64_t n_new, void* stream);
 int ibl_memgrid_info(const ibl_memgrid* grid, int64_t* n, int32_t* n_cells, int64_t* table_slots, int64_t* point_capacity,
                      int32_t* ustart_end, void* stream);
+
+/* Live memory, the other direction: ibl_memgrid_remove takes points out of a grid built with live != 0.
+ *   range_begin / range_end [HOST] n_ranges entries: half-open ranges over the ORIGINAL point indices of the grid -- a point's position
+ *   in the array the grid was built from, plus everything appended since (the indices a batch's segment offsets speak of).  The
+ *   ranges must be ascending, disjoint (they may touch) and non-empty, and must leave at least one point.
+ *   Afterwards the grid holds what ibl_memgrid_build returns for the kept points in their original order, array for array: sorted,
+ *   ukeys, ustart, n, n_cells and the table dimension of the build's rule (smallest power of two >= 3 x cells, >= 1024 -- the table
+ *   shrinks logically when cells disappear).  The kept points count as renumbered: original index i becomes i - #removed below i.
+ *   Allocations and capacities do not shrink: the freed room is headroom for later appends, and ibl_memgrid_info reports the same
+ *   point capacity before and after (the half of the ping-pong pair that becomes current is brought to the current half's size).
+ *   A live grid keeps, for this call, the original index of the point in every sorted slot (4 bytes per point on top of the 16,
+ *   in both halves of the ping-pong pair; an immutable grid has none; no evaluation reads it).  The removal is one stable compaction
+ *   of the cell-ordered points into the other half of the pair -- no sort: slots are flagged by a binary search of their index in
+ *   the ranges, the flags are scanned, kept points move with their keys and renumbered indices, and cell arrays and table are
+ *   rebuilt as after an append.  A stable compaction of an array in (cell, index) order is in (cell, index) order: that is the
+ *   build's order of the kept points.  Traffic ~36 B per point for points and indices + ~40 B for flags, keys and scans.  Scratch:
+ *   8 bytes per resident point + 16 per kept point + 12 per range from ctx's arena, released on return; a grid that was never
+ *   appended to allocates the second half of its pair here, and one whose last append grew reallocates the smaller half (both as
+ *   large as the current one).
+ *   n_ranges == 0 is a no-op (IBL_OK).  IBL_ERR_ARG, decided on the host before anything is launched and leaving the grid as it
+ *   was: a grid built with live == 0; ranges that are unsorted, overlapping, empty or pass n; ranges that cover every point; null
+ *   pointers with n_ranges > 0.  The arena error and an allocation error leave the grid as it was, too.
+ *   Synchronisation: as ibl_memgrid_append -- the call synchronises `stream` before it returns, and no evaluation that uses the grid
+ *   may be in flight on ANY other stream during the call.
+ * ibl_memgrid_export copies the grid's current arrays, device to device and asynchronously on `stream`: the n points in cell order,
+ * the n_cells unique cell keys and the n_cells + 1 cell starts (sizes from ibl_memgrid_info; any pointer may be NULL).  For tests
+ * and diagnostics that compare grids array for array. */
+int ibl_memgrid_remove(ibl_reg_ctx* ctx, ibl_memgrid* grid, const int64_t* range_begin, const int64_t* range_end, int n_ranges,
+                       void* stream);
+int ibl_memgrid_export(const ibl_memgrid* grid, float* sorted_out /* [dev] n x 4 */, uint64_t* ukeys_out /* [dev] n_cells */,
+                       int32_t* ustart_out /* [dev] n_cells + 1 */, void* stream);
 
 /* evaluate_transform(all_detected_pcd, all_memory_pcd, T) for n_jobs candidates: job j transforms the detected
  * points [job_begin[j], job_end[j]) of det_pts4 [dev] by T_global[j] (host, 16 doubles row-major) and looks for

@@ -35,11 +35,14 @@ struct MemGridView {
 
 // The grid owns its device arrays (hipMalloc; freed by ibl_memgrid_destroy): a ping-pong pair for the points (a merge writes buf[cur]
 // and the new points into buf[1 - cur], which the first append that needs it allocates), cell arrays and a table with their own
-// capacities.  v.sorted is buf[cur].
+// capacities.  v.sorted is buf[cur].  A live grid also remembers, per sorted slot, the original index of the point that sits there
+// (sidx, 4 bytes per point, allocated, ping-ponged and grown with the point buffers): ibl_memgrid_remove finds a removed instance's
+// slots by it.  Nothing on the query path reads it; an immutable grid has none.
 struct ibl_memgrid {
     MemGridView v = {};
-    int fixed = 0;                      // 1: made by ibl_memgrid_build with live = 0 -- immutable, ibl_memgrid_append refuses it
+    int fixed = 0;                      // 1: made by ibl_memgrid_build with live = 0 -- immutable, ibl_memgrid_append / _remove refuse it
     float4* buf[2] = {nullptr, nullptr};
+    int* sidx[2] = {nullptr, nullptr};  // original index of the point in slot i of buf[.] (live grids only)
     int64_t buf_cap[2] = {0, 0};        // points
     int cur = 0;
     int64_t cell_cap = 0;               // ukeys holds cell_cap, ustart cell_cap + 1 entries
@@ -84,10 +87,12 @@ __device__ __forceinline__ int mg_bound(const unsigned long long* __restrict__ k
 
 // Stable merge, old side: point i of the cell-ordered old points moves up by the number of new points in cells before its own (new
 // points of its own cell follow it: they have the higher original indices).  One thread per point, 16-byte load and store; the new
-// keys are a few thousand and stay in cache.  The merged keys go along for the cell boundaries.
-__global__ __launch_bounds__(256) void ibl_mg_merge_old_kernel(const float4* __restrict__ src, int64_t n_old, float inv,
-                                                               const unsigned long long* __restrict__ nkeys, int n_new,
-                                                               float4* __restrict__ dst, unsigned long long* __restrict__ mkeys) {
+// keys are a few thousand and stay in cache.  The merged keys go along for the cell boundaries, and a live grid's original indices
+// (sidx_src / sidx_dst, null for an immutable grid) with their points.
+__global__ __launch_bounds__(256) void ibl_mg_merge_old_kernel(const float4* __restrict__ src, const int* __restrict__ sidx_src, int64_t n_old,
+                                                               float inv, const unsigned long long* __restrict__ nkeys, int n_new,
+                                                               float4* __restrict__ dst, int* __restrict__ sidx_dst,
+                                                               unsigned long long* __restrict__ mkeys) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_old) return;
     const float4 p = src[i];
@@ -95,6 +100,7 @@ __global__ __launch_bounds__(256) void ibl_mg_merge_old_kernel(const float4* __r
     const int64_t d = i + mg_bound(nkeys, n_new, k, 0);
     dst[d] = p;
     mkeys[d] = k;
+    if (sidx_dst) sidx_dst[d] = sidx_src[i];
 }
 
 // new side: sorted new point j moves up by the number of old points in cells up to and including its own, read from the old cell arrays
@@ -102,13 +108,63 @@ __global__ __launch_bounds__(256) void ibl_mg_merge_old_kernel(const float4* __r
 __global__ __launch_bounds__(256) void ibl_mg_merge_new_kernel(const float4* __restrict__ pts, const int* __restrict__ order,
                                                                const unsigned long long* __restrict__ nkeys, int n_new,
                                                                const unsigned long long* __restrict__ ukeys, const int* __restrict__ ustart,
-                                                               int n_cells, float4* __restrict__ dst, unsigned long long* __restrict__ mkeys) {
+                                                               int n_cells, int n_old, float4* __restrict__ dst, int* __restrict__ sidx_dst,
+                                                               unsigned long long* __restrict__ mkeys) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= n_new) return;
     const unsigned long long k = nkeys[j];
     const int64_t d = (int64_t)j + ustart[mg_bound(ukeys, n_cells, k, 1)];
-    dst[d] = pts[order[j]];
+    const int src = order[j];
+    dst[d] = pts[src];
     mkeys[d] = k;
+    if (sidx_dst) sidx_dst[d] = n_old + src;        // the new points count as the points behind all earlier ones
+}
+
+// ---- removal: a stable compaction of the cell-ordered points (ibl_memgrid_remove) ------------------------------------------------
+// The removed points are given as R ascending, disjoint, non-empty ranges of original indices: rbeg / rend, and rcum[r] = the
+// points in the ranges 0 .. r.  For original index `idx`: is it kept, and how many removed points lie below it.  One binary
+// search, bounded by R (a few thousand entries at most: they stay in cache).
+__device__ __forceinline__ bool mg_kept(const int* __restrict__ rbeg, const int* __restrict__ rend, const int* __restrict__ rcum, int R,
+                                        int idx, int* below) {
+    int lo = 0, hi = R;                             // lo = number of ranges that begin at or below idx
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (rbeg[mid] <= idx) lo = mid + 1; else hi = mid;
+    }
+    if (lo == 0) { *below = 0; return true; }
+    *below = rcum[lo - 1];                          // (of a kept point: every range that begins below it also ends below it)
+    return idx >= rend[lo - 1];
+}
+
+// one thread per resident slot: 1 for a point that stays
+__global__ __launch_bounds__(256) void ibl_mg_remove_flag_kernel(const int* __restrict__ sidx, int64_t n, const int* __restrict__ rbeg,
+                                                                 const int* __restrict__ rend, const int* __restrict__ rcum, int R,
+                                                                 int* __restrict__ keep) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int below;
+    keep[i] = mg_kept(rbeg, rend, rcum, R, sidx[i], &below) ? 1 : 0;
+}
+
+// Kept slot i moves to keep_scan[i] (the exclusive sum of the flags) of the other point buffer: 16-byte load and store, its key
+// (recomputed with the build's floorf(p * inv)) for the cell boundaries, its original index renumbered to the index it has among
+// the kept points.  Per resident point 4 B (flag) + 4 B (scan) + 4 B (sidx) read, per kept point 16 B read and 16 + 8 + 4 B written.
+__global__ __launch_bounds__(256) void ibl_mg_remove_scatter_kernel(const float4* __restrict__ src, const int* __restrict__ sidx_src, int64_t n,
+                                                                    float inv, const int* __restrict__ rbeg, const int* __restrict__ rend,
+                                                                    const int* __restrict__ rcum, int R, const int* __restrict__ keep,
+                                                                    const int* __restrict__ keep_scan, int64_t n_keep, float4* __restrict__ dst,
+                                                                    int* __restrict__ sidx_dst, unsigned long long* __restrict__ mkeys) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || !keep[i]) return;
+    const int64_t d = keep_scan[i];
+    if (d < 0 || d >= n_keep) return;               // (cannot happen: the host counted n_keep from the same ranges)
+    int below;
+    const int idx = sidx_src[i];
+    mg_kept(rbeg, rend, rcum, R, idx, &below);
+    const float4 p = src[i];
+    dst[d] = p;
+    mkeys[d] = mg_key((int)floorf(p.x * inv), (int)floorf(p.y * inv), (int)floorf(p.z * inv));
+    sidx_dst[d] = idx - below;
 }
 
 __global__ __launch_bounds__(256) void ibl_mg_merged_cells_kernel(const unsigned long long* __restrict__ mkeys, const int* __restrict__ head,
@@ -135,49 +191,35 @@ __global__ __launch_bounds__(256) void ibl_mg_insert_bounded_kernel(const unsign
     atomicExch(failed, 1);
 }
 
-// Merges n_new (> 0) further points into the grid -- all of them into an empty grid: that is the build.  The new points are keyed and
-// sorted (stable: equal keys keep their index order), both sides are merged into the other point buffer, the cells are read off the
-// merged keys and the table is refilled.  reserve_points: room for further cells when the cell arrays are (re)allocated.
-// The arena is scratch only.  Synchronises `s` after the cells are counted and before it returns.
-static int mg_merge(ibl_reg_ctx* ctx, ibl_memgrid* g, const float4* P, int64_t n_new, int64_t reserve_points, hipStream_t s, const char* who) {
-    const int64_t n_old = g->v.n, n = n_old + n_new;
-    ArenaMark scratch(ctx);
-    unsigned long long *keys, *nkeys, *mkeys; int *vals, *order, *head, *hscan, *failed; unsigned char* tmp;
-    IBL_ARENA(keys, unsigned long long, n_new);
-    IBL_ARENA(nkeys, unsigned long long, n_new);
-    IBL_ARENA(vals, int, n_new);
-    IBL_ARENA(order, int, n_new);
-    IBL_ARENA(mkeys, unsigned long long, n);
-    IBL_ARENA(head, int, n + 1);
-    IBL_ARENA(hscan, int, n + 1);
-    IBL_ARENA(failed, int, 1);
-    size_t t1 = 0, t2 = 0;
-    IBL_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, keys, nkeys, vals, order, (int)n_new, 0, 63, s));
-    IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, head, hscan, (int)n, s));
-    IBL_ARENA(tmp, unsigned char, (int64_t)std::max(t1, t2) + 256);
-    // the other half of the ping-pong pair: grown by 1.5 when the merged points no longer fit
+// Frees the half of the ping-pong pair that is not current and allocates it again for `cap` points (a live grid's original indices
+// with it).  The current half, and with it the grid, is untouched whatever happens.
+static int mg_alloc_other(ibl_memgrid* g, int64_t cap, hipStream_t s, const char* who) {
     const int o = 1 - g->cur;
-    if (g->buf_cap[o] < n) {
-        const int64_t cap = std::min<int64_t>(0x7FFFFFF0ll, std::max<int64_t>(n, g->buf_cap[g->cur] + g->buf_cap[g->cur] / 2));
-        IBL_HIP_CHECK(hipStreamSynchronize(s));
+    IBL_HIP_CHECK(hipStreamSynchronize(s));
+    (void)hipFree(g->buf[o]); (void)hipFree(g->sidx[o]);
+    g->buf[o] = nullptr; g->sidx[o] = nullptr; g->buf_cap[o] = 0;
+    hipError_t e = hipMalloc(&g->buf[o], sizeof(float4) * (size_t)cap);
+    if (e == hipSuccess && !g->fixed) e = hipMalloc(&g->sidx[o], sizeof(int) * (size_t)cap);
+    if (e != hipSuccess) {
         (void)hipFree(g->buf[o]);
-        g->buf[o] = nullptr; g->buf_cap[o] = 0;
-        IBL_HIP_CHECK(hipMalloc(&g->buf[o], sizeof(float4) * (size_t)cap));
-        g->buf_cap[o] = cap;
+        g->buf[o] = nullptr;
+        return ibl_set_error(IBL_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     }
+    g->buf_cap[o] = cap;
+    return IBL_OK;
+}
+
+// The tail of a merge and of a removal: buf[1 - cur] holds the n points of the new state in cell order and mkeys their keys.  Reads
+// the cells off the keys (head flags, scan), dimensions and allocates what no longer fits, makes the other buffer the current one
+// and refills the table.  head / hscan: n + 1 ints each, tmp: tmp_bytes of scan scratch, failed: 1 int -- the caller's arena scratch.
+// Synchronises `s` after the cells are counted and before it returns.
+static int mg_cells_table(ibl_memgrid* g, int64_t n, const unsigned long long* mkeys, int* head, int* hscan, int* failed,
+                          unsigned char* tmp, size_t tmp_bytes, int64_t reserve_points, hipStream_t s, const char* who) {
+    const int o = 1 - g->cur;
     float4* dst = g->buf[o];
-    const unsigned nb_new = (unsigned)((n_new + 255) / 256), nb_old = (unsigned)((n_old + 255) / 256), nb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(ibl_mg_key_kernel, dim3(nb_new), dim3(256), 0, s, P, n_new, g->v.inv, keys, vals);
-    IBL_LAUNCH_CHECK();
-    IBL_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, t1, keys, nkeys, vals, order, (int)n_new, 0, 63, s));
-    if (n_old > 0) {
-        hipLaunchKernelGGL(ibl_mg_merge_old_kernel, dim3(nb_old), dim3(256), 0, s, g->v.sorted, n_old, g->v.inv, nkeys, (int)n_new, dst, mkeys);
-        IBL_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(ibl_mg_merge_new_kernel, dim3(nb_new), dim3(256), 0, s, P, order, nkeys, (int)n_new, g->v.ukeys, g->v.ustart,
-                       g->v.n_cells, dst, mkeys);
-    IBL_LAUNCH_CHECK();
-    // cells of the merged order, counted
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    size_t t2 = tmp_bytes;
+    // cells of the new order, counted
     hipLaunchKernelGGL(ibl_mg_heads_kernel, dim3(nb), dim3(256), 0, s, mkeys, n, head);
     IBL_LAUNCH_CHECK();
     IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, t2, head, hscan, (int)n, s));
@@ -232,9 +274,67 @@ static int mg_merge(ibl_reg_ctx* ctx, ibl_memgrid* g, const float4* P, int64_t n
     return IBL_OK;
 }
 
+// Merges n_new (> 0) further points into the grid -- all of them into an empty grid: that is the build.  The new points are keyed and
+// sorted (stable: equal keys keep their index order), both sides are merged into the other point buffer, the cells are read off the
+// merged keys and the table is refilled.  reserve_points: room for further cells when the cell arrays are (re)allocated.
+// The arena is scratch only.  Synchronises `s` after the cells are counted and before it returns.
+static int mg_merge(ibl_reg_ctx* ctx, ibl_memgrid* g, const float4* P, int64_t n_new, int64_t reserve_points, hipStream_t s, const char* who) {
+    const int64_t n_old = g->v.n, n = n_old + n_new;
+    ArenaMark scratch(ctx);
+    unsigned long long *keys, *nkeys, *mkeys; int *vals, *order, *head, *hscan, *failed; unsigned char* tmp;
+    IBL_ARENA(keys, unsigned long long, n_new);
+    IBL_ARENA(nkeys, unsigned long long, n_new);
+    IBL_ARENA(vals, int, n_new);
+    IBL_ARENA(order, int, n_new);
+    IBL_ARENA(mkeys, unsigned long long, n);
+    IBL_ARENA(head, int, n + 1);
+    IBL_ARENA(hscan, int, n + 1);
+    IBL_ARENA(failed, int, 1);
+    size_t t1 = 0, t2 = 0;
+    IBL_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, keys, nkeys, vals, order, (int)n_new, 0, 63, s));
+    IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, head, hscan, (int)n, s));
+    IBL_ARENA(tmp, unsigned char, (int64_t)std::max(t1, t2) + 256);
+    // the other half of the ping-pong pair: grown by 1.5 when the merged points no longer fit
+    const int o = 1 - g->cur;
+    if (g->buf_cap[o] < n) {
+        const int st = mg_alloc_other(g, std::min<int64_t>(0x7FFFFFF0ll, std::max<int64_t>(n, g->buf_cap[g->cur] + g->buf_cap[g->cur] / 2)), s, who);
+        if (st != IBL_OK) return st;
+    }
+    float4* dst = g->buf[o];
+    const unsigned nb_new = (unsigned)((n_new + 255) / 256), nb_old = (unsigned)((n_old + 255) / 256);
+    hipLaunchKernelGGL(ibl_mg_key_kernel, dim3(nb_new), dim3(256), 0, s, P, n_new, g->v.inv, keys, vals);
+    IBL_LAUNCH_CHECK();
+    IBL_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, t1, keys, nkeys, vals, order, (int)n_new, 0, 63, s));
+    if (n_old > 0) {
+        hipLaunchKernelGGL(ibl_mg_merge_old_kernel, dim3(nb_old), dim3(256), 0, s, g->v.sorted, g->sidx[g->cur], n_old, g->v.inv, nkeys,
+                           (int)n_new, dst, g->sidx[o], mkeys);
+        IBL_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(ibl_mg_merge_new_kernel, dim3(nb_new), dim3(256), 0, s, P, order, nkeys, (int)n_new, g->v.ukeys, g->v.ustart,
+                       g->v.n_cells, (int)n_old, dst, g->sidx[o], mkeys);
+    IBL_LAUNCH_CHECK();
+    return mg_cells_table(g, n, mkeys, head, hscan, failed, tmp, t2, reserve_points, s, who);
+}
+
+// The compaction of a removal: flags the n resident slots whose original index lies outside the R uploaded ranges (`ranges` = rbeg |
+// rend | rcum), scans the flags and moves the n_keep kept points, their renumbered indices and their keys into the other buffer.
+static int mg_remove_compact(ibl_memgrid* g, int64_t n, int64_t n_keep, const int* ranges, int R, int* keep, int* kscan,
+                             unsigned long long* mkeys, unsigned char* tmp, size_t tmp_bytes, hipStream_t s) {
+    const int o = 1 - g->cur;
+    const int *rbeg = ranges, *rend = ranges + R, *rcum = ranges + 2 * (size_t)R;
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(ibl_mg_remove_flag_kernel, dim3(nb), dim3(256), 0, s, g->sidx[g->cur], n, rbeg, rend, rcum, R, keep);
+    IBL_LAUNCH_CHECK();
+    IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, keep, kscan, (int)n, s));
+    hipLaunchKernelGGL(ibl_mg_remove_scatter_kernel, dim3(nb), dim3(256), 0, s, g->v.sorted, g->sidx[g->cur], n, g->v.inv, rbeg, rend, rcum, R,
+                       keep, kscan, n_keep, g->buf[o], g->sidx[o], mkeys);
+    IBL_LAUNCH_CHECK();
+    return IBL_OK;
+}
+
 extern "C" int ibl_memgrid_destroy(ibl_memgrid* g) {
     if (!g) return IBL_OK;
-    (void)hipFree(g->buf[0]); (void)hipFree(g->buf[1]); (void)hipFree(g->v.ukeys); (void)hipFree(g->v.ustart);
+    (void)hipFree(g->buf[0]); (void)hipFree(g->buf[1]); (void)hipFree(g->sidx[0]); (void)hipFree(g->sidx[1]); (void)hipFree(g->v.ukeys); (void)hipFree(g->v.ustart);
     (void)hipFree(g->v.tkeys); (void)hipFree(g->v.tvals);
     delete g;
     return IBL_OK;
@@ -249,6 +349,7 @@ static int mg_build(ibl_reg_ctx* ctx, const float* mem_pts4, int64_t n, double c
     g->cur = 1;                                                                                          // the merge writes buf[0]
     IBL_HIP_CHECK(hipMalloc(&g->buf[0], sizeof(float4) * (size_t)(n + reserve_points)));
     g->buf_cap[0] = n + reserve_points;
+    if (!fixed) IBL_HIP_CHECK(hipMalloc(&g->sidx[0], sizeof(int) * (size_t)(n + reserve_points)));
     IBL_HIP_CHECK(hipMalloc(&g->v.ustart, sizeof(int)));
     IBL_HIP_CHECK(hipMemsetAsync(g->v.ustart, 0, sizeof(int), s));
     const int st = mg_merge(ctx, g.get(), reinterpret_cast<const float4*>(mem_pts4), n, reserve_points, s, who);
@@ -271,6 +372,72 @@ extern "C" int ibl_memgrid_append(ibl_reg_ctx* ctx, ibl_memgrid* g, const float*
     if (n_new == 0) return IBL_OK;
     if (g->v.n + n_new > 0x7FFFFFF0ll) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_append: more than 0x7FFFFFF0 points");
     return mg_merge(ctx, g, reinterpret_cast<const float4*>(new_pts4), n_new, 0, (hipStream_t)stream, "ibl_memgrid_append");
+}
+
+// Removes the points whose ORIGINAL indices lie in the given ranges: one stable compaction of the cell-ordered points into the other
+// point buffer -- no sort.  The resident order is (cell, original index); dropping points from it leaves the kept points in (cell,
+// index) order, and renumbering them by the count of removed points below is monotone, so the result is the order the build gives the
+// kept points alone.  Cells and table then follow as after a merge.  Traffic per resident point: 36 B for points and indices (16 + 4
+// read, 16 + 4 written when kept) and ~40 B for flags, keys, head flags and their scans.  Scratch (arena, released on return): 8 B per
+// resident point + 16 B per kept point + the scan's.  Everything is checked on the host before the first launch.
+extern "C" int ibl_memgrid_remove(ibl_reg_ctx* ctx, ibl_memgrid* g, const int64_t* range_begin, const int64_t* range_end, int n_ranges,
+                                  void* stream) {
+    if (!ctx || !g || n_ranges < 0 || (n_ranges > 0 && (!range_begin || !range_end)))
+        return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_remove: bad argument");
+    if (g->fixed) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_remove: a grid built with live = 0 is immutable (build it with live = 1)");
+    if (n_ranges == 0) return IBL_OK;
+    const int64_t n = g->v.n;
+    const int R = n_ranges;
+    std::vector<int> h(3 * (size_t)R);              // rbeg | rend | rcum
+    int64_t removed = 0, prev_end = 0;
+    for (int r = 0; r < R; ++r) {
+        if (range_begin[r] < prev_end || range_end[r] <= range_begin[r] || range_end[r] > n)
+            return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_remove: range %d [%lld, %lld) is empty, out of order, overlaps the one before or "
+                                 "passes the grid's %lld points", r, (long long)range_begin[r], (long long)range_end[r], (long long)n);
+        prev_end = range_end[r];
+        removed += range_end[r] - range_begin[r];
+        h[r] = (int)range_begin[r]; h[R + r] = (int)range_end[r]; h[2 * (size_t)R + r] = (int)removed;
+    }
+    if (removed >= n) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_remove: the ranges cover every point (a grid is never empty)");
+    const int64_t n_keep = n - removed;
+    hipStream_t s = (hipStream_t)stream;
+    ArenaMark scratch(ctx);
+    int *ranges, *keep, *kscan, *head, *hscan, *failed; unsigned long long* mkeys; unsigned char* tmp;
+    IBL_ARENA(ranges, int, 3 * (int64_t)R);
+    IBL_ARENA(keep, int, n + 1);
+    IBL_ARENA(kscan, int, n + 1);
+    IBL_ARENA(mkeys, unsigned long long, n_keep);
+    IBL_ARENA(head, int, n_keep + 1);
+    IBL_ARENA(hscan, int, n_keep + 1);
+    IBL_ARENA(failed, int, 1);
+    size_t t1 = 0, t2 = 0;
+    IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, keep, kscan, (int)n, s));
+    IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, head, hscan, (int)n_keep, s));
+    IBL_ARENA(tmp, unsigned char, (int64_t)std::max(t1, t2) + 256);
+    // The other half of the ping-pong pair becomes the current one: it is brought to the current half's capacity first (there is none
+    // before the first append, and it lags one growth behind after an append that grew), so that the capacity the grid reports never
+    // shrinks and what was freed is headroom.
+    const int o = 1 - g->cur;
+    if (g->buf_cap[o] < g->buf_cap[g->cur]) {
+        const int st = mg_alloc_other(g, g->buf_cap[g->cur], s, "ibl_memgrid_remove");
+        if (st != IBL_OK) return st;
+    }
+    int st = ibl_stage_upload(ctx, ranges, h.data(), (int64_t)(sizeof(int) * h.size()), s);
+    if (st == IBL_OK) st = mg_remove_compact(g, n, n_keep, ranges, R, keep, kscan, mkeys, tmp, t1, s);
+    if (st == IBL_OK) st = mg_cells_table(g, n_keep, mkeys, head, hscan, failed, tmp, t2, 0, s, "ibl_memgrid_remove");
+    if (st != IBL_OK) (void)hipStreamSynchronize(s);        // (mg_cells_table has synchronised when it succeeds)
+    ibl_stage_reset(ctx);                                   // the pinned staging of the ranges is recycled by the next call
+    return st;
+}
+
+extern "C" int ibl_memgrid_export(const ibl_memgrid* g, float* sorted_out, uint64_t* ukeys_out, int32_t* ustart_out, void* stream) {
+    if (!g) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_export: grid is null");
+    hipStream_t s = (hipStream_t)stream;
+    if (sorted_out) IBL_HIP_CHECK(hipMemcpyAsync(sorted_out, g->v.sorted, sizeof(float4) * (size_t)g->v.n, hipMemcpyDeviceToDevice, s));
+    if (ukeys_out)
+        IBL_HIP_CHECK(hipMemcpyAsync(ukeys_out, g->v.ukeys, sizeof(unsigned long long) * (size_t)g->v.n_cells, hipMemcpyDeviceToDevice, s));
+    if (ustart_out) IBL_HIP_CHECK(hipMemcpyAsync(ustart_out, g->v.ustart, sizeof(int) * ((size_t)g->v.n_cells + 1), hipMemcpyDeviceToDevice, s));
+    return IBL_OK;
 }
 
 extern "C" int ibl_memgrid_info(const ibl_memgrid* g, int64_t* n, int32_t* n_cells, int64_t* table_slots, int64_t* point_capacity,

@@ -29,8 +29,8 @@ from scipy.spatial.transform import Rotation
 from . import match
 from .assign import K_HI, K_LO, assign_batch, assign_candidates
 from .parallel import ShardExchange, shard_range, sharded_candidates
-from .registration import (CloudBatch, InstanceFeatures, MemGrid, RegContext, evaluate_batch, evaluate_points, grow_rows,
-                           instance_features_batch, radius_outlier_batch, register_batch, register_evaluate_batch)
+from .registration import (CloudBatch, InstanceFeatures, MemGrid, RegContext, compact_rows, compact_scratch, evaluate_batch, evaluate_points, grow_rows,
+                           instance_features_batch, kept_runs, merged_ranges, radius_outlier_batch, register_batch, register_evaluate_batch)
 
 IBL_ST_GRID_OVERFLOW = 1          # ibl_reg_ctx_status bits (include/ibloc.h)
 
@@ -50,7 +50,8 @@ class MemoryShard:
     instance indices everywhere else remain global.  The clouds stay replicated unless shard_clouds=True: then this rank also keeps
     only the clouds, cached features and evaluation grid of [lo, hi) (`clouds` / `colors` / `intensities` may be the full lists or just
     that range), registration jobs are routed between the ranks and the evaluation is reduced over them (routing.py).
-    live=True (unsharded memories): the memory can grow while it is resident -- `append` adds instances without rebuilding anything.
+    live=True (unsharded memories): the memory can grow and shrink while it is resident -- `append` adds instances and `remove` takes
+    instances out without rebuilding anything.
     The embeddings, clouds and instance features then sit in buffers with room for reserve_points further points (default: an
     eighth of the memory + 65 536) and reserve_rows further embedding rows, and the spatial hash accepts appends
     (ibl_memgrid_build with live = 1).  Without live there is no headroom anywhere.  Everything computed is the same either way."""
@@ -158,6 +159,48 @@ class MemoryShard:
         self.emb_offsets_host = np.concatenate([self.emb_offsets_host, self.emb_offsets_host[-1] + counts]).astype(np.int32)
         self.emb_offsets = torch.from_numpy(self.emb_offsets_host).to(self.device)
         self.M += len(embs)
+        self.hi = self.M
+        torch.cuda.synchronize(self.device)
+
+    def remove(self, instances):
+        """Takes the instances `instances` (any iterable of distinct indices, not all of them) out of a live memory; the later
+        instances move down and take the lower indices, as `del memory[i]` moves them.  The spatial hash drops their points by one
+        compaction (ibl_memgrid_remove: no sort), the clouds, every resident feature set and the embedding rows are compacted in
+        place in their buffers (registration.compact_rows) -- nothing is uploaded, normalised, sorted or recomputed, and the
+        InstanceFeatures objects stay the same objects.  The state afterwards is, array for array, that of a MemoryShard constructed
+        from the kept instances; the buffers keep their sizes, the freed room is headroom.  Synchronises the device first: no
+        localisation may be in flight (LocaliseEngine keeps nothing sized by M for an unsharded memory; it reads M on every call).
+        Raises ValueError, before anything is touched, for a sharded or non-live memory, an index out of range, a duplicate index or
+        a request to remove every instance.  An empty list is a no-op."""
+        if self.shard is not None:
+            raise ValueError("MemoryShard.remove: sharded memories cannot shrink while resident")
+        if not self.live:
+            raise ValueError("MemoryShard.remove: construct the shard with live=True")
+        given = [int(i) for i in instances]
+        idx = sorted(set(given))
+        if len(idx) != len(given):
+            raise ValueError("MemoryShard.remove: an instance is named twice")
+        if idx and (idx[0] < 0 or idx[-1] >= self.M):
+            raise ValueError(f"MemoryShard.remove: instance index out of range (the memory holds {self.M})")
+        if len(idx) == self.M and idx:
+            raise ValueError("MemoryShard.remove: a resident memory is never empty (drop the shard instead)")
+        if not idx:
+            return
+        torch.cuda.synchronize(self.device)
+        # one scratch chunk for every row compaction below, allocated before anything is changed (132 B: the widest row, fpfh)
+        scratch = compact_scratch(self.device, max(self.mem_emb.numel() * 4, 0 if self.clouds is None else self.clouds.n * 132))
+        if self.clouds is not None:
+            # the grid first: the only step that can fail in the library, and it leaves the grid as it was when it does
+            self.grid.remove(merged_ranges(self.clouds.seg_off_host, idx))
+            ranges = self.clouds.remove(idx, scratch=scratch)
+            for feat in self._features.values():
+                feat.remove(idx, ranges, scratch=scratch)
+        rows = self.mem_emb.shape[0]
+        self.mem_emb = compact_rows(self._emb_buf, rows, kept_runs(rows, merged_ranges(self.emb_offsets_host, idx)), scratch=scratch)
+        counts = np.delete(np.diff(self.emb_offsets_host), idx)
+        self.emb_offsets_host = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        self.emb_offsets = torch.from_numpy(self.emb_offsets_host).to(self.device)
+        self.M -= len(idx)
         self.hi = self.M
         torch.cuda.synchronize(self.device)
 

@@ -113,6 +113,29 @@ class ObjectMemory():
             self._engine = None          # whatever state the shard is in, the next query rebuilds it from self.memory
             raise
 
+    def remove_objects(self, indices):
+        """Deletes the entries `indices` (distinct positions in self.memory) -- objects that were carried away or merged elsewhere.
+        The remaining ObjectInfos keep their ids, as the reference's own `self.memory.remove(info)` leaves them.  A resident live
+        memory drops the instances in place (MemoryShard.remove) and the engine stays; otherwise, or when the shard raises, the
+        engine is dropped and the next query rebuilds it from self.memory."""
+        given = [int(i) for i in indices]
+        idx = sorted(set(given))
+        if len(idx) != len(given) or (idx and (idx[0] < 0 or idx[-1] >= len(self.memory))):
+            raise ValueError(f"remove_objects: distinct indices below {len(self.memory)} expected, got {given}")
+        if not idx:
+            return
+        resident = self._engine is not None and self._shard.M == len(self.memory)
+        for i in reversed(idx):
+            del self.memory[i]
+        if not resident or not self.live_memory or not self._shard.live or not self.memory:
+            self._engine = None
+            return
+        try:
+            self._shard.remove(idx)
+        except Exception:
+            self._engine = None          # whatever state the shard is in, the next query rebuilds it from self.memory
+            raise
+
     # ---- memory build (object_memory.py:163-256) ----------------------------------------------------------
     def _log(self, *a):
         if self.log_enabled:

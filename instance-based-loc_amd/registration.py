@@ -82,6 +82,77 @@ def grow_rows(buf: torch.Tensor, n_used: int, rows: torch.Tensor):
     return buf, buf[:n]
 
 
+COMPACT_SCRATCH_BYTES = 64 << 20
+
+
+def kept_runs(n, removed):
+    """the runs [(begin, end), ...] of 0 .. n - 1 that the ascending, disjoint half-open ranges `removed` leave"""
+    runs, at = [], 0
+    for b, e in removed:
+        if b > at:
+            runs.append((at, b))
+        at = e
+    if at < n:
+        runs.append((at, n))
+    return runs
+
+
+def merged_ranges(off, segments):
+    """the row ranges off[s] .. off[s + 1] of the ascending `segments`, neighbours joined and empty ones left out"""
+    out = []
+    for s in segments:
+        b, e = int(off[s]), int(off[s + 1])
+        if e == b:
+            continue
+        if out and out[-1][1] == b:
+            out[-1] = (out[-1][0], e)
+        else:
+            out.append((b, e))
+    return out
+
+
+def compact_scratch(device, bytes_needed=COMPACT_SCRATCH_BYTES):
+    """the scratch chunk of `compact_rows` as a tensor of its own (at most COMPACT_SCRATCH_BYTES): allocated once, before anything is
+    changed, by a caller that compacts several buffers in a row"""
+    return torch.empty((max(1, min(int(bytes_needed), COMPACT_SCRATCH_BYTES)),), dtype=torch.uint8, device=device)
+
+
+def compact_rows(buf: torch.Tensor, n_used: int, keep_runs, scratch_bytes=COMPACT_SCRATCH_BYTES, scratch=None):
+    """Rows taken out of a device buffer (live memory): the ascending, disjoint row runs `keep_runs` = [(begin, end), ...] of the
+    first n_used rows move to the front of `buf` IN PLACE -- a resident feature set is tens of GB and is never duplicated.  A run that
+    moves down by at least its length is one copy.  A run that overlaps its destination goes in ascending pieces: of the shift's
+    length, copied directly, when the shift is at least the scratch chunk, else through a scratch chunk of scratch_bytes (source
+    piece -> scratch -> destination), so the number of copies follows the chunk, never a small shift.  No copy is between overlapping
+    views.  Everything is queued on the current stream.  scratch: a `compact_scratch` tensor to use (its size then stands for
+    scratch_bytes) instead of allocating one when a run needs it.  Returns the view of the kept rows."""
+    row_bytes = buf.element_size() * int(np.prod(buf.shape[1:], dtype=np.int64))
+    if scratch is not None:
+        scratch_bytes = scratch.numel()
+    chunk = max(1, min(int(scratch_bytes) // max(row_bytes, 1), n_used))
+    if scratch is not None:             # the caller's bytes as rows of this buffer (none if not even one row fits: allocated below)
+        scratch = scratch[:chunk * row_bytes].view(buf.dtype).view((chunk,) + tuple(buf.shape[1:])) if scratch.numel() >= row_bytes else None
+    at = 0
+    for b, e in keep_runs:
+        assert at <= b < e <= n_used
+        shift, length = b - at, e - b
+        if shift >= length:
+            buf[at:at + length].copy_(buf[b:e])
+        elif shift > 0:
+            direct = shift >= chunk                      # source and destination of a piece no longer than the shift are disjoint
+            piece = shift if direct else chunk
+            if not direct and scratch is None:
+                scratch = torch.empty((chunk,) + tuple(buf.shape[1:]), dtype=buf.dtype, device=buf.device)
+            for o in range(0, length, piece):
+                c = min(piece, length - o)
+                if direct:
+                    buf[at + o:at + o + c].copy_(buf[b + o:b + o + c])
+                else:
+                    scratch[:c].copy_(buf[b + o:b + o + c])
+                    buf[at + o:at + o + c].copy_(scratch[:c])
+        at += length
+    return buf[:at]
+
+
 class CloudBatch:
     """Packed clouds on the device."""
 
@@ -141,6 +212,20 @@ class CloudBatch:
         self.seg_off_host = np.concatenate([self.seg_off_host, self.seg_off_host[-1] + new.seg_off_host[1:]]).astype(np.int32)
         self.seg_off = torch.from_numpy(self.seg_off_host).to(self.pts4.device)
         return new
+
+    def remove(self, segments, scratch=None):
+        """Takes the clouds `segments` (ascending, distinct segment indices; not all of them) out of the batch: the later clouds move
+        down in the backing buffer (`compact_rows`, in place) and take the lower segment indices.  `pts4` and `seg_off` are NEW tensor
+        objects afterwards.  Returns the point ranges [(begin, end), ...] that were removed, in the numbering before the call
+        (neighbouring clouds joined) -- what `MemGrid.remove` and `InstanceFeatures.remove` take.  scratch: see `compact_rows`."""
+        segments = [int(s) for s in segments]
+        assert all(a < b for a, b in zip([-1] + segments, segments + [self.n_seg])) and len(segments) < self.n_seg
+        ranges = merged_ranges(self.seg_off_host, segments)
+        self.pts4 = compact_rows(self._buf, self.n, kept_runs(self.n, ranges), scratch=scratch)
+        sizes = np.delete(np.diff(self.seg_off_host), segments)
+        self.seg_off_host = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+        self.seg_off = torch.from_numpy(self.seg_off_host).to(self.pts4.device)
+        return ranges
 
 
 def unproject_masks(ctx: RegContext, depth: torch.Tensor, rgb: torch.Tensor, masks: torch.Tensor, fx: float, fy: float,
@@ -261,6 +346,23 @@ class InstanceFeatures:
         self.bbox = np.ascontiguousarray(np.concatenate([self.bbox[:self.n_seg], new.bbox[:new.n_seg]]))
         self.n += new.n
         self.n_seg += new.n_seg
+
+    def remove(self, segments, point_ranges, scratch=None):
+        """Takes the features of the clouds `segments` (ascending, distinct) out: `point_ranges` are the point ranges of those clouds
+        as `CloudBatch.remove` returns them.  Every device array that is present is compacted in its backing buffer
+        (`compact_rows`: in place, nothing is duplicated or recomputed -- a feature depends on its own cloud only), the bounding-box
+        rows of the clouds are dropped.  scratch: see `compact_rows`."""
+        if self.n is None:
+            raise ValueError("InstanceFeatures.remove: point counts unknown (features not made by instance_features_batch)")
+        runs = kept_runs(self.n, point_ranges)
+        for name in self.DEVICE_ARRAYS:
+            cur = getattr(self, name)
+            if cur is not None:
+                self._bufs[name] = self._bufs.get(name, cur)
+                setattr(self, name, compact_rows(self._bufs[name], self.n, runs, scratch=scratch))
+        self.bbox = np.ascontiguousarray(np.delete(self.bbox[:self.n_seg], list(segments), axis=0))
+        self.n = sum(e - b for b, e in runs)
+        self.n_seg -= len(segments)
 
     def as_struct(self):
         return _FeatStruct(self.normals.data_ptr(), self.fpfh.data_ptr(), self.fpfh_split.data_ptr() if self.fpfh_split is not None else None,
@@ -394,13 +496,14 @@ def register_evaluate_batch(ctx: RegContext, det: CloudBatch, q_per_frame, assns
 class MemGrid:
     """Spatial hash over all memory points.  It owns its device memory: `close` frees it, and nothing of it lives in the context
     arena (RegContext.reset leaves it valid).  Built once and immutable unless live=True: then the grid has room for reserve_points
-    further points and `append` merges further points into it."""
+    further points, `append` merges further points into it and `remove` takes points out."""
 
     def __init__(self, ctx: RegContext, mem_pts4: torch.Tensor, cell=0.04, live=False, reserve_points=0):
         assert mem_pts4.is_cuda and mem_pts4.dtype == torch.float32 and mem_pts4.shape[1] == 4 and mem_pts4.is_contiguous()
         self.ctx = ctx
         self.cell = cell
         self.live = bool(live)
+        self.device = mem_pts4.device
         self._h = C.c_void_p()
         st = _lib.lib.ibl_memgrid_build(ctx.handle, mem_pts4.data_ptr(), mem_pts4.shape[0], float(cell), int(self.live),
                                         int(reserve_points) if self.live else 0, C.byref(self._h), _stream())
@@ -413,6 +516,28 @@ class MemGrid:
         assert pts4_new.is_cuda and pts4_new.dtype == torch.float32 and pts4_new.dim() == 2 and pts4_new.shape[1] == 4 and pts4_new.is_contiguous()
         st = _lib.lib.ibl_memgrid_append(self.ctx.handle, self._h, pts4_new.data_ptr(), pts4_new.shape[0], _stream())
         _lib.check(st, "ibl_memgrid_append")
+
+    def remove(self, ranges):
+        """Takes the points whose original indices (position in the array the grid was built from, plus everything appended since) lie
+        in the half-open `ranges` = [(begin, end), ...] -- ascending, disjoint, non-empty, not everything -- out of a live grid:
+        afterwards it equals the grid built from the kept points, which count as renumbered from 0.  Synchronises the current stream;
+        the rule for other streams is `append`'s.  Whatever the library refuses (IblError) leaves the grid unchanged."""
+        rb = np.ascontiguousarray([r[0] for r in ranges], dtype=np.int64)
+        re = np.ascontiguousarray([r[1] for r in ranges], dtype=np.int64)
+        st = _lib.lib.ibl_memgrid_remove(self.ctx.handle, self._h, rb.ctypes.data, re.ctypes.data, len(rb), _stream())
+        _lib.check(st, "ibl_memgrid_remove")
+
+    def export(self):
+        """copies of the grid's arrays as device tensors: dict(sorted (n, 4) float32 -- the points in cell order --, ukeys (n_cells,)
+        int64 holding the unsigned 64-bit cell keys, ustart (n_cells + 1,) int32)"""
+        i = self.info()
+        dev = self.device
+        out = dict(sorted=torch.empty((i["n"], 4), dtype=torch.float32, device=dev),
+                   ukeys=torch.empty((i["n_cells"],), dtype=torch.int64, device=dev),
+                   ustart=torch.empty((i["n_cells"] + 1,), dtype=torch.int32, device=dev))
+        st = _lib.lib.ibl_memgrid_export(self._h, out["sorted"].data_ptr(), out["ukeys"].data_ptr(), out["ustart"].data_ptr(), _stream())
+        _lib.check(st, "ibl_memgrid_export")
+        return out
 
     def info(self):
         """dict(n, n_cells, table_slots, point_capacity, ustart_end = ustart[n_cells]) of the grid as it stands"""

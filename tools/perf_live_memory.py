@@ -1,5 +1,5 @@
-"""Cost of adding an object to a resident memory: MemoryShard.append on a live memory against the rebuild it replaces, on a synthetic
-memory of N instances x 5 000 points (ibloc_amd.synth.SynthWorld).
+"""Cost of adding an object to a resident memory, and of taking one out: MemoryShard.append / MemoryShard.remove on a live memory
+against the rebuild they replace, on a synthetic memory of N instances x 5 000 points (ibloc_amd.synth.SynthWorld).
 
     python tools/perf_live_memory.py N [--points P] [--seed S] [--compact] [--arena-gb G]
 
@@ -7,7 +7,10 @@ Prints one JSON line: rebuild_s = rebuild_shard_s + rebuild_features_s, the time
 live memory (MemoryShard construction from host arrays + features(0.05, 0.4), device synchronised), with rebuild_host_s, the part of it
 that is host packing and the host-to-device copy of the clouds (CloudBatch.from_numpy alone); live_build_s, the same construction with
 live=True; append_1_s / append_32_s, MemoryShard.append of 1 and of 32 instances (median of 5 after a warm-up append, device
-synchronised), with append_*_grid_s, the ibl_memgrid_append part of those appends, and append_*_all the single times.  Needs a GPU."""
+synchronised), with append_*_grid_s, the ibl_memgrid_append part of those appends, and append_*_all the single times; remove_1_s /
+remove_32_s, MemoryShard.remove of 1 and of 32 neighbouring instances from the middle of the same memory (median of 5 after a warm-up
+removal), with remove_*_grid_s, the ibl_memgrid_remove part, and remove_*_all; grid_rebuild_s, a MemGrid built from the kept points
+(median of 5 after a warm-up): the re-sort the removal avoids.  Without a live memory a removal costs rebuild_s.  Needs a GPU."""
 import argparse
 import json
 import os
@@ -30,7 +33,7 @@ def main():
 
     import torch
     from ibloc_amd.engine import MemoryShard, intensity_from_colors
-    from ibloc_amd.registration import CloudBatch, RegContext
+    from ibloc_amd.registration import CloudBatch, MemGrid, RegContext
     from ibloc_amd.synth import SynthWorld
     if not torch.cuda.is_available():
         raise SystemExit("perf_live_memory.py measures device work: no GPU here")
@@ -96,8 +99,43 @@ def main():
         out[f"append_{k}_all"] = times
         out[f"append_{k}_grid_s"] = float(np.median(grid_times[-5:]))
     out["resident_points"] = m.clouds.n
+    grid_times = []
+    grid_remove = m.grid.remove
+
+    def timed_grid_remove(ranges):
+        sync()
+        t0 = time.perf_counter()
+        grid_remove(ranges)
+        sync()
+        grid_times.append(time.perf_counter() - t0)
+
+    m.grid.remove = timed_grid_remove
+    for k in (1, 32):
+        times = []
+        for _ in range(6):
+            first = m.M // 2
+            sync()
+            t = time.perf_counter()
+            m.remove(range(first, first + k))
+            sync()
+            times.append(time.perf_counter() - t)
+        out[f"remove_{k}_s"] = float(np.median(times[1:]))
+        out[f"remove_{k}_all"] = times
+        out[f"remove_{k}_grid_s"] = float(np.median(grid_times[-5:]))
+    times = []
+    for _ in range(6):
+        sync()
+        t = time.perf_counter()
+        g = MemGrid(ctx, m.clouds.pts4, cell=2 * m.eval_threshold)
+        sync()
+        times.append(time.perf_counter() - t)
+        g.close()
+    out["grid_rebuild_s"] = float(np.median(times[1:]))
+    out["points_after_removals"] = m.clouds.n
     out["grid"] = m.grid.info()
     out["rebuild_over_append_1"] = out["rebuild_s"] / out["append_1_s"]
+    out["rebuild_over_remove_1"] = out["rebuild_s"] / out["remove_1_s"]
+    out["grid_rebuild_over_grid_remove_1"] = out["grid_rebuild_s"] / out["remove_1_grid_s"]
     m.close()
     ctx.close()
     out["device"] = torch.cuda.get_device_name(0)
