@@ -20,7 +20,7 @@
  *     never synchronise.  Functions that return HOST results synchronise the stream -- how often is stated per function:
  *     ibl_radius_outlier_batch 1 (grid table size), ibl_instance_features_batch 2 (bounding boxes; end),
  *     ibl_register_jobs 2-4 (one per group of RANSAC rounds -- most calls need one -- plus the results; one more when
- *     instances of a job lie within the influence radius of each other), ibl_evaluate_batch 1, ibl_memgrid_build / _append / _remove 2
+ *     instances of a job lie within the influence radius of each other), ibl_evaluate_batch 1, ibl_memgrid_build / _append / _remove / _replace 2
  *     (cell count; end; one more when the call has to reallocate the other point buffer).  Plan tables are staged through pinned host memory of the registration context, so uploads never wait.
  *   - plain C types only; no torch types in any signature.
  */
@@ -650,6 +650,35 @@ int ibl_memgrid_remove(ibl_reg_ctx* ctx, ibl_memgrid* grid, const int64_t* range
                        void* stream);
 int ibl_memgrid_export(const ibl_memgrid* grid, float* sorted_out /* [dev] n x 4 */, uint64_t* ukeys_out /* [dev] n_cells */,
                        int32_t* ustart_out /* [dev] n_cells + 1 */, void* stream);
+
+/* Live memory, in place: ibl_memgrid_replace changes points that stay where they are in the index space (an instance seen again,
+ * two fragments joined, a cloud downsampled) in a grid built with live != 0.
+ *   range_begin / range_end [HOST] n_ranges entries: half-open ranges over the ORIGINAL point indices, as for ibl_memgrid_remove:
+ *   ascending and disjoint (they may touch).  Range r is replaced by the next new_count[r] rows of new_pts4 ([HOST] n_ranges counts;
+ *   [dev] sum(new_count) x 4 floats).  A range may be empty (begin == end, begin == n allowed): a pure insertion in front of index
+ *   `begin`, which needs new_count > 0.  new_count[r] may be 0: a pure removal.  Two ranges never begin at the same index, and at
+ *   least one point must remain.
+ *   Afterwards the grid holds what ibl_memgrid_build returns for the spliced point sequence, array for array: sorted, ukeys, ustart,
+ *   n, n_cells and the table dimension of the build's rule; the per-slot original indices are renumbered to the spliced sequence.
+ *   One empty range at n is ibl_memgrid_append, counts that are all 0 are ibl_memgrid_remove.
+ *   The merge of an append relies on "old before new within a cell" -- appended points have the highest indices.  Points spliced
+ *   into the middle interleave, inside a cell, with points of lower and of higher index, so both sides look their place up: a kept
+ *   old point with index idx stands behind its kept predecessors (the scan of the removal's flags), the new points of lower cells
+ *   and the new points of its own cell whose range begins at or below idx (a search in the stable sort's order of the new
+ *   points, which ascends inside a cell); a sorted new point j of range r stands behind j new points and the kept old points in
+ *   front of the first slot of its cell whose index is not below range_begin[r] (a search in the cell's indices, which ascend).
+ *   No sort of resident points, no atomics, bounded binary searches only; cell arrays and table are rebuilt as after an append.
+ *   Traffic: that of a removal per resident point, 56 B per new point.  Scratch from ctx's arena, released on return: 8 bytes per
+ *   resident point + 16 per point of the result + 24 per new point + 16 per range + the sort's.
+ *   Capacities never shrink: the other half of the ping-pong pair is brought to the current half's size, or grown by 1.5 when the
+ *   result no longer fits.
+ *   n_ranges == 0 is a no-op (IBL_OK).  IBL_ERR_ARG, decided on the host before anything is launched and leaving the grid as it
+ *   was: a grid built with live == 0; ranges that are unsorted, overlapping, reversed or pass n; two ranges with the same begin; an
+ *   empty range without new points; a negative count; nothing left; more than 0x7FFFFFF0 points; null pointers.  The arena error
+ *   and an allocation error leave the grid as it was, too: nothing of it is overwritten before the new state is complete.
+ *   Synchronisation: as ibl_memgrid_append and ibl_memgrid_remove. */
+int ibl_memgrid_replace(ibl_reg_ctx* ctx, ibl_memgrid* grid, const int64_t* range_begin, const int64_t* range_end,
+                        const int64_t* new_count, const float* new_pts4, int n_ranges, void* stream);
 
 /* evaluate_transform(all_detected_pcd, all_memory_pcd, T) for n_jobs candidates: job j transforms the detected
  * points [job_begin[j], job_end[j]) of det_pts4 [dev] by T_global[j] (host, 16 doubles row-major) and looks for

@@ -72,6 +72,7 @@ _SIGS = {
     "ibl_memgrid_append": (C.c_int, [vp, vp, vp, C.c_int64, vp]),
     "ibl_memgrid_info": (C.c_int, [vp, C.POINTER(C.c_int64), c_i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_i32p, vp]),
     "ibl_memgrid_remove": (C.c_int, [vp, vp, vp, vp, C.c_int, vp]),
+    "ibl_memgrid_replace": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "ibl_memgrid_export": (C.c_int, [vp, vp, vp, vp, vp]),
     "ibl_evaluate_batch": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp]),
     "ibl_register_evaluate_batch": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_double, C.c_int, C.c_double, C.c_int,

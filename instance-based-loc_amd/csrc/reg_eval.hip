@@ -37,10 +37,10 @@ struct MemGridView {
 // and the new points into buf[1 - cur], which the first append that needs it allocates), cell arrays and a table with their own
 // capacities.  v.sorted is buf[cur].  A live grid also remembers, per sorted slot, the original index of the point that sits there
 // (sidx, 4 bytes per point, allocated, ping-ponged and grown with the point buffers): ibl_memgrid_remove finds a removed instance's
-// slots by it.  Nothing on the query path reads it; an immutable grid has none.
+// slots by it, ibl_memgrid_replace also the place of the new points inside a cell.  Nothing on the query path reads it; an immutable grid has none.
 struct ibl_memgrid {
     MemGridView v = {};
-    int fixed = 0;                      // 1: made by ibl_memgrid_build with live = 0 -- immutable, ibl_memgrid_append / _remove refuse it
+    int fixed = 0;                      // 1: made by ibl_memgrid_build with live = 0 -- immutable, ibl_memgrid_append / _remove / _replace refuse it
     float4* buf[2] = {nullptr, nullptr};
     int* sidx[2] = {nullptr, nullptr};  // original index of the point in slot i of buf[.] (live grids only)
     int64_t buf_cap[2] = {0, 0};        // points
@@ -121,29 +121,27 @@ __global__ __launch_bounds__(256) void ibl_mg_merge_new_kernel(const float4* __r
 }
 
 // ---- removal: a stable compaction of the cell-ordered points (ibl_memgrid_remove) ------------------------------------------------
-// The removed points are given as R ascending, disjoint, non-empty ranges of original indices: rbeg / rend, and rcum[r] = the
-// points in the ranges 0 .. r.  For original index `idx`: is it kept, and how many removed points lie below it.  One binary
-// search, bounded by R (a few thousand entries at most: they stay in cache).
-__device__ __forceinline__ bool mg_kept(const int* __restrict__ rbeg, const int* __restrict__ rend, const int* __restrict__ rcum, int R,
-                                        int idx, int* below) {
+// The removed points are given as R ascending, disjoint ranges of original indices: rbeg / rend, and rcum[r] = the points in the
+// ranges 0 .. r (a replacement's ranges may be empty; a removal's are not).  For original index `idx`: is it kept, and *nr = the
+// number of ranges that begin at or below it -- rcum[*nr - 1] removed points lie below a kept point.  One binary search, bounded by
+// R (a few thousand entries at most: they stay in cache).
+__device__ __forceinline__ bool mg_kept(const int* __restrict__ rbeg, const int* __restrict__ rend, int R, int idx, int* nr) {
     int lo = 0, hi = R;                             // lo = number of ranges that begin at or below idx
     while (lo < hi) {
         const int mid = lo + ((hi - lo) >> 1);
         if (rbeg[mid] <= idx) lo = mid + 1; else hi = mid;
     }
-    if (lo == 0) { *below = 0; return true; }
-    *below = rcum[lo - 1];                          // (of a kept point: every range that begins below it also ends below it)
-    return idx >= rend[lo - 1];
+    *nr = lo;
+    return lo == 0 || idx >= rend[lo - 1];          // (of a kept point: every range that begins at or below it ends at or below it)
 }
 
 // one thread per resident slot: 1 for a point that stays
 __global__ __launch_bounds__(256) void ibl_mg_remove_flag_kernel(const int* __restrict__ sidx, int64_t n, const int* __restrict__ rbeg,
-                                                                 const int* __restrict__ rend, const int* __restrict__ rcum, int R,
-                                                                 int* __restrict__ keep) {
+                                                                 const int* __restrict__ rend, int R, int* __restrict__ keep) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    int below;
-    keep[i] = mg_kept(rbeg, rend, rcum, R, sidx[i], &below) ? 1 : 0;
+    int nr;
+    keep[i] = mg_kept(rbeg, rend, R, sidx[i], &nr) ? 1 : 0;
 }
 
 // Kept slot i moves to keep_scan[i] (the exclusive sum of the flags) of the other point buffer: 16-byte load and store, its key
@@ -158,13 +156,84 @@ __global__ __launch_bounds__(256) void ibl_mg_remove_scatter_kernel(const float4
     if (i >= n || !keep[i]) return;
     const int64_t d = keep_scan[i];
     if (d < 0 || d >= n_keep) return;               // (cannot happen: the host counted n_keep from the same ranges)
-    int below;
+    int nr;
     const int idx = sidx_src[i];
-    mg_kept(rbeg, rend, rcum, R, idx, &below);
+    mg_kept(rbeg, rend, R, idx, &nr);
     const float4 p = src[i];
     dst[d] = p;
     mkeys[d] = mg_key((int)floorf(p.x * inv), (int)floorf(p.y * inv), (int)floorf(p.z * inv));
-    sidx_dst[d] = idx - below;
+    sidx_dst[d] = idx - (nr ? rcum[nr - 1] : 0);
+}
+
+// ---- replacement: points spliced into the middle of the index space (ibl_memgrid_replace) -------------------------------------------
+// The ranges of a replacement are those of a removal (rbeg / rend / rcum; empty ones allowed) with ncum[r] = the new points of the
+// ranges 0 .. r: the new points, in the order they are given, carry the concatenation indices c = 0 .. n_new - 1, those of range r
+// are ncum[r - 1] <= c < ncum[r].  In the spliced sequence an old point with original index idx stands behind the new points of
+// every range that begins at or below idx, a new point of range r behind the old points below rbeg[r] -- and that order, within
+// a cell, is the build's.
+
+// first index of the ascending vals[lo, hi) that is not below v
+__device__ __forceinline__ int mg_bound_int(const int* __restrict__ vals, int lo, int hi, int v) {
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (vals[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// Old side: kept slot i moves to keep_scan[i] (the kept points before it) + the new points of lower cells + the new points of its
+// own cell that precede it in the spliced sequence: those with c < ncum[nr - 1].  `order` ascends inside a run of equal new keys
+// (the sort is stable), so that count is one more bounded search.  16-byte load and store, the key for the cell boundaries.
+__global__ __launch_bounds__(256) void ibl_mg_replace_old_kernel(const float4* __restrict__ src, const int* __restrict__ sidx_src, int64_t n,
+                                                                 float inv, const int* __restrict__ rbeg, const int* __restrict__ rend,
+                                                                 const int* __restrict__ rcum, const int* __restrict__ ncum, int R,
+                                                                 const int* __restrict__ keep, const int* __restrict__ keep_scan,
+                                                                 const unsigned long long* __restrict__ nkeys, const int* __restrict__ order,
+                                                                 int n_new, int64_t n_out, float4* __restrict__ dst,
+                                                                 int* __restrict__ sidx_dst, unsigned long long* __restrict__ mkeys) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || !keep[i]) return;
+    int nr;
+    const int idx = sidx_src[i];
+    mg_kept(rbeg, rend, R, idx, &nr);
+    const int c_before = nr ? ncum[nr - 1] : 0;
+    const float4 p = src[i];
+    const unsigned long long k = mg_key((int)floorf(p.x * inv), (int)floorf(p.y * inv), (int)floorf(p.z * inv));
+    int64_t d = keep_scan[i];
+    if (n_new > 0) {
+        const int lo = mg_bound(nkeys, n_new, k, 0);
+        d += (lo < n_new && nkeys[lo] == k) ? mg_bound_int(order, lo, mg_bound(nkeys, n_new, k, 1), c_before) : lo;
+    }
+    if (d < 0 || d >= n_out) return;                // (cannot happen: the host counted n_out from the same ranges)
+    dst[d] = p;
+    mkeys[d] = k;
+    sidx_dst[d] = idx - (nr ? rcum[nr - 1] : 0) + c_before;
+}
+
+// New side: sorted new point j of range r moves up by the kept old points before it: those of lower cells and, inside its own cell
+// [s, e) of the old grid, those below rbeg[r] -- sidx ascends inside a cell, one bounded search; a cell the old grid does not have
+// begins where the next higher one does.  keep_scan has n + 1 entries (a position behind the last slot counts every kept point).
+__global__ __launch_bounds__(256) void ibl_mg_replace_new_kernel(const float4* __restrict__ pts, const int* __restrict__ order,
+                                                                 const unsigned long long* __restrict__ nkeys, int n_new,
+                                                                 const unsigned long long* __restrict__ ukeys, const int* __restrict__ ustart,
+                                                                 int n_cells, const int* __restrict__ sidx_src,
+                                                                 const int* __restrict__ keep_scan, const int* __restrict__ rbeg,
+                                                                 const int* __restrict__ rcum, const int* __restrict__ ncum, int R,
+                                                                 int64_t n_out, float4* __restrict__ dst, int* __restrict__ sidx_dst,
+                                                                 unsigned long long* __restrict__ mkeys) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n_new) return;
+    const unsigned long long k = nkeys[j];
+    const int c = order[j];
+    const int r = min(mg_bound_int(ncum, 0, R, c + 1), R - 1);      // the first range with ncum[r] > c (ranges without new points pass)
+    const int cell = mg_bound(ukeys, n_cells, k, 0);
+    int pos = ustart[cell];
+    if (cell < n_cells && ukeys[cell] == k) pos = mg_bound_int(sidx_src, pos, ustart[cell + 1], rbeg[r]);
+    const int64_t d = (int64_t)j + keep_scan[pos];
+    if (d < 0 || d >= n_out) return;                // (cannot happen, as above)
+    dst[d] = pts[c];
+    mkeys[d] = k;
+    sidx_dst[d] = rbeg[r] - (r ? rcum[r - 1] : 0) + c;
 }
 
 __global__ __launch_bounds__(256) void ibl_mg_merged_cells_kernel(const unsigned long long* __restrict__ mkeys, const int* __restrict__ head,
@@ -323,7 +392,7 @@ static int mg_remove_compact(ibl_memgrid* g, int64_t n, int64_t n_keep, const in
     const int o = 1 - g->cur;
     const int *rbeg = ranges, *rend = ranges + R, *rcum = ranges + 2 * (size_t)R;
     const unsigned nb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(ibl_mg_remove_flag_kernel, dim3(nb), dim3(256), 0, s, g->sidx[g->cur], n, rbeg, rend, rcum, R, keep);
+    hipLaunchKernelGGL(ibl_mg_remove_flag_kernel, dim3(nb), dim3(256), 0, s, g->sidx[g->cur], n, rbeg, rend, R, keep);
     IBL_LAUNCH_CHECK();
     IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, keep, kscan, (int)n, s));
     hipLaunchKernelGGL(ibl_mg_remove_scatter_kernel, dim3(nb), dim3(256), 0, s, g->v.sorted, g->sidx[g->cur], n, g->v.inv, rbeg, rend, rcum, R,
@@ -425,6 +494,101 @@ extern "C" int ibl_memgrid_remove(ibl_reg_ctx* ctx, ibl_memgrid* g, const int64_
     int st = ibl_stage_upload(ctx, ranges, h.data(), (int64_t)(sizeof(int) * h.size()), s);
     if (st == IBL_OK) st = mg_remove_compact(g, n, n_keep, ranges, R, keep, kscan, mkeys, tmp, t1, s);
     if (st == IBL_OK) st = mg_cells_table(g, n_keep, mkeys, head, hscan, failed, tmp, t2, 0, s, "ibl_memgrid_remove");
+    if (st != IBL_OK) (void)hipStreamSynchronize(s);        // (mg_cells_table has synchronised when it succeeds)
+    ibl_stage_reset(ctx);                                   // the pinned staging of the ranges is recycled by the next call
+    return st;
+}
+
+// Replaces the points whose ORIGINAL indices lie in range r by the next new_count[r] rows of new_pts4: the new points take the place
+// of the range in the index space, everything else keeps its relative order, and the grid afterwards is the build of the spliced
+// sequence.  No sort of resident points: the new points are keyed and sorted as an append's are, the resident slots are flagged and
+// scanned as a removal's are, and both sides scatter into the other point buffer to positions found by bounded binary searches
+// (ibl_mg_replace_old_kernel / _new_kernel).  Traffic per resident point: as a removal, + 8 B of the new keys' searches (cached);
+// per new point 16 + 8 + 4 B read and 16 + 8 + 4 B written.  Scratch (arena, released on return): 8 B per resident point, 16 B per
+// point of the result, 24 B per new point + the sort's and scans'.  Everything is checked on the host before the first launch.
+extern "C" int ibl_memgrid_replace(ibl_reg_ctx* ctx, ibl_memgrid* g, const int64_t* range_begin, const int64_t* range_end,
+                                   const int64_t* new_count, const float* new_pts4, int n_ranges, void* stream) {
+    if (!ctx || !g || n_ranges < 0 || (n_ranges > 0 && (!range_begin || !range_end || !new_count)))
+        return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_replace: bad argument");
+    if (g->fixed) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_replace: a grid built with live = 0 is immutable (build it with live = 1)");
+    if (n_ranges == 0) return IBL_OK;
+    const int64_t n = g->v.n;
+    const int R = n_ranges;
+    std::vector<int> h(4 * (size_t)R);              // rbeg | rend | rcum | ncum
+    int64_t removed = 0, added = 0, prev_end = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t b = range_begin[r], e = range_end[r], c = new_count[r];
+        if (b < prev_end || e < b || e > n || (r > 0 && b == range_begin[r - 1]))
+            return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_replace: range %d [%lld, %lld) is reversed, out of order, overlaps the one before, "
+                                 "begins where it begins or passes the grid's %lld points", r, (long long)b, (long long)e, (long long)n);
+        if (c < 0 || (c == 0 && e == b) || c > 0x7FFFFFF0ll)
+            return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_replace: range %d [%lld, %lld) gets %lld new points (an empty range needs some)", r,
+                                 (long long)b, (long long)e, (long long)c);
+        prev_end = e;
+        removed += e - b;
+        added += c;
+        if (added > 0x7FFFFFF0ll) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_replace: more than 0x7FFFFFF0 points");
+        h[r] = (int)b; h[R + r] = (int)e; h[2 * (size_t)R + r] = (int)removed; h[3 * (size_t)R + r] = (int)added;
+    }
+    const int64_t n_keep = n - removed, n_new = added, n_out = n_keep + n_new;
+    if (n_new > 0 && !new_pts4) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_replace: new_pts4 is null");
+    if (n_out <= 0) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_replace: nothing would remain (a grid is never empty)");
+    if (n_out > 0x7FFFFFF0ll) return ibl_set_error(IBL_ERR_ARG, "ibl_memgrid_replace: more than 0x7FFFFFF0 points");
+    hipStream_t s = (hipStream_t)stream;
+    ArenaMark scratch(ctx);
+    int *ranges, *keep, *kscan, *vals, *order, *head, *hscan, *failed; unsigned long long *keys, *nkeys, *mkeys; unsigned char* tmp;
+    IBL_ARENA(ranges, int, 4 * (int64_t)R);
+    IBL_ARENA(keep, int, n + 1);
+    IBL_ARENA(kscan, int, n + 1);
+    IBL_ARENA(keys, unsigned long long, n_new);
+    IBL_ARENA(nkeys, unsigned long long, n_new);
+    IBL_ARENA(vals, int, n_new);
+    IBL_ARENA(order, int, n_new);
+    IBL_ARENA(mkeys, unsigned long long, n_out);
+    IBL_ARENA(head, int, n_out + 1);
+    IBL_ARENA(hscan, int, n_out + 1);
+    IBL_ARENA(failed, int, 1);
+    size_t t0 = 0, t1 = 0, t2 = 0;
+    if (n_new > 0) IBL_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, t0, keys, nkeys, vals, order, (int)n_new, 0, 63, s));
+    IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, keep, kscan, (int)(n + 1), s));
+    IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, head, hscan, (int)n_out, s));
+    IBL_ARENA(tmp, unsigned char, (int64_t)std::max(t0, std::max(t1, t2)) + 256);
+    // the other half of the ping-pong pair: brought to the current half's capacity as in a removal, grown by 1.5 as in a merge when
+    // the result no longer fits -- the capacity the grid reports never shrinks
+    const int o = 1 - g->cur;
+    const int64_t cap_cur = g->buf_cap[g->cur];
+    const int64_t cap = n_out <= cap_cur ? cap_cur : std::min<int64_t>(0x7FFFFFF0ll, std::max<int64_t>(n_out, cap_cur + cap_cur / 2));
+    if (g->buf_cap[o] < cap) {
+        const int st = mg_alloc_other(g, cap, s, "ibl_memgrid_replace");
+        if (st != IBL_OK) return st;
+    }
+    const int *rbeg = ranges, *rend = ranges + R, *rcum = ranges + 2 * (size_t)R, *ncum = ranges + 3 * (size_t)R;
+    const float4* P = reinterpret_cast<const float4*>(new_pts4);
+    const unsigned nb = (unsigned)((n + 255) / 256), nb_new = (unsigned)((n_new + 255) / 256);
+    auto scatter = [&]() -> int {
+        int st = ibl_stage_upload(ctx, ranges, h.data(), (int64_t)(sizeof(int) * h.size()), s);
+        if (st != IBL_OK) return st;
+        if (n_new > 0) {
+            hipLaunchKernelGGL(ibl_mg_key_kernel, dim3(nb_new), dim3(256), 0, s, P, n_new, g->v.inv, keys, vals);
+            IBL_LAUNCH_CHECK();
+            IBL_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, t0, keys, nkeys, vals, order, (int)n_new, 0, 63, s));
+        }
+        hipLaunchKernelGGL(ibl_mg_remove_flag_kernel, dim3(nb), dim3(256), 0, s, g->sidx[g->cur], n, rbeg, rend, R, keep);
+        IBL_LAUNCH_CHECK();
+        IBL_HIP_CHECK(hipMemsetAsync(keep + n, 0, sizeof(int), s));
+        IBL_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, t1, keep, kscan, (int)(n + 1), s));
+        hipLaunchKernelGGL(ibl_mg_replace_old_kernel, dim3(nb), dim3(256), 0, s, g->v.sorted, g->sidx[g->cur], n, g->v.inv, rbeg, rend, rcum, ncum,
+                           R, keep, kscan, nkeys, order, (int)n_new, n_out, g->buf[o], g->sidx[o], mkeys);
+        IBL_LAUNCH_CHECK();
+        if (n_new > 0) {
+            hipLaunchKernelGGL(ibl_mg_replace_new_kernel, dim3(nb_new), dim3(256), 0, s, P, order, nkeys, (int)n_new, g->v.ukeys, g->v.ustart,
+                               g->v.n_cells, g->sidx[g->cur], kscan, rbeg, rcum, ncum, R, n_out, g->buf[o], g->sidx[o], mkeys);
+            IBL_LAUNCH_CHECK();
+        }
+        return IBL_OK;
+    };
+    int st = scatter();
+    if (st == IBL_OK) st = mg_cells_table(g, n_out, mkeys, head, hscan, failed, tmp, t2, 0, s, "ibl_memgrid_replace");
     if (st != IBL_OK) (void)hipStreamSynchronize(s);        // (mg_cells_table has synchronised when it succeeds)
     ibl_stage_reset(ctx);                                   // the pinned staging of the ranges is recycled by the next call
     return st;

@@ -30,7 +30,8 @@ from . import match
 from .assign import K_HI, K_LO, assign_batch, assign_candidates
 from .parallel import ShardExchange, shard_range, sharded_candidates
 from .registration import (CloudBatch, InstanceFeatures, MemGrid, RegContext, compact_rows, compact_scratch, evaluate_batch, evaluate_points, grow_rows,
-                           instance_features_batch, kept_runs, merged_ranges, radius_outlier_batch, register_batch, register_evaluate_batch)
+                           instance_features_batch, kept_runs, merged_ranges, radius_outlier_batch, register_batch, register_evaluate_batch,
+                           replaced_ranges, splice_rows)
 
 IBL_ST_GRID_OVERFLOW = 1          # ibl_reg_ctx_status bits (include/ibloc.h)
 
@@ -50,8 +51,8 @@ class MemoryShard:
     instance indices everywhere else remain global.  The clouds stay replicated unless shard_clouds=True: then this rank also keeps
     only the clouds, cached features and evaluation grid of [lo, hi) (`clouds` / `colors` / `intensities` may be the full lists or just
     that range), registration jobs are routed between the ranks and the evaluation is reduced over them (routing.py).
-    live=True (unsharded memories): the memory can grow and shrink while it is resident -- `append` adds instances and `remove` takes
-    instances out without rebuilding anything.
+    live=True (unsharded memories): the memory can grow and shrink while it is resident -- `append` adds instances, `remove` takes
+    instances out and `replace` changes instances where they are, without rebuilding anything.
     The embeddings, clouds and instance features then sit in buffers with room for reserve_points further points (default: an
     eighth of the memory + 65 536) and reserve_rows further embedding rows, and the spatial hash accepts appends
     (ibl_memgrid_build with live = 1).  Without live there is no headroom anywhere.  Everything computed is the same either way."""
@@ -202,6 +203,77 @@ class MemoryShard:
         self.emb_offsets = torch.from_numpy(self.emb_offsets_host).to(self.device)
         self.M -= len(idx)
         self.hi = self.M
+        torch.cuda.synchronize(self.device)
+
+    def replace(self, instances, embeddings, clouds=None, colors=None, intensities=None):
+        """Gives the instances `instances` (distinct indices, any subset, in any order) of a live memory new embeddings
+        (`embeddings[i]` an (E_i, D) array; E_i may change) and new clouds (`clouds[i]` any non-empty (n, 3) array, with `colors` /
+        `intensities` as the constructor takes them) -- an object seen again, two fragments joined, a cloud downsampled.  Every
+        instance keeps its index.  The new instances' features are computed from their own batch for every resident feature set,
+        the spatial hash splices their points into the middle of its index space (ibl_memgrid_replace: no sort of resident points),
+        and the clouds, every feature set and the embedding rows are spliced in place in their buffers (registration.splice_rows;
+        a buffer without room grows by 1.5) -- nothing resident is recomputed, re-uploaded or re-sorted, and the InstanceFeatures
+        objects stay the same objects.  The state afterwards is, array for array, that of a MemoryShard constructed from the edited
+        instance list.  An embedding-only memory replaces embedding rows only.  Synchronises the device first: no localisation may
+        be in flight.  Raises ValueError, before anything is touched, for a sharded or non-live memory, an index out of range, a
+        duplicate index, a count or dimension mismatch, clouds given to an embedding-only memory (or withheld from one with clouds)
+        or more than 0x7FFFFFF0 points.  An empty list is a no-op."""
+        if self.shard is not None:
+            raise ValueError("MemoryShard.replace: sharded memories cannot change while resident")
+        if not self.live:
+            raise ValueError("MemoryShard.replace: construct the shard with live=True")
+        if (clouds is None) != (self.clouds is None):
+            raise ValueError("MemoryShard.replace: an embedding-only memory takes no clouds, a memory with clouds needs them")
+        given = [int(i) for i in instances]
+        if len(set(given)) != len(given):
+            raise ValueError("MemoryShard.replace: an instance is named twice")
+        if given and (min(given) < 0 or max(given) >= self.M):
+            raise ValueError(f"MemoryShard.replace: instance index out of range (the memory holds {self.M})")
+        embs = [np.asarray(e, dtype=np.float32) for e in embeddings]
+        dim = self.mem_emb.shape[1]
+        if len(embs) != len(given):
+            raise ValueError("MemoryShard.replace: as many embedding arrays as instances")
+        if any(e.ndim != 2 or e.shape[1] != dim or len(e) == 0 for e in embs):
+            raise ValueError(f"MemoryShard.replace: every instance needs an (E, {dim}) array of embeddings")
+        if clouds is not None:
+            if len(clouds) != len(embs) or any(x is not None and len(x) != len(embs) for x in (colors, intensities)):
+                raise ValueError("MemoryShard.replace: as many clouds (colours, intensities) as instances")
+            if any(np.asarray(c).ndim != 2 or np.asarray(c).shape[1] != 3 or len(c) == 0 for c in clouds):
+                raise ValueError("MemoryShard.replace: every cloud is a non-empty (n, 3) array")
+            sizes = np.diff(self.clouds.seg_off_host)
+            if self.clouds.n - int(sizes[given].sum()) + sum(len(c) for c in clouds) > 0x7FFFFFF0:
+                raise ValueError("MemoryShard.replace: more than 0x7FFFFFF0 memory points")
+        if not given:
+            return
+        by_index = np.argsort(given)                        # the library and the buffers take the instances in ascending order
+        idx = [given[i] for i in by_index]
+        embs = [embs[i] for i in by_index]
+        torch.cuda.synchronize(self.device)
+        # one scratch chunk for every splice below, allocated before anything is changed (132 B: the widest row, fpfh)
+        scratch = compact_scratch(self.device, max(self.mem_emb.numel() * 4, 0 if self.clouds is None else self.clouds.n * 132))
+        if clouds is not None:
+            if intensities is None:
+                intensities = [intensity_from_colors(c) for c in colors] if colors is not None else None
+            new = CloudBatch.from_numpy([clouds[i] for i in by_index], None if intensities is None else [intensities[i] for i in by_index],
+                                        device=self.device)
+            # the new instances' features first, from their own batch: nothing resident has changed if this raises
+            new_feat = {key: instance_features_batch(self.ctx, new, key[0], 2.0 * (key[0] * key[1]), compact=self.compact_features)
+                        for key in self._features}
+            # then the grid: the only step that can fail in the library, and it leaves the grid as it was when it does
+            edits = replaced_ranges(self.clouds.seg_off_host, idx, new.seg_off_host)
+            self.grid.replace([(b, e) for b, e, _, _ in edits], [ne - nb for _, _, nb, ne in edits], new.pts4)
+            self.clouds.replace(idx, new, scratch=scratch)
+            for key, feat in self._features.items():
+                feat.replace(idx, edits, new_feat[key], scratch=scratch)
+        rows = match.normalize_rows(torch.from_numpy(np.ascontiguousarray(np.concatenate(embs))).to(self.device))
+        new_off = np.concatenate([[0], np.cumsum([len(e) for e in embs])])
+        self._emb_buf, self.mem_emb = splice_rows(self._emb_buf, self.mem_emb.shape[0],
+                                                  [(b, e, rows[nb:ne]) for b, e, nb, ne in replaced_ranges(self.emb_offsets_host, idx, new_off)],
+                                                  scratch=scratch)
+        counts = np.diff(self.emb_offsets_host)
+        counts[idx] = np.diff(new_off)
+        self.emb_offsets_host = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        self.emb_offsets = torch.from_numpy(self.emb_offsets_host).to(self.device)
         torch.cuda.synchronize(self.device)
 
     def close(self):

@@ -136,6 +136,43 @@ class ObjectMemory():
             self._engine = None          # whatever state the shard is in, the next query rebuilds it from self.memory
             raise
 
+    def update_objects(self, indices):
+        """The ObjectInfos at the positions `indices` (distinct) of self.memory were edited where they are -- `add_info`, `downsample`,
+        `update_pointcloud_with_mask`, `memory[i] = memory[i] + other`.  A resident live memory takes their current embeddings and
+        clouds in place (MemoryShard.replace) and the engine stays; otherwise, or when the shard raises, the engine is dropped and the
+        next query rebuilds it from self.memory."""
+        given = [int(i) for i in indices]
+        idx = sorted(set(given))
+        if len(idx) != len(given) or (idx and (idx[0] < 0 or idx[-1] >= len(self.memory))):
+            raise ValueError(f"update_objects: distinct indices below {len(self.memory)} expected, got {given}")
+        if not idx:
+            return
+        if self._engine is None or self._shard.M != len(self.memory) or not self.live_memory or not self._shard.live:
+            self._engine = None
+            return
+        infos = [self.memory[i] for i in idx]
+        try:
+            self._shard.replace(idx, [np.stack(m.embeddings).astype(np.float32) for m in infos],
+                                [np.asarray(m.pointcloud.points) for m in infos],
+                                colors=[np.asarray(m.pointcloud.colors) for m in infos])
+        except Exception:
+            self._engine = None          # whatever state the shard is in, the next query rebuilds it from self.memory
+            raise
+
+    def merge_objects(self, dst, src):
+        """Two entries found to be one object: memory[dst] takes the names, embeddings and points of memory[src] (ObjectInfo.__add__,
+        then its means are refreshed) and memory[src] is deleted as `remove_objects` deletes -- the other ObjectInfos keep their
+        ids.  A resident live memory replaces `dst` in place and then removes `src`."""
+        dst, src = int(dst), int(src)
+        if dst == src or not (0 <= dst < len(self.memory) and 0 <= src < len(self.memory)):
+            raise ValueError(f"merge_objects: two distinct indices below {len(self.memory)} expected, got {dst}, {src}")
+        self.memory[dst] = self.memory[dst] + self.memory[src]
+        self.memory[dst]._compute_means()
+        try:
+            self.update_objects([dst])
+        finally:
+            self.remove_objects([src])   # (the list is edited whatever became of the resident memory)
+
     # ---- memory build (object_memory.py:163-256) ----------------------------------------------------------
     def _log(self, *a):
         if self.log_enabled:

@@ -125,32 +125,104 @@ def compact_rows(buf: torch.Tensor, n_used: int, keep_runs, scratch_bytes=COMPAC
     piece -> scratch -> destination), so the number of copies follows the chunk, never a small shift.  No copy is between overlapping
     views.  Everything is queued on the current stream.  scratch: a `compact_scratch` tensor to use (its size then stands for
     scratch_bytes) instead of allocating one when a run needs it.  Returns the view of the kept rows."""
+    chunk, scratch = _scratch_rows(buf, n_used, scratch_bytes, scratch)
+    at = 0
+    for b, e in keep_runs:
+        assert at <= b < e <= n_used
+        scratch = _move_rows(buf, b, at, e - b, chunk, scratch)
+        at += e - b
+    return buf[:at]
+
+
+def _scratch_rows(buf, n_used, scratch_bytes, scratch):
+    """(rows per piece, the caller's scratch bytes as rows of `buf` or None) for `_move_rows`"""
     row_bytes = buf.element_size() * int(np.prod(buf.shape[1:], dtype=np.int64))
     if scratch is not None:
         scratch_bytes = scratch.numel()
     chunk = max(1, min(int(scratch_bytes) // max(row_bytes, 1), n_used))
-    if scratch is not None:             # the caller's bytes as rows of this buffer (none if not even one row fits: allocated below)
+    if scratch is not None:             # the caller's bytes as rows of this buffer (none if not even one row fits: allocated when needed)
         scratch = scratch[:chunk * row_bytes].view(buf.dtype).view((chunk,) + tuple(buf.shape[1:])) if scratch.numel() >= row_bytes else None
-    at = 0
-    for b, e in keep_runs:
-        assert at <= b < e <= n_used
-        shift, length = b - at, e - b
-        if shift >= length:
-            buf[at:at + length].copy_(buf[b:e])
-        elif shift > 0:
-            direct = shift >= chunk                      # source and destination of a piece no longer than the shift are disjoint
-            piece = shift if direct else chunk
-            if not direct and scratch is None:
-                scratch = torch.empty((chunk,) + tuple(buf.shape[1:]), dtype=buf.dtype, device=buf.device)
-            for o in range(0, length, piece):
-                c = min(piece, length - o)
-                if direct:
-                    buf[at + o:at + o + c].copy_(buf[b + o:b + o + c])
-                else:
-                    scratch[:c].copy_(buf[b + o:b + o + c])
-                    buf[at + o:at + o + c].copy_(scratch[:c])
-        at += length
-    return buf[:at]
+    return chunk, scratch
+
+
+def _move_rows(buf, src, dst, length, chunk, scratch):
+    """The rows [src, src + length) of `buf` move to [dst, dst + length), down or up.  A run that moves by at least its length is one
+    copy.  A run that overlaps its destination goes in pieces, ascending when it moves down and descending when it moves up, so that
+    no piece lands on rows still to be read: pieces of the shift's length, copied directly, when the shift is at least `chunk`
+    rows, else of `chunk` rows through `scratch` (allocated here when None).  No copy is between overlapping views.  Returns scratch."""
+    shift = abs(src - dst)
+    if shift >= length:
+        buf[dst:dst + length].copy_(buf[src:src + length])
+    elif shift > 0:
+        direct = shift >= chunk                          # source and destination of a piece no longer than the shift are disjoint
+        piece = shift if direct else chunk
+        if not direct and scratch is None:
+            scratch = torch.empty((chunk,) + tuple(buf.shape[1:]), dtype=buf.dtype, device=buf.device)
+        starts = range(0, length, piece)
+        for o in (starts if dst < src else reversed(starts)):
+            c = min(piece, length - o)
+            if direct:
+                buf[dst + o:dst + o + c].copy_(buf[src + o:src + o + c])
+            else:
+                scratch[:c].copy_(buf[src + o:src + o + c])
+                buf[dst + o:dst + o + c].copy_(scratch[:c])
+    return scratch
+
+
+def splice_rows(buf: torch.Tensor, n_used: int, edits, scratch=None, scratch_bytes=COMPACT_SCRATCH_BYTES):
+    """Rows replaced in the middle of a buffer with headroom (live memory): `edits` = [(begin, end, new_rows), ...], ascending and
+    disjoint over the first n_used rows of `buf`; the rows [begin, end) give way to new_rows (a tensor of any number of rows of
+    buf's row shape: none is a removal, begin == end an insertion).  IN PLACE while the result fits -- a resident array is never
+    duplicated: the kept runs between the edits move first, those that move down in ascending and then those that move up in
+    descending order (`_move_rows`: through one bounded scratch chunk, as `compact_rows`), and the new rows are written last.  In
+    that order no run lands on rows another run has yet to leave: a run that moves down lands below its own end, which lies below
+    every later run; a run that moves up lands above its own begin, above every earlier run; and the later runs that move up, and
+    every run that moves down, have left by then.  A result that does not fit is built once into a buffer 1.5 times as large.
+    Any device; everything is queued on the current stream.  scratch / scratch_bytes: see `compact_rows`.
+    Returns (buffer, view of its used rows)."""
+    moves, fresh, at, to = [], [], 0, 0                  # (source, destination, length) of kept runs, (destination, rows) of new ones
+    for b, e, rows in edits:
+        assert at <= b <= e <= n_used and tuple(rows.shape[1:]) == tuple(buf.shape[1:])
+        if b > at:
+            moves.append((at, to, b - at))
+            to += b - at
+        if rows.shape[0]:
+            fresh.append((to, rows))
+            to += rows.shape[0]
+        at = e
+    if at < n_used:
+        moves.append((at, to, n_used - at))
+        to += n_used - at
+    if to > buf.shape[0]:
+        grown = torch.empty((max(to, buf.shape[0] + buf.shape[0] // 2),) + tuple(buf.shape[1:]), dtype=buf.dtype, device=buf.device)
+        for src, dst, length in moves:
+            grown[dst:dst + length].copy_(buf[src:src + length])
+        buf = grown
+    else:
+        chunk, scratch = _scratch_rows(buf, n_used, scratch_bytes, scratch)
+        for src, dst, length in moves:
+            if dst < src:
+                scratch = _move_rows(buf, src, dst, length, chunk, scratch)
+        for src, dst, length in reversed(moves):
+            if dst > src:
+                scratch = _move_rows(buf, src, dst, length, chunk, scratch)
+    for dst, rows in fresh:
+        buf[dst:dst + rows.shape[0]].copy_(rows)
+    return buf, buf[:to]
+
+
+def replaced_ranges(off, segments, new_off):
+    """the edits [(begin, end, new_begin, new_end), ...] that put segment i of a batch with offsets `new_off` in the place of
+    segment segments[i] (ascending, distinct) of a batch with offsets `off`: row ranges of the old and of the new batch, neighbours
+    joined, edits of nothing by nothing left out"""
+    out = []
+    for i, s in enumerate(segments):
+        b, e, nb, ne = int(off[s]), int(off[s + 1]), int(new_off[i]), int(new_off[i + 1])
+        if out and out[-1][1] == b:
+            out[-1] = (out[-1][0], e, out[-1][2], ne)
+        elif e > b or ne > nb:
+            out.append((b, e, nb, ne))
+    return [x for x in out if x[1] > x[0] or x[3] > x[2]]
 
 
 class CloudBatch:
@@ -226,6 +298,24 @@ class CloudBatch:
         self.seg_off_host = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
         self.seg_off = torch.from_numpy(self.seg_off_host).to(self.pts4.device)
         return ranges
+
+    def replace(self, segments, new_batch: "CloudBatch", scratch=None):
+        """Puts cloud i of `new_batch` (a CloudBatch on the same device with len(segments) clouds) in the place of the cloud
+        segments[i] (ascending, distinct segment indices): every cloud keeps its segment index, the clouds behind a replaced one move
+        in the backing buffer (`splice_rows`: in place unless it has to grow by 1.5).  `pts4` and `seg_off` are NEW tensor objects
+        afterwards.  Returns the edits [(begin, end, new_begin, new_end), ...] (`replaced_ranges`: point ranges in the numbering
+        before the call and the rows of new_batch that took their place) -- what `InstanceFeatures.replace` takes."""
+        segments = [int(s) for s in segments]
+        assert all(a < b for a, b in zip([-1] + segments, segments + [self.n_seg])) and new_batch.n_seg == len(segments)
+        edits = replaced_ranges(self.seg_off_host, segments, new_batch.seg_off_host)
+        if self.n + sum((ne - nb) - (e - b) for b, e, nb, ne in edits) > 0x7FFFFFF0:
+            raise ValueError("more than 0x7FFFFFF0 points in a cloud batch")
+        self._buf, self.pts4 = splice_rows(self._buf, self.n, [(b, e, new_batch.pts4[nb:ne]) for b, e, nb, ne in edits], scratch=scratch)
+        sizes = np.diff(self.seg_off_host)
+        sizes[segments] = np.diff(new_batch.seg_off_host)
+        self.seg_off_host = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+        self.seg_off = torch.from_numpy(self.seg_off_host).to(self.pts4.device)
+        return edits
 
 
 def unproject_masks(ctx: RegContext, depth: torch.Tensor, rgb: torch.Tensor, masks: torch.Tensor, fx: float, fy: float,
@@ -364,6 +454,31 @@ class InstanceFeatures:
         self.n = sum(e - b for b, e in runs)
         self.n_seg -= len(segments)
 
+    def replace(self, segments, point_ranges, new: "InstanceFeatures", scratch=None):
+        """Puts the features `new` of len(segments) clouds (computed on their own, as for `append`) in the place of those of the
+        clouds `segments` (ascending, distinct): `point_ranges` are the edits `CloudBatch.replace` returns.  Same parameters and same
+        form only, as `append`.  Every device array that is present is spliced in its backing buffer (`splice_rows`: in place
+        unless it has to grow, nothing resident is recomputed), the bounding-box rows of the clouds are replaced."""
+        if self.n is None or new.n is None:
+            raise ValueError("InstanceFeatures.replace: point counts unknown (features not made by instance_features_batch)")
+        if (self.voxel_size, self.grad_radius) != (new.voxel_size, new.grad_radius):
+            raise ValueError("InstanceFeatures.replace: the features were computed with other parameters")
+        for name in self.DEVICE_ARRAYS:
+            if (getattr(self, name) is None) != (getattr(new, name) is None):
+                raise ValueError(f"InstanceFeatures.replace: `{name}` is present on one side only")
+        if new.n_seg != len(segments):
+            raise ValueError("InstanceFeatures.replace: as many new clouds as segments")
+        for name in self.DEVICE_ARRAYS:
+            cur = getattr(self, name)
+            if cur is not None:
+                rows = getattr(new, name)
+                self._bufs[name], view = splice_rows(self._bufs.get(name, cur), self.n, [(b, e, rows[nb:ne]) for b, e, nb, ne in point_ranges],
+                                                     scratch=scratch)
+                setattr(self, name, view)
+        self.bbox = np.array(self.bbox[:self.n_seg], order="C")
+        self.bbox[list(segments)] = new.bbox[:new.n_seg]
+        self.n += sum((ne - nb) - (e - b) for b, e, nb, ne in point_ranges)
+
     def as_struct(self):
         return _FeatStruct(self.normals.data_ptr(), self.fpfh.data_ptr(), self.fpfh_split.data_ptr() if self.fpfh_split is not None else None,
                            self.fpfh_norm.data_ptr(),
@@ -496,7 +611,7 @@ def register_evaluate_batch(ctx: RegContext, det: CloudBatch, q_per_frame, assns
 class MemGrid:
     """Spatial hash over all memory points.  It owns its device memory: `close` frees it, and nothing of it lives in the context
     arena (RegContext.reset leaves it valid).  Built once and immutable unless live=True: then the grid has room for reserve_points
-    further points, `append` merges further points into it and `remove` takes points out."""
+    further points, `append` merges further points into it, `remove` takes points out and `replace` changes points in place."""
 
     def __init__(self, ctx: RegContext, mem_pts4: torch.Tensor, cell=0.04, live=False, reserve_points=0):
         assert mem_pts4.is_cuda and mem_pts4.dtype == torch.float32 and mem_pts4.shape[1] == 4 and mem_pts4.is_contiguous()
@@ -526,6 +641,21 @@ class MemGrid:
         re = np.ascontiguousarray([r[1] for r in ranges], dtype=np.int64)
         st = _lib.lib.ibl_memgrid_remove(self.ctx.handle, self._h, rb.ctypes.data, re.ctypes.data, len(rb), _stream())
         _lib.check(st, "ibl_memgrid_remove")
+
+    def replace(self, ranges, counts, pts4_new: torch.Tensor):
+        """Replaces the points whose original indices lie in ranges[r] = (begin, end) -- ascending, disjoint, no two with the same
+        begin; an empty range is an insertion in front of `begin` -- by the next counts[r] rows of pts4_new (0: a removal) in a live
+        grid: afterwards it equals the grid built from the spliced points (ibl_memgrid_replace).  Synchronises the current stream;
+        the rule for other streams is `append`'s.  Whatever the library refuses (IblError) leaves the grid unchanged."""
+        assert pts4_new.is_cuda and pts4_new.dtype == torch.float32 and pts4_new.dim() == 2 and pts4_new.shape[1] == 4 and pts4_new.is_contiguous()
+        rb = np.ascontiguousarray([r[0] for r in ranges], dtype=np.int64)
+        re = np.ascontiguousarray([r[1] for r in ranges], dtype=np.int64)
+        nc = np.ascontiguousarray(counts, dtype=np.int64)
+        if len(nc) != len(rb) or int(nc.sum()) != pts4_new.shape[0]:
+            raise ValueError("MemGrid.replace: one count per range, and as many new rows as the counts say")
+        st = _lib.lib.ibl_memgrid_replace(self.ctx.handle, self._h, rb.ctypes.data, re.ctypes.data, nc.ctypes.data,
+                                          pts4_new.data_ptr() if pts4_new.shape[0] else None, len(rb), _stream())
+        _lib.check(st, "ibl_memgrid_replace")
 
     def export(self):
         """copies of the grid's arrays as device tensors: dict(sorted (n, 4) float32 -- the points in cell order --, ukeys (n_cells,)

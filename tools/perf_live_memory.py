@@ -1,5 +1,5 @@
-"""Cost of adding an object to a resident memory, and of taking one out: MemoryShard.append / MemoryShard.remove on a live memory
-against the rebuild they replace, on a synthetic memory of N instances x 5 000 points (ibloc_amd.synth.SynthWorld).
+"""Cost of adding an object to a resident memory, of taking one out and of changing one where it is: MemoryShard.append / .remove /
+.replace on a live memory against the rebuild they replace, on a synthetic memory of N instances x 5 000 points (ibloc_amd.synth.SynthWorld).
 
     python tools/perf_live_memory.py N [--points P] [--seed S] [--compact] [--arena-gb G]
 
@@ -9,7 +9,10 @@ that is host packing and the host-to-device copy of the clouds (CloudBatch.from_
 live=True; append_1_s / append_32_s, MemoryShard.append of 1 and of 32 instances (median of 5 after a warm-up append, device
 synchronised), with append_*_grid_s, the ibl_memgrid_append part of those appends, and append_*_all the single times; remove_1_s /
 remove_32_s, MemoryShard.remove of 1 and of 32 neighbouring instances from the middle of the same memory (median of 5 after a warm-up
-removal), with remove_*_grid_s, the ibl_memgrid_remove part, and remove_*_all; grid_rebuild_s, a MemGrid built from the kept points
+removal), with remove_*_grid_s, the ibl_memgrid_remove part, and remove_*_all; replace_1_s, MemoryShard.replace of the middle instance by
+another cloud of the same size elsewhere (median of 5 after a warm-up), with replace_1_grid_s, the ibl_memgrid_replace part, and
+replace_1_all, against remove_append_1_s, the removal and append a caller had to use instead (it moves the instance to the end);
+grid_rebuild_s, a MemGrid built from the kept points
 (median of 5 after a warm-up): the re-sort the removal avoids.  Without a live memory a removal costs rebuild_s.  Needs a GPU."""
 import argparse
 import json
@@ -38,7 +41,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("perf_live_memory.py measures device work: no GPU here")
 
-    extra = 6 * (1 + 32)                                     # a warm-up and five timed appends of 1 and of 32 instances
+    extra = 6 * (1 + 32) + 12                                # a warm-up and five timed appends of 1 and of 32 instances, 2 x 6 replacements
     t = time.perf_counter()
     w = SynthWorld(a.n + extra, pts_per_object=a.points, E=2, D=64, seed=a.seed)
     emb = list(w.embeddings)
@@ -122,6 +125,40 @@ def main():
         out[f"remove_{k}_s"] = float(np.median(times[1:]))
         out[f"remove_{k}_all"] = times
         out[f"remove_{k}_grid_s"] = float(np.median(grid_times[-5:]))
+    grid_times = []
+    grid_replace = m.grid.replace
+
+    def timed_grid_replace(ranges, counts, p):
+        sync()
+        t0 = time.perf_counter()
+        grid_replace(ranges, counts, p)
+        sync()
+        grid_times.append(time.perf_counter() - t0)
+
+    m.grid.replace = timed_grid_replace
+    times, substitute = [], []
+    for _ in range(6):
+        mid = m.M // 2
+        sync()
+        t = time.perf_counter()
+        m.replace([mid], emb[nxt:nxt + 1], w.points[nxt:nxt + 1], intensities=ints[nxt:nxt + 1])
+        sync()
+        times.append(time.perf_counter() - t)
+        nxt += 1
+    out["replace_1_s"] = float(np.median(times[1:]))
+    out["replace_1_all"] = times
+    out["replace_1_grid_s"] = float(np.median(grid_times[-5:]))
+    for _ in range(6):                                       # what a caller had to do instead, and it moves the instance to the end
+        mid = m.M // 2
+        sync()
+        t = time.perf_counter()
+        m.remove([mid])
+        m.append(emb[nxt:nxt + 1], w.points[nxt:nxt + 1], intensities=ints[nxt:nxt + 1])
+        sync()
+        substitute.append(time.perf_counter() - t)
+        nxt += 1
+    out["remove_append_1_s"] = float(np.median(substitute[1:]))
+    out["remove_append_1_all"] = substitute
     times = []
     for _ in range(6):
         sync()
@@ -136,6 +173,8 @@ def main():
     out["rebuild_over_append_1"] = out["rebuild_s"] / out["append_1_s"]
     out["rebuild_over_remove_1"] = out["rebuild_s"] / out["remove_1_s"]
     out["grid_rebuild_over_grid_remove_1"] = out["grid_rebuild_s"] / out["remove_1_grid_s"]
+    out["rebuild_over_replace_1"] = out["rebuild_s"] / out["replace_1_s"]
+    out["remove_append_over_replace_1"] = out["remove_append_1_s"] / out["replace_1_s"]
     m.close()
     ctx.close()
     out["device"] = torch.cuda.get_device_name(0)
