@@ -20,7 +20,7 @@
  *     never synchronise.  Functions that return HOST results synchronise the stream -- how often is stated per function:
  *     ibl_radius_outlier_batch 1 (grid table size), ibl_instance_features_batch 2 (bounding boxes; end),
  *     ibl_register_jobs 2-4 (one per group of RANSAC rounds -- most calls need one -- plus the results; one more when
- *     instances of a job lie within the influence radius of each other), ibl_evaluate_batch 1, ibl_memgrid_build / _append / _remove / _replace 2
+ *     instances of a job lie within the influence radius of each other), ibl_evaluate_batch 1, ibl_memgrid_overlap 1, ibl_memgrid_build / _append / _remove / _replace 2
  *     (cell count; end; one more when the call has to reallocate the other point buffer).  Plan tables are staged through pinned host memory of the registration context, so uploads never wait.
  *   - plain C types only; no torch types in any signature.
  */
@@ -679,6 +679,32 @@ int ibl_memgrid_export(const ibl_memgrid* grid, float* sorted_out /* [dev] n x 4
  *   Synchronisation: as ibl_memgrid_append and ibl_memgrid_remove. */
 int ibl_memgrid_replace(ibl_reg_ctx* ctx, ibl_memgrid* grid, const int64_t* range_begin, const int64_t* range_end,
                         const int64_t* new_count, const float* new_pts4, int n_ranges, void* stream);
+
+/* Live memory, association: which resident instances does each detection cloud overlap -- the geometric half of deciding whether a
+ * detection is an instance seen again (the reference raises "Only final clustering available currently" where it would decide,
+ * object_memory/object_memory.py:230-235).  For detection d (the world-frame points det_off_host[d] .. det_off_host[d + 1] of
+ * det_pts4) and instance m (the ORIGINAL point indices inst_off[m] .. inst_off[m + 1] of the grid)
+ *       hits(d, m) = #{ p in d : some point q of m has d2(p, q) < r2 },
+ *   d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) in fp32 with a strict <, r2 = (float)(radius * radius) as ibl_evaluate_batch forms its
+ *   threshold.  A point near several instances counts once for each: "some point within r", not "the owner of the nearest point", so
+ *   no tie between instances decides a count and hits is an exact integer.
+ *   Per detection the call returns the instances with hits > 0 ordered by hits descending, then instance ascending, cut to k:
+ *   pair_inst / pair_hits [HOST] n_det x k (-1 / 0 padded), n_hit_inst [HOST] n_det = the uncut number of such instances (may exceed k).
+ *   inst_off [dev] n_inst + 1 ascending offsets (empty instances allowed), inst_off_end = its last entry as the caller knows it:
+ *   it must equal the grid's n (checked without a device read).  det_pts4 [dev] float4 rows; det_off_host [HOST] n_det + 1.
+ *   Two launches: one thread per detection point walks the cells of its +-radius box through the table (every probe bounded by the
+ *   table size), reads the per-slot original index next to a point within r, maps it to its instance by a bounded search and adds 1
+ *   to a dense int32 [n_det][n_inst] array (integer atomics: deterministic totals; an instance met in several cells of the box counts
+ *   once, for any number of instances); one workgroup per detection then ranks the non-zero entries.
+ *   Scratch from ctx's arena, released on return: 4 n_det n_inst + 8 n_det k + 4 (2 n_det + 1) bytes; exhaustion is the arena error.
+ *   A LIVE grid is required: an immutable one keeps no per-slot indices.  IBL_ERR_ARG, decided on the host before anything is
+ *   launched and leaving the outputs untouched: a grid built with live == 0; radius <= 0; radius > the grid's cell (a box is then at
+ *   most 27 cells); k < 1; n_inst < 1; inst_off_end != n; det_off_host that begins below 0 or descends; null pointers.  n_det == 0
+ *   succeeds and launches nothing.
+ *   Synchronisation: the call synchronises `stream` before it returns (its results are host arrays); the grid is only read. */
+int ibl_memgrid_overlap(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const int32_t* inst_off, int32_t n_inst, int32_t inst_off_end,
+                        const float* det_pts4, const int32_t* det_off_host, int32_t n_det, double radius, int32_t k,
+                        int32_t* pair_inst, int32_t* pair_hits, int32_t* n_hit_inst, void* stream);
 
 /* evaluate_transform(all_detected_pcd, all_memory_pcd, T) for n_jobs candidates: job j transforms the detected
  * points [job_begin[j], job_end[j]) of det_pts4 [dev] by T_global[j] (host, 16 doubles row-major) and looks for

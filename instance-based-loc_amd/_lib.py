@@ -74,6 +74,7 @@ _SIGS = {
     "ibl_memgrid_remove": (C.c_int, [vp, vp, vp, vp, C.c_int, vp]),
     "ibl_memgrid_replace": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "ibl_memgrid_export": (C.c_int, [vp, vp, vp, vp, vp]),
+    "ibl_memgrid_overlap": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_double, C.c_int32, vp, vp, vp, vp]),
     "ibl_evaluate_batch": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp]),
     "ibl_register_evaluate_batch": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_double, C.c_int, C.c_double, C.c_int,
                                               vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -41,6 +41,7 @@ int ibl_set_error(int code, const char* fmt, ...);
 #define IBL_PROF_ST_ICP 13        // ICP of a registration call: 56 B per source point and iteration run
 #define IBL_PROF_ST_EVAL 14       // ibl_evaluate_*: 24 B per detected point and candidate
 #define IBL_PROF_ST_OUTLIER 15    // ibl_radius_outlier_batch: 12 B in + 1 B out per point
+#define IBL_PROF_ST_ASSOC 16      // ibl_memgrid_overlap (count + rank): 16 B per detection point, the compulsory read
 #define IBL_PROF_MAX 24
 int ibl_prof_enabled();
 void ibl_prof_begin(int id, double units, void* stream, void** token);

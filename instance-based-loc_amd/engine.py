@@ -52,7 +52,8 @@ class MemoryShard:
     only the clouds, cached features and evaluation grid of [lo, hi) (`clouds` / `colors` / `intensities` may be the full lists or just
     that range), registration jobs are routed between the ranks and the evaluation is reduced over them (routing.py).
     live=True (unsharded memories): the memory can grow and shrink while it is resident -- `append` adds instances, `remove` takes
-    instances out and `replace` changes instances where they are, without rebuilding anything.
+    instances out and `replace` changes instances where they are, without rebuilding anything; `overlap` tells which resident
+    instances a detection lies on (what decides between them: ObjectMemory.process_detections(associate=True)).
     The embeddings, clouds and instance features then sit in buffers with room for reserve_points further points (default: an
     eighth of the memory + 65 536) and reserve_rows further embedding rows, and the spatial hash accepts appends
     (ibl_memgrid_build with live = 1).  Without live there is no headroom anywhere.  Everything computed is the same either way."""
@@ -275,6 +276,24 @@ class MemoryShard:
         self.emb_offsets_host = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
         self.emb_offsets = torch.from_numpy(self.emb_offsets_host).to(self.device)
         torch.cuda.synchronize(self.device)
+
+    def overlap(self, det: CloudBatch, radius=None, k=8):
+        """Which resident instances does each detection overlap: `det` the detection clouds in the WORLD frame, radius the distance
+        within which a detection point counts as lying on an instance (default: eval_threshold, the distance at which
+        evaluate_transform counts a point as explained by the memory; at most the grid's cell, 2 * eval_threshold), k the number of
+        candidates kept per detection.  Returns numpy arrays (inst (n_det, k) int32, -1 padded; hits (n_det, k) int32, 0 padded;
+        n_hit_inst (n_det,) int32): per detection the instances with hits > 0 by hits descending, then index ascending, where
+        hits = the detection's points with some point of the instance within radius (MemGrid.overlap, ibl_memgrid_overlap), and the
+        uncut number of such instances.  Changes nothing; synchronises the current stream.  Raises ValueError for a sharded or
+        non-live memory (the grid of a live memory alone knows the instance of a resident point) and for one without clouds."""
+        if self.shard is not None:
+            raise ValueError("MemoryShard.overlap: sharded memories cannot be associated with while resident")
+        if not self.live:
+            raise ValueError("MemoryShard.overlap: construct the shard with live=True")
+        if self.clouds is None:
+            raise ValueError("MemoryShard.overlap: an embedding-only memory has no clouds to overlap")
+        return self.grid.overlap(det.pts4, det.seg_off_host, self.clouds.seg_off, self.eval_threshold if radius is None else radius, k,
+                                 inst_off_end=int(self.clouds.seg_off_host[-1]))
 
     def close(self):
         """Frees the spatial hash and drops the resident features."""

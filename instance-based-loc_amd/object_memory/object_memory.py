@@ -12,6 +12,8 @@ is scikit-learn's as in the reference, and the object-aligned IoU (Open3D OBB + 
 `iou_func`.  `add_object()` / `load()` fill the memory with (name, embeddings, cloud) records in the reference's ObjectInfo layout.
 """
 import os
+from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -23,6 +25,38 @@ from ibloc_amd.utils.fpfh_register import Cloud
 from .object_info import ObjectInfo
 
 DEFAULT_OUTLIER_REMOVAL_CONFIG = {"radius_nb_points": 12, "radius": 0.05}      # utils/depth_utils.py:5-10
+
+
+@dataclass(frozen=True)
+class AssociationParams:
+    """The policy of `ObjectMemory.associate_detections`.  The defaults are values the code base already carries, not tuned results:
+    min_overlap = the default IoU_threshold of `_recluster_IoU` (0.6); min_similarity = 1 - the reference's
+    embedding_distance_threshold (1 - 0.4); radius None = the resident memory's eval_threshold (0.02 m, the distance at which
+    evaluate_transform counts a point as explained by the memory); k = 8 candidates per detection."""
+    min_overlap: float = 0.6            # hits / len(detection) a candidate needs
+    min_similarity: float = 0.6         # cosine of the detection's embedding with the candidate's mean_emb it needs
+    radius: Optional[float] = None      # metres; at most the grid's cell (2 * eval_threshold)
+    k: int = 8
+
+
+def association_decisions(inst, hits, det_sizes, det_embs, mean_emb_of, params=AssociationParams()):
+    """The decision half of `ObjectMemory.associate_detections` (its docstring has the rule): inst / hits the (n_det, k) candidate
+    arrays of MemoryShard.overlap, det_sizes the points per detection, det_embs their embeddings, mean_emb_of(m) the mean embedding
+    of instance m.  A handful of float64 dot products per detection; returns one instance index or None per detection."""
+    decisions = []
+    for d, e in enumerate(det_embs):
+        e = np.asarray(e, dtype=np.float64).reshape(-1)
+        best, best_cos = None, -np.inf
+        for m, h in zip(inst[d], hits[d]):                         # (instance ascending among equal hits; -1 pads the tail)
+            if m < 0 or det_sizes[d] == 0 or h / det_sizes[d] < params.min_overlap:
+                continue
+            mean = np.asarray(mean_emb_of(int(m)), dtype=np.float64).reshape(-1)
+            norm = np.linalg.norm(e) * np.linalg.norm(mean)
+            cos = float(np.dot(e, mean) / norm) if norm > 0 else -np.inf
+            if cos > best_cos or (cos == best_cos and best is not None and m < best):
+                best, best_cos = int(m), cos
+        decisions.append(best if best is not None and best_cos >= params.min_similarity else None)
+    return decisions
 
 
 def default_load_rgb(path: str) -> np.ndarray:
@@ -178,10 +212,38 @@ class ObjectMemory():
         if self.log_enabled:
             print(*a)
 
+    def associate_detections(self, embs, clouds_world, params=AssociationParams()):
+        """For each detection -- embs[i] its embedding, clouds_world[i] its points in the WORLD frame, an (N, 3) array or a (points,
+        colors) tuple -- the index of the resident instance it is a re-observation of, or None.  Changes nothing.
+        The rule is a documented policy, not a tuned result.  The resident spatial hash returns per detection the (at most params.k)
+        instances with the most hits, hits = the detection's points with some point of the instance within params.radius
+        (MemoryShard.overlap: one launch for all detections).  Of these candidates those with hits / len(detection) >=
+        params.min_overlap are kept, and of those the one whose mean_emb has the highest cosine with the detection's embedding is
+        taken if that cosine is >= params.min_similarity; ties go to the lower instance index.  The defaults: `AssociationParams`.
+        Decisions are taken against the memory as it stands: the detections of one call never see each other, and two of them may
+        choose the same instance.  Builds the resident engine if there is none; on an empty memory every decision is None."""
+        embs = [np.asarray(e, dtype=np.float64).reshape(-1) for e in embs]
+        pts = [np.asarray(c[0] if isinstance(c, tuple) else c) for c in clouds_world]
+        if len(embs) != len(pts):
+            raise ValueError("associate_detections: one embedding per cloud")
+        if not pts or not self.memory:
+            return [None] * len(pts)
+        self._get_engine()
+        det = CloudBatch.from_numpy(pts, device=self.device)
+        inst, hits, _ = self._shard.overlap(det, radius=params.radius, k=params.k)
+        return association_decisions(inst, hits, [len(p) for p in pts], embs, lambda m: self.memory[m].mean_emb, params)
+
     def process_detections(self, obj_phrases, embs, obj_clouds, pose, add_noise=False, pose_noise={'trans': 0.0005, 'rot': 0.0005},
-                           depth_noise=0.003, min_points=500):
+                           depth_noise=0.003, min_points=500, associate=False, association=None):
         """process_image after perception (:187-256): obj_clouds = [(points (N, 3), colors (N, 3)), ...] in the camera frame, pose =
-        x y z qx qy qz qw (its quaternion slice is normalised in place, as the reference's transform_pointcloud does)."""
+        x y z qx qy qz qw (its quaternion slice is normalised in place, as the reference's transform_pointcloud does).
+        associate=False: every detection becomes a new instance, as the reference's will_cluster_later=True path does.
+        associate=True (what the reference's dead will_cluster_later=False loop was after, :230-235): the detections that pass
+        min_points and are no floor are first held against the memory as it stands (`associate_detections` with `association`, an
+        AssociationParams, or the defaults).  A matched detection goes into its instance (ObjectInfo.add_info: name, embedding, points,
+        means refreshed), all touched instances then through ONE `update_objects`, and the unmatched ones are appended as before.
+        Returns the decisions, one per input detection (None also for a skipped detection and for a floor), or None without
+        associate."""
         from ibloc_amd.build import transform_points
         from .object_finder_phrases import check_if_floor
         if add_noise:
@@ -190,23 +252,47 @@ class ObjectMemory():
             nq = np.linalg.norm(q)
             pose[3:] = q if nq == 0 else q / nq
             obj_clouds = [(np.asarray(p) + np.random.normal(0, depth_noise, np.asarray(p).shape), c) for p, c in obj_clouds]
-        added = []
-        for phrase, emb, (p, c) in zip(obj_phrases, embs, [(transform_points(p, pose), c) for p, c in obj_clouds]):
+        added, held = [], []
+        for k, (phrase, emb, (p, c)) in enumerate(zip(obj_phrases, embs, [(transform_points(p, pose), c) for p, c in obj_clouds])):
             if len(p) < min_points:
                 self._log(f"\t\tSkipping as number of points {len(p)} < min_points = {min_points}.")
                 continue
             info = ObjectInfo(len(self.memory), phrase, emb, Cloud(p, c), self.object_info_max_embeddings_num)
             if check_if_floor(info.names):
                 self.floors = info if self.floors is None else self.floors + info
+            elif associate:
+                held.append((k, info))
             else:
                 self.memory.append(info)
                 added.append(info)
+        decisions = None
+        if associate:
+            decisions = [None] * len(obj_phrases)
+            found = self.associate_detections([info.embeddings[0] for _, info in held], [np.asarray(info.pointcloud.points) for _, info in held],
+                                              association or AssociationParams())
+            touched, fresh = [], []
+            for (k, info), m in zip(held, found):
+                decisions[k] = m
+                if m is None:
+                    fresh.append(info)
+                else:                        # (in order: two detections of one call may go into the same instance)
+                    self.memory[m].add_info(info.names[0], info.embeddings[0], info.pointcloud)
+                    touched.append(m)
+            self._log(f"\t\tAssociation: {decisions}")
+            try:                             # the resident memory holds the instances of before the call: they are edited first
+                self.update_objects(sorted(set(touched)))
+            finally:
+                for info in fresh:
+                    info.id = len(self.memory)
+                    self.memory.append(info)
+                    added.append(info)
         if added:                        # (the floor is not part of the resident memory)
             self._appended(added)
+        return decisions
 
     def process_image(self, rgb_image_path, depth_image_path, pose, consider_floor, outlier_removal_config=DEFAULT_OUTLIER_REMOVAL_CONFIG,
                       add_noise=False, pose_noise={'trans': 0.0005, 'rot': 0.0005}, depth_noise=0.003, min_points=500,
-                      will_cluster_later=True, depth_factor=1.):
+                      will_cluster_later=True, depth_factor=1., associate=False, association=None):
         if not will_cluster_later:
             raise NotImplementedError("Only final clustering available currently")                     # :233-234
         obj_phrases, embs, obj_clouds = self._get_object_info(rgb_image_path, depth_image_path, consider_floor, outlier_removal_config,
@@ -214,7 +300,8 @@ class ObjectMemory():
         if obj_phrases is None:
             self._log("ObjectMemory.process_image did NOT find any objects")
             return
-        self.process_detections(obj_phrases, embs, obj_clouds, pose, add_noise, pose_noise, depth_noise, min_points)
+        return self.process_detections(obj_phrases, embs, obj_clouds, pose, add_noise, pose_noise, depth_noise, min_points,
+                                       associate=associate, association=association)
 
     def downsample_all_objects(self, voxel_size):
         """:258-263 -- every object (and the floor) in ONE device call (ibl_voxel_downsample_batch), bit-identical to the python loop"""

@@ -8,6 +8,7 @@ from . import _lib
 
 GEMM, ATTN, SPFH = 1, 2, 3
 ST_FEATURES, ST_FEATMATCH, ST_RANSAC, ST_ICP, ST_EVAL, ST_OUTLIER = 10, 11, 12, 13, 14, 15
+ST_ASSOC = 16                 # ibl_memgrid_overlap (live-memory association; not a stage of localise(): read it with `read`)
 PEAK_F32_VALU_TFLOPS = 157.3  # fp32 vector peak, the bound SURVEY names for RANSAC
 PEAK_F16_TFLOPS = 2500.0      # dense fp16 / bf16 MFMA (same rate), /opt/skills/guides/MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0

@@ -657,6 +657,31 @@ class MemGrid:
                                           pts4_new.data_ptr() if pts4_new.shape[0] else None, len(rb), _stream())
         _lib.check(st, "ibl_memgrid_replace")
 
+    def overlap(self, det_pts4: torch.Tensor, det_off_host, inst_off: torch.Tensor, radius, k=8, inst_off_end=None):
+        """Which instances does each detection cloud overlap (ibl_memgrid_overlap; live grids only): det_pts4 the world-frame points of
+        all detections (float32 (N, 4) on the device), det_off_host their n_det + 1 offsets, inst_off an int32 DEVICE tensor of
+        n_inst + 1 instance offsets over the grid's original point indices (a memory's `clouds.seg_off`).  hits(d, m) = the points of
+        detection d with some point of instance m at squared fp32 distance < (float)(radius * radius).  Returns numpy arrays
+        (inst (n_det, k) int32, -1 padded; hits (n_det, k) int32, 0 padded; n_hit_inst (n_det,) int32): per detection the instances
+        with hits > 0 by hits descending, then index ascending, cut to k, and their uncut number.  inst_off_end: the last entry of
+        inst_off where the caller holds it on the host (the library checks it against the grid's point count); None reads it from
+        the device.  Synchronises the current stream.  Whatever the library refuses raises IblError before anything is launched."""
+        assert det_pts4.is_cuda and det_pts4.dtype == torch.float32 and det_pts4.dim() == 2 and det_pts4.shape[1] == 4 and det_pts4.is_contiguous()
+        assert inst_off.is_cuda and inst_off.dtype == torch.int32 and inst_off.dim() == 1 and inst_off.is_contiguous() and len(inst_off) >= 2
+        off = np.ascontiguousarray(det_off_host, dtype=np.int32)
+        if len(off) < 1 or (len(off) > 1 and int(off.max()) > det_pts4.shape[0]):
+            raise ValueError("MemGrid.overlap: n_det + 1 detection offsets within the rows of det_pts4 expected")
+        n_det, n_inst, k = len(off) - 1, len(inst_off) - 1, int(k)
+        inst = np.full((n_det, max(k, 1)), -1, dtype=np.int32)          # (k < 1 is the library's to refuse)
+        hits = np.zeros((n_det, max(k, 1)), dtype=np.int32)
+        n_hit = np.zeros(n_det, dtype=np.int32)
+        end = int(inst_off[-1].item()) if inst_off_end is None else int(inst_off_end)
+        st = _lib.lib.ibl_memgrid_overlap(self.ctx.handle, self._h, inst_off.data_ptr(), n_inst, end, det_pts4.data_ptr(),
+                                          off.ctypes.data, n_det, float(radius), k, inst.ctypes.data, hits.ctypes.data, n_hit.ctypes.data,
+                                          _stream())
+        _lib.check(st, "ibl_memgrid_overlap")
+        return inst, hits, n_hit
+
     def export(self):
         """copies of the grid's arrays as device tensors: dict(sorted (n, 4) float32 -- the points in cell order --, ukeys (n_cells,)
         int64 holding the unsigned 64-bit cell keys, ustart (n_cells + 1,) int32)"""
