@@ -278,6 +278,27 @@ int64_t ibl_dator_head_workspace_bytes(int batch);
 int ibl_dator_head_forward(const ibl_dator_head_weights* w, const float* rgb_tokens, const float* depth_tokens, int batch,
                            float* out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The fp32 buffers ibl_dator_head_forward carves out of its workspace, in carving order, and what each holds once a forward
+ * pass has finished (R = batch * 128 token rows, row-major; the pass reads its offsets from the same table this query returns):
+ *   FR, FD          [R][128]  the final RGB / depth features, after all four attentions
+ *   GL              [batch][128], LP [R][128]  global (CLS) and local projections of the DEPTH side (the RGB side's are overwritten)
+ *   CAT             [R][256]  [fd | fr]: the merged features of both sides before any attention (the hyper-network's input)
+ *   H1 H2 H3 H4     [R][128], [R][32], [R][8], [R][2]  hyper-network activations (ReLU after the first three)
+ *   RGB_F, DEPTH_F  [R]       the two gates (softmax over H4)
+ *   Q_R V_R Q_D V_D [R][128]  queries / values, projected from the merged (un-updated) features
+ *   SEL [R][48], AW [R][24], SAMP [R][128], FEAT [R][128]  of the LAST attention, R2D (queries Q_R, values V_D): selectors after
+ *                   the sigmoid (x = first 24, y = last 24), attention LOGITS (the softmax is taken inside the sampler), the
+ *                   sampled and weighted values, and the ffn output that is gated into FD */
+enum {
+    IBL_DATOR_WS_FR = 0, IBL_DATOR_WS_FD, IBL_DATOR_WS_GL, IBL_DATOR_WS_LP, IBL_DATOR_WS_CAT,
+    IBL_DATOR_WS_H1, IBL_DATOR_WS_H2, IBL_DATOR_WS_H3, IBL_DATOR_WS_H4, IBL_DATOR_WS_RGB_F, IBL_DATOR_WS_DEPTH_F,
+    IBL_DATOR_WS_Q_R, IBL_DATOR_WS_V_R, IBL_DATOR_WS_Q_D, IBL_DATOR_WS_V_D,
+    IBL_DATOR_WS_SEL, IBL_DATOR_WS_AW, IBL_DATOR_WS_SAMP, IBL_DATOR_WS_FEAT, IBL_DATOR_WS_COUNT
+};
+/* offsets [host] [n], n <= IBL_DATOR_WS_COUNT: byte offsets of the first n buffers above, relative to the workspace pointer
+ * rounded up to 256 bytes.  No device call. */
+int ibl_dator_head_workspace_layout(int batch, int64_t* offsets, int n);
+
 /* Depth crops (float, [dev], crop i = sizes[2i] x sizes[2i+1] floats at src + offsets[i]) -> fp16 patch matrix of the
  * depth stream: bilinear resize to out_h x out_w (cv2.INTER_LINEAR convention), clip [dmin, dmax], (d - dmin)/(dmax - dmin),
  * (x - 0.5)/0.5, three identical channels (dator/get_embeds.py:129-136; the reference's dator_wrapper is missing). */

@@ -80,6 +80,7 @@ _SIGS = {
                                               vp, vp, vp, vp, vp, vp, vp, vp]),
     "ibl_dator_head_workspace_bytes": (C.c_int64, [C.c_int]),
     "ibl_dator_head_forward": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp]),
+    "ibl_dator_head_workspace_layout": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "ibl_preprocess_depth": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp, vp]),
     "ibl_assign_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int]),
     "ibl_assign_candidates": (C.c_int, [vp, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp,

@@ -205,6 +205,35 @@ extern "C" int64_t ibl_dator_head_workspace_bytes(int batch) {
     return (R * per_row + (int64_t)batch * 256) * 4 + 32 * 256;
 }
 
+// The workspace layout, in one place: byte offsets of the IBL_DATOR_WS_* buffers from the 256-byte-aligned workspace base, each
+// buffer on a 256-byte boundary.  The forward pass and ibl_dator_head_workspace_layout both read this table.  Returns the end.
+static int64_t dator_head_layout(int batch, int64_t offs[IBL_DATOR_WS_COUNT]) {
+    const int64_t B = batch, R = B * DT;
+    int64_t floats[IBL_DATOR_WS_COUNT];
+    floats[IBL_DATOR_WS_FR] = R * DC; floats[IBL_DATOR_WS_FD] = R * DC;
+    floats[IBL_DATOR_WS_GL] = B * DC; floats[IBL_DATOR_WS_LP] = R * DC; floats[IBL_DATOR_WS_CAT] = R * 2 * DC;
+    floats[IBL_DATOR_WS_H1] = R * 128; floats[IBL_DATOR_WS_H2] = R * 32; floats[IBL_DATOR_WS_H3] = R * 8; floats[IBL_DATOR_WS_H4] = R * 2;
+    floats[IBL_DATOR_WS_RGB_F] = R; floats[IBL_DATOR_WS_DEPTH_F] = R;
+    floats[IBL_DATOR_WS_Q_R] = R * DC; floats[IBL_DATOR_WS_V_R] = R * DC; floats[IBL_DATOR_WS_Q_D] = R * DC; floats[IBL_DATOR_WS_V_D] = R * DC;
+    floats[IBL_DATOR_WS_SEL] = R * 48; floats[IBL_DATOR_WS_AW] = R * 24; floats[IBL_DATOR_WS_SAMP] = R * DC; floats[IBL_DATOR_WS_FEAT] = R * DC;
+    int64_t p = 0;
+    for (int i = 0; i < IBL_DATOR_WS_COUNT; ++i) {
+        p = (p + 255) & ~(int64_t)255;
+        offs[i] = p;
+        p += floats[i] * 4;
+    }
+    return p;
+}
+
+extern "C" int ibl_dator_head_workspace_layout(int batch, int64_t* offsets, int n) {
+    if (batch <= 0 || !offsets || n < 0 || n > IBL_DATOR_WS_COUNT)
+        return ibl_set_error(IBL_ERR_ARG, "ibl_dator_head_workspace_layout: bad argument");
+    int64_t offs[IBL_DATOR_WS_COUNT];
+    dator_head_layout(batch, offs);
+    for (int i = 0; i < n; ++i) offsets[i] = offs[i];
+    return IBL_OK;
+}
+
 extern "C" int ibl_dator_head_forward(const ibl_dator_head_weights* w, const float* rgb_tokens, const float* depth_tokens, int batch,
                                       float* out, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!w || !rgb_tokens || !depth_tokens || !out || !workspace || batch <= 0)
@@ -212,19 +241,18 @@ extern "C" int ibl_dator_head_forward(const ibl_dator_head_weights* w, const flo
     if (workspace_bytes < ibl_dator_head_workspace_bytes(batch)) return ibl_set_error(IBL_ERR_ARG, "ibl_dator_head_forward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int B = batch, R = batch * DT, T = DT + 1, D = 768;
-    unsigned char* p = reinterpret_cast<unsigned char*>(workspace);
-    auto carve = [&](int64_t floats) {
-        p = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(p) + 255) & ~(uintptr_t)255);
-        float* r = reinterpret_cast<float*>(p);
-        p += floats * 4;
-        return r;
-    };
-    float* fr = carve((int64_t)R * DC); float* fd = carve((int64_t)R * DC);
-    float* gl = carve((int64_t)B * DC); float* lp = carve((int64_t)R * DC); float* cat = carve((int64_t)R * 2 * DC);
-    float* h1 = carve((int64_t)R * 128); float* h2 = carve((int64_t)R * 32); float* h3 = carve((int64_t)R * 8); float* h4 = carve((int64_t)R * 2);
-    float* rgb_f = carve(R); float* depth_f = carve(R);
-    float* q_r = carve((int64_t)R * DC); float* v_r = carve((int64_t)R * DC); float* q_d = carve((int64_t)R * DC); float* v_d = carve((int64_t)R * DC);
-    float* sel = carve((int64_t)R * 48); float* aw = carve((int64_t)R * 24); float* samp = carve((int64_t)R * DC); float* feat = carve((int64_t)R * DC);
+    int64_t offs[IBL_DATOR_WS_COUNT];
+    const int64_t end = dator_head_layout(batch, offs);
+    unsigned char* base = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    if ((base - reinterpret_cast<unsigned char*>(workspace)) + end > workspace_bytes)
+        return ibl_set_error(IBL_ERR_ARG, "ibl_dator_head_forward: workspace too small");
+    auto buf = [&](int i) { return reinterpret_cast<float*>(base + offs[i]); };
+    float* fr = buf(IBL_DATOR_WS_FR); float* fd = buf(IBL_DATOR_WS_FD);
+    float* gl = buf(IBL_DATOR_WS_GL); float* lp = buf(IBL_DATOR_WS_LP); float* cat = buf(IBL_DATOR_WS_CAT);
+    float* h1 = buf(IBL_DATOR_WS_H1); float* h2 = buf(IBL_DATOR_WS_H2); float* h3 = buf(IBL_DATOR_WS_H3); float* h4 = buf(IBL_DATOR_WS_H4);
+    float* rgb_f = buf(IBL_DATOR_WS_RGB_F); float* depth_f = buf(IBL_DATOR_WS_DEPTH_F);
+    float* q_r = buf(IBL_DATOR_WS_Q_R); float* v_r = buf(IBL_DATOR_WS_V_R); float* q_d = buf(IBL_DATOR_WS_Q_D); float* v_d = buf(IBL_DATOR_WS_V_D);
+    float* sel = buf(IBL_DATOR_WS_SEL); float* aw = buf(IBL_DATOR_WS_AW); float* samp = buf(IBL_DATOR_WS_SAMP); float* feat = buf(IBL_DATOR_WS_FEAT);
     int st;
     const int nb_cat = (int)(((int64_t)R * 2 * DC + 255) / 256);
     // ---- global / local projections and merge, per stream (make_model.py:680-712) ----------------------------

@@ -148,14 +148,18 @@ class DatorHeadWeights(C.Structure):
                 + [f"hyper{i}_{p}" for i in range(4) for p in ("w", "b")]]
 
 
-class DatorEncoder:
-    def __init__(self, rgb_weights: dict, depth_weights: dict, head_weights: dict, device="cuda", precision=None):
-        """precision: operand-term plan of the two streams (ibloc_amd.vit syntax; None = $IBL_VIT_PREC or DEFAULT_PRECISION below)"""
-        import os
+# workspace buffers of ibl_dator_head_forward in the order of include/ibloc.h's IBL_DATOR_WS_* enum, with their row widths
+# (0: one float per token, viewed [B, 128]; "gl" has one row per crop, every other buffer one per token)
+HEAD_TAPS = [("fr", 128), ("fd", 128), ("gl", 128), ("lp", 128), ("cat", 256), ("h1", 128), ("h2", 32), ("h3", 8), ("h4", 2),
+             ("rgb_f", 0), ("depth_f", 0), ("q_r", 128), ("v_r", 128), ("q_d", 128), ("v_d", 128),
+             ("sel", 48), ("aw", 24), ("samp", 128), ("feat", 128)]
+
+
+class DatorHead:
+    """The fusion head alone: packs the head weights for `ibl_dator_head_forward` and owns its workspaces."""
+
+    def __init__(self, head_weights: dict, device="cuda"):
         self.device = torch.device(device)
-        self.precision = precision if precision is not None else os.environ.get("IBL_VIT_PREC", DEFAULT_PRECISION)
-        self.rgb = V.VitEncoder(STREAM_CFG, fold_lora(rgb_weights), device=device, precision=self.precision)
-        self.depth = V.VitEncoder(STREAM_CFG, fold_lora(depth_weights), device=device, precision=self.precision)
         self._keep = []
         H = DatorHeadWeights()
         for name, _ in DatorHeadWeights._fields_:
@@ -176,7 +180,46 @@ class DatorEncoder:
             self._keep.append(t)
             setattr(H, name, t.data_ptr())
         self.H = H
-        self._ws = None
+        self._ws = {}
+
+    def forward(self, rgb_tokens: torch.Tensor, depth_tokens: torch.Tensor, lane: int = 0) -> torch.Tensor:
+        """fp32 token tensors (B, 129, 768) of the two streams -> (B, 128).  lane: workspace index for concurrent forwards."""
+        B = rgb_tokens.shape[0]
+        ws_bytes = _lib.lib.ibl_dator_head_workspace_bytes(B)
+        ws = self._ws.get(lane)
+        if ws is None or ws.numel() < ws_bytes:
+            ws = self._ws[lane] = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+        out = torch.empty((B, 128), dtype=torch.float32, device=self.device)
+        st = _lib.lib.ibl_dator_head_forward(C.byref(self.H), rgb_tokens.data_ptr(), depth_tokens.data_ptr(), B, out.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+        _lib.check(st, "ibl_dator_head_forward")
+        return out
+
+    def taps(self, batch: int, lane: int = 0) -> dict:
+        """Views of what the last `forward` of `batch` crops on `lane` left in its workspace (include/ibloc.h, IBL_DATOR_WS_*):
+        name -> [B*128, C] tensor ("gl": [B, C]; the gates "rgb_f" / "depth_f": [B, 128]).  The next forward overwrites them."""
+        ws = self._ws[lane]
+        offs = (C.c_int64 * len(HEAD_TAPS))()
+        _lib.check(_lib.lib.ibl_dator_head_workspace_layout(batch, offs, len(HEAD_TAPS)), "ibl_dator_head_workspace_layout")
+        base = (-ws.data_ptr()) % 256
+        out = {}
+        for (name, width), off in zip(HEAD_TAPS, offs):
+            shape = (batch, 128) if width == 0 or name == "gl" else (batch * 128, width)
+            n = shape[0] * shape[1] * 4
+            assert base + off + n <= ws.numel()
+            out[name] = ws[base + off:base + off + n].view(torch.float32).view(shape)
+        return out
+
+
+class DatorEncoder:
+    def __init__(self, rgb_weights: dict, depth_weights: dict, head_weights: dict, device="cuda", precision=None):
+        """precision: operand-term plan of the two streams (ibloc_amd.vit syntax; None = $IBL_VIT_PREC or DEFAULT_PRECISION below)"""
+        import os
+        self.device = torch.device(device)
+        self.precision = precision if precision is not None else os.environ.get("IBL_VIT_PREC", DEFAULT_PRECISION)
+        self.rgb = V.VitEncoder(STREAM_CFG, fold_lora(rgb_weights), device=device, precision=self.precision)
+        self.depth = V.VitEncoder(STREAM_CFG, fold_lora(depth_weights), device=device, precision=self.precision)
+        self._head = DatorHead(head_weights, device=device)
 
     def preprocess_depth(self, depth_crops) -> torch.Tensor:
         """list of (h, w) float depth crops, or one float32 tensor (N, h, w) of equally sized crops (host or device) -> fp16 patch
@@ -201,18 +244,7 @@ class DatorEncoder:
         return patches
 
     def head(self, rgb_tokens: torch.Tensor, depth_tokens: torch.Tensor, lane: int = 0) -> torch.Tensor:
-        B = rgb_tokens.shape[0]
-        ws_bytes = _lib.lib.ibl_dator_head_workspace_bytes(B)
-        if self._ws is None:
-            self._ws = {}
-        ws = self._ws.get(lane)
-        if ws is None or ws.numel() < ws_bytes:
-            ws = self._ws[lane] = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-        out = torch.empty((B, 128), dtype=torch.float32, device=self.device)
-        st = _lib.lib.ibl_dator_head_forward(C.byref(self.H), rgb_tokens.data_ptr(), depth_tokens.data_ptr(), B, out.data_ptr(),
-                                             ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(st, "ibl_dator_head_forward")
-        return out
+        return self._head.forward(rgb_tokens, depth_tokens, lane=lane)
 
     def forward_pixels(self, rgb: torch.Tensor, depth: torch.Tensor) -> torch.Tensor:
         """(B, 3, 256, 128) pre-normalised tensors -> (B, 128)."""
