@@ -373,7 +373,7 @@ extern "C" int ibl_dbscan_batch(ibl_reg_ctx* ctx, const double* points, const in
     hipLaunchKernelGGL(ibl_db_to_float_kernel, dim3(nb), dim3(256), 0, s, points, n, pts4);
     IBL_LAUNCH_CHECK();
     BatchGrid g;
-    st = ibl_build_batch_grid(ctx, pts4, grp_off, grp_off_host, n_grp, (float)eps, (int64_t)64 << 20, &g, s);
+    st = ibl_build_batch_grid(ctx, pts4, grp_off, grp_off_host, n_grp, (float)eps, (int64_t)64 << 20, true, &g, s);
     if (st) return st;
     IBL_ARENA(spts, double, (int64_t)3 * n);
     IBL_ARENA(core, unsigned char, n);

@@ -178,7 +178,7 @@ extern "C" int ibl_radius_outlier_batch(ibl_reg_ctx* ctx, const float* pts4, con
     void* tok;
     ibl_prof_begin(IBL_PROF_ST_OUTLIER, 13.0 * (double)seg_off_host[n_seg], s, &tok);
     st = ibl_build_batch_grid(ctx, reinterpret_cast<const float4*>(pts4), seg_off_dev, seg_off_host, n_seg, (float)radius,
-                              (int64_t)64 << 20, &g, s);
+                              (int64_t)64 << 20, true, &g, s);
     if (st) return st;
     st = ibl_launch_radius_count(g, reinterpret_cast<const float4*>(pts4), seg_off_dev, seg_off_host[n_seg], radius, nb_points, keep, s);
     ibl_prof_end(tok, s);

@@ -111,8 +111,11 @@ static inline T* arena_alloc(ibl_reg_ctx* ctx, int64_t count, bool* ok) {
 #define IBL_ST_RANSAC_REDONE 32      // (sticky, informational) a registration call was redone with a full-size survivor list
 
 // grid construction (reg_grid.hip)
+// max_cells is the budget of the full-size grids.  collapse = true: a segment that does not fit collapses to one cell (slow, correct,
+// IBL_ST_GRID_OVERFLOW is set; each collapsed segment adds its one cell, if need be past the budget).  collapse = false: the call
+// fails with IBL_ERR_OVERFLOW instead and the caller chooses a larger cell.
 int ibl_build_batch_grid(ibl_reg_ctx* ctx, const float4* pts, const int* seg_off_dev, const int* seg_off_host, int n_seg,
-                         float cell, int64_t max_cells, BatchGrid* out, hipStream_t s);
+                         float cell, int64_t max_cells, bool collapse, BatchGrid* out, hipStream_t s);
 // The same grid without the read-back of the table size: `cells_bound` (>= the number of cells the dims kernel will find, e.g. from
 // bounding boxes the host already holds) sizes the tables; a segment that does not fit collapses to one cell (status bit).
 int ibl_build_batch_grid_bounded(ibl_reg_ctx* ctx, const float4* pts, const int* seg_off_dev, const int* seg_off_host, int n_seg,

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(256) void ibl_grid_dims_kernel(const float* __restr
     __shared__ long long carry;
     __shared__ int overflow_at;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) { carry = 0; overflow_at = -1; }
+    if (tid == 0) { carry = 0; overflow_at = n_seg; }      // n_seg = none: atomicMin lowers it to the first segment that does not fit
     __syncthreads();
     for (int base = 0; base < n_seg; base += 256) {
         const int s = base + tid;
@@ -100,9 +101,9 @@ __global__ __launch_bounds__(256) void ibl_grid_dims_kernel(const float* __restr
         __syncthreads();
         if (tid == 0) carry += wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
         __syncthreads();
-        if (overflow_at >= 0) break;
+        if (overflow_at < n_seg) break;
     }
-    if (overflow_at >= 0) {
+    if (overflow_at < n_seg) {
         // budget exceeded: from the first offending segment on, the serial rule (that segment and every later one that does not
         // fit collapse to one cell; the status bit tells the host)
         if (tid == 0) {
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(256) void ibl_grid_dims_kernel(const float* __restr
         }
         return;
     }
-    if (tid == 0) *total_cells = (int)carry;
+    if (tid == 0) *total_cells = (int)(carry > INT_MAX ? (long long)INT_MAX : carry);
 }
 
 __global__ __launch_bounds__(256) void ibl_cell_id_kernel(const float4* __restrict__ pts, const int* __restrict__ seg_off, int n_seg,
@@ -185,7 +186,7 @@ static int grid_fill(ibl_reg_ctx* ctx, const float4* pts, const int* seg_off_dev
 }
 
 int ibl_build_batch_grid(ibl_reg_ctx* ctx, const float4* pts, const int* seg_off_dev, const int* seg_off_host, int n_seg,
-                         float cell, int64_t max_cells, BatchGrid* out, hipStream_t s) {
+                         float cell, int64_t max_cells, bool collapse, BatchGrid* out, hipStream_t s) {
     const int n = seg_off_host[n_seg];
     float* bbox; SegGrid* seg; int* total;
     IBL_ARENA(bbox, float, (int64_t)n_seg * 6 + 6);
@@ -196,13 +197,18 @@ int ibl_build_batch_grid(ibl_reg_ctx* ctx, const float4* pts, const int* seg_off
     if (n_seg == 0) return IBL_OK;
     hipLaunchKernelGGL(ibl_bbox_kernel, dim3(n_seg), dim3(256), 0, s, pts, seg_off_dev, bbox);
     IBL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ibl_grid_dims_kernel, dim3(1), dim3(256), 0, s, bbox, n_seg, cell, (long long)max_cells, seg, total,
-                       ctx->d_status);
+    // without `collapse` the kernel sees no budget: it reports the full-size total and the check below refuses it
+    hipLaunchKernelGGL(ibl_grid_dims_kernel, dim3(1), dim3(256), 0, s, bbox, n_seg, cell, collapse ? (long long)max_cells : LLONG_MAX, seg,
+                       total, ctx->d_status);
     IBL_LAUNCH_CHECK();
     int h_total = 0;
     IBL_HIP_CHECK(hipMemcpyAsync(&h_total, total, sizeof(int), hipMemcpyDeviceToHost, s));
     IBL_HIP_CHECK(hipStreamSynchronize(s));     // the table size decides the scan length (one small read-back per grid)
-    if (h_total <= 0 || h_total > max_cells) return ibl_set_error(IBL_ERR_OVERFLOW, "grid: %d cells exceed the budget %lld", h_total, (long long)max_cells);
+    // The budget bounds the full-size grids.  A collapsed segment still owns one cell, placed after whatever came before it, so the
+    // table may run past the budget by one cell per collapsed segment (segments that fill the budget exactly leave no cell inside
+    // it); grid_fill sizes its tables from h_total.
+    if (h_total <= 0 || h_total > max_cells + (collapse ? n_seg : 0))
+        return ibl_set_error(IBL_ERR_OVERFLOW, "grid: %d cells exceed the budget %lld", h_total, (long long)max_cells);
     return grid_fill(ctx, pts, seg_off_dev, n_seg, n, seg, h_total, out, s);
 }
 

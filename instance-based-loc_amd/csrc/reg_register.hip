@@ -191,7 +191,7 @@ static int build_grid_c(ibl_reg_ctx* ctx, RegPass& ps) {
     for (int tries = 0; have && bound >= budget && tries < 12; ++tries) { cellC *= 1.5f; bound = grid_c_cell_bound(ps, cellC); }
     if (have && bound < budget) return ibl_build_batch_grid_bounded(ctx, ps.P, ps.d_piece_off, piece_off.data(), 4 * J, cellC, bound, &ps.gC, s);
     for (int tries = 0; tries < 8; ++tries) {
-        st = ibl_build_batch_grid(ctx, ps.P, ps.d_piece_off, piece_off.data(), 4 * J, cellC, budget, &ps.gC, s);
+        st = ibl_build_batch_grid(ctx, ps.P, ps.d_piece_off, piece_off.data(), 4 * J, cellC, budget, false, &ps.gC, s);
         if (st != IBL_ERR_OVERFLOW) break;
         cellC *= 2.0f;
     }
