@@ -639,9 +639,13 @@ __global__ __launch_bounds__(256) void ibl_evaluate_kernel(MemGridView g, const 
         const float qx = (float)p[0], qy = (float)p[1], qz = (float)p[2];
         float best = thr2;
         bool found = false;
-        const int x0 = (int)floorf((qx - thr) * g.inv), x1 = (int)floorf((qx + thr) * g.inv);
-        const int y0 = (int)floorf((qy - thr) * g.inv), y1 = (int)floorf((qy + thr) * g.inv);
-        const int z0 = (int)floorf((qz - thr) * g.inv), z1 = (int)floorf((qz + thr) * g.inv);
+        // The box is padded as the overlap kernel's is: a hit has |q - m| < thr (1 + 3 * 2^-24) per axis (the roundings of thr2, of the
+        // difference and of its square), not |q - m| < (float)thr.  For a threshold whose float, squared in fp32, lies below thr2 (0.021,
+        // 0.036: not 0.02) a difference of exactly (float)thr is a hit, and q - thr = 0 put a point 1e-10 below 0 one cell outside.
+        const float px = thr * 1.000001f + 2.4e-7f * fabsf(qx), py = thr * 1.000001f + 2.4e-7f * fabsf(qy), pz = thr * 1.000001f + 2.4e-7f * fabsf(qz);
+        const int x0 = (int)floorf((qx - px) * g.inv), x1 = (int)floorf((qx + px) * g.inv);
+        const int y0 = (int)floorf((qy - py) * g.inv), y1 = (int)floorf((qy + py) * g.inv);
+        const int z0 = (int)floorf((qz - pz) * g.inv), z1 = (int)floorf((qz + pz) * g.inv);
         // The query's own cell first, then the (up to seven) others of its +-thr box only while they can still hold a closer point:
         // a neighbouring cell lies behind the face it shares with the own cell, so the distance to that face (per axis that differs) bounds
         // every point of it from below.  Round 4: an inlier's nearest point is millimetres away and the faces are centimetres away, so ~1.5
@@ -725,8 +729,13 @@ extern "C" int ibl_evaluate_batch(ibl_reg_ctx* ctx, const ibl_memgrid* grid, con
     const int prune = !ctx->diag.eval_fullscan;          // diagnostics: full scan = every cell of the query's box (the tests compare both)
     void* tok;
     ibl_prof_begin(IBL_PROF_ST_EVAL, 24.0 * (double)(jobs[J - 1].out + (jobs[J - 1].end - jobs[J - 1].begin)), s, &tok);
-    hipLaunchKernelGGL(ibl_evaluate_kernel, dim3(ICP_BPJ, J), dim3(256), 0, s, grid->v, reinterpret_cast<const float4*>(det_pts4), d_jobs,
-                       (float)threshold, (float)(threshold * threshold), partial, d2_out, prune);
+    // gridDim.y holds at most 65 535 rows: more jobs go in several launches.  A launch numbers its jobs from 0, so it is given its part
+    // of the jobs and of the partials; job.out stays an offset into the whole of d2_out.
+    const int max_rows = 65535;
+    for (int j0 = 0; j0 < J; j0 += max_rows)
+        hipLaunchKernelGGL(ibl_evaluate_kernel, dim3(ICP_BPJ, std::min(J - j0, max_rows)), dim3(256), 0, s, grid->v,
+                           reinterpret_cast<const float4*>(det_pts4), d_jobs + j0, (float)threshold, (float)(threshold * threshold),
+                           partial + (int64_t)j0 * ICP_BPJ * 2, d2_out, prune);
     ibl_prof_end(tok, s);
     IBL_LAUNCH_CHECK();
     std::vector<double> h((size_t)J * ICP_BPJ * 2);

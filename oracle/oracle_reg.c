@@ -700,6 +700,34 @@ void oracle_correspondences(const float* src, int ns, const float* tgt, int nt, 
     grid_free(&g);
 }
 
+/* The same decision with no grid at all (tests/evaluate_cases.py: the reference of the whole-memory evaluation, which may not share a
+ * cell lookup with what it checks): every source point is transformed in double and rounded to fp32, then compared with EVERY target
+ * point by dist2f.  d2_out[i] = the smallest distance strictly below (float)(max_dist * max_dist), or +inf; idx_out[i] = the lowest
+ * target index that attains it, or -1.  (The walk ascends and replaces on `<` only: the first of equal distances stays.) */
+void oracle_nearest_bruteforce(const float* src, int ns, const float* tgt, int nt, const double T[16], double max_dist, float* d2_out,
+                               int32_t* idx_out) {
+    const float r2 = (float)(max_dist * max_dist);
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < ns; ++i) {
+        double sp[3] = {src[3 * i], src[3 * i + 1], src[3 * i + 2]}, p[3];
+        xform(T, sp, p);
+        const float qf[3] = {(float)p[0], (float)p[1], (float)p[2]};
+        float bd = r2; int best = -1;
+        for (int j = 0; j < nt; ++j) {
+            /* dist2f with its first product looked at early: the two fmaf() only add squares to it and rounding is monotone, so
+             * d2 >= dx * dx, and a target whose dx * dx alone is not below the best cannot replace it */
+            const float* t = tgt + 3 * j;
+            const float dx = qf[0] - t[0], xx = dx * dx;
+            if (!(xx < bd)) continue;
+            const float dy = qf[1] - t[1], dz = qf[2] - t[2];
+            const float d2 = fmaf(dz, dz, fmaf(dy, dy, xx));
+            if (d2 < bd) { bd = d2; best = j; }
+        }
+        d2_out[i] = best >= 0 ? bd : INFINITY;
+        idx_out[i] = best;
+    }
+}
+
 /* ------------------------------------------------------------------------------------------ */
 /* coloured ICP                                                                                 */
 /* ------------------------------------------------------------------------------------------ */

@@ -106,6 +106,17 @@ def correspondences(src, tgt, T, max_dist):
     return corr
 
 
+def nearest_bruteforce(src, tgt, T, max_dist):
+    """the fp32 rule with no grid: (d2 float32, +inf when none; idx int32, -1 when none) of every transformed source point against
+    every target point, strictly below (float)(max_dist^2), the lowest index among equal distances"""
+    src, tgt = _f32(src), _f32(tgt)
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+    d2 = np.zeros(len(src), dtype=np.float32)
+    idx = np.zeros(len(src), dtype=np.int32)
+    lib.oracle_nearest_bruteforce(_p(src), C.c_int(len(src)), _p(tgt), C.c_int(len(tgt)), _p(T), C.c_double(max_dist), _p(d2), _p(idx))
+    return d2, idx
+
+
 def register_point_clouds(src, src_int, tgt, tgt_int, voxel_size, global_dist_factor=1.5, local_dist_factor=0.4, seed=0,
                           job_id=0, ransac_max_iter=4000000, have_colors=True, src_raw=None, tgt_raw=None):
     """== utils/fpfh_register.py:100-143; returns (T 4x4, inlier_rmse, fitness, T_ransac, ransac_stats).

@@ -6,7 +6,7 @@ Tolerances (parity at the Open3D boundary is unpinned; the checker is the oracle
     agreed; the RANSAC stage itself must agree bit-for-bit in its statistics for >= 80 % of the jobs (a single
     differing feature correspondence changes the draw -> hypothesis mapping) and in every case land within
     the ICP basin (final poses agree);
-  * evaluate: fitness within 2 points, rmse within 1e-5."""
+  * evaluate: equal inlier counts (fitness equal), rmse within 1e-5."""
 import numpy as np
 import pytest
 import torch
@@ -109,7 +109,9 @@ def test_evaluate_batch_vs_oracle(ctx, scene):
     all_mem = np.concatenate(w.points).astype(np.float32)
     for j, (b, T) in enumerate(zip([0, 0, det.seg_off_host[1]], Ts)):
         er, ef = ro.evaluate(all_det[b:], all_mem, T, 0.02)
-        assert abs(ef - fit[j]) <= 2.0 / (n - b) and abs(er - rmse[j]) < 1e-5, (j, ef, fit[j], er, rmse[j])
+        # equal inlier counts: the oracle's 27-cell scan at cell = radius is the exact fp32 rule, and so is the device's evaluation
+        # (tests/test_gpu_evaluate.py holds every point to the brute force of that rule); both divide the count by n in double
+        assert ef == fit[j] and abs(er - rmse[j]) < 1e-5, (j, ef, fit[j], er, rmse[j])
     assert fit[0] > fit[2] > fit[1]
     grid.close()
 
