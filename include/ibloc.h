@@ -60,12 +60,17 @@ int ibl_prof_read(int id, double* ms, double* units, int64_t* launches);
 #define IBL_VIT_OUT_ALL_TOKENS 32 /* return every token (DATOR/TransReID local_feature=True)       */
 #define IBL_VIT_ACT_TERMS2 64     /* some block has o_terms / fc2_terms = 2: attention output / hidden layer as rows of 2 terms  */
 #define IBL_VIT_ACT_TERMS3 128    /* ... = 3: rows of 3 terms (sizes the workspace)                                             */
+#define IBL_VIT_NO_CLS 256        /* no class token (SigLIP): n_tokens is the patch count, `patches` is [batch*n_tokens][patch_k_pad], patch p of crop b
+                                     goes to row b*n_tokens + p, pos_patch has n_tokens rows and cls_pos is not read (may be NULL).  Needs
+                                     IBL_VIT_OUT_ALL_TOKENS -- there is no row to return otherwise: refused with IBL_ERR_UNSUPPORTED before any launch */
+#define IBL_VIT_TANH_GELU 512     /* fc1 activation 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) (gelu_pytorch_tanh: SigLIP) in place of erf GELU;
+                                     together with IBL_VIT_QUICK_GELU it is refused                  */
 #define IBL_VIT_SPLIT_SCALE 64.0f /* S of the two-term operands below                              */
 
 typedef struct {
     int32_t dim, depth, heads, mlp_dim;
     int32_t patch, img_h, img_w;   /* model input size after preprocessing                          */
-    int32_t n_tokens;              /* 1 + (img_h/patch)*(img_w/patch)                               */
+    int32_t n_tokens;              /* 1 + (img_h/patch)*(img_w/patch); without the 1 with IBL_VIT_NO_CLS */
     int32_t patch_k_pad;           /* 3*patch*patch rounded up to a multiple of 64 (zero padded)    */
     int32_t flags;                 /* IBL_VIT_*                                                     */
     int32_t n_blocks_run;          /* blocks actually executed (DATOR runs depth-1)                 */
@@ -112,8 +117,8 @@ typedef struct {                   /* all [dev]; weights fp16 [N][K] row-major (
 typedef struct {
     const void* w_patch;           /* fp16 [dim][patch_k_pad]: conv weight flattened (c, kh, kw)     */
     const float* b_patch;          /* [dim] or NULL                                                  */
-    const float* cls_pos;          /* [dim]: cls_token + position_embedding[0]                       */
-    const float* pos_patch;        /* [n_tokens-1][dim]: position embeddings of the patch tokens,
+    const float* cls_pos;          /* [dim]: cls_token + position_embedding[0]; not read with IBL_VIT_NO_CLS */
+    const float* pos_patch;        /* [n_tokens-1][dim] ([n_tokens][dim] with IBL_VIT_NO_CLS): position embeddings of the patch tokens,
                                       already interpolated to the (img_h/patch, img_w/patch) grid    */
     const float* ln_pre_g; const float* ln_pre_b;
     const float* ln_f_g;   const float* ln_f_b;
@@ -162,7 +167,7 @@ int ibl_preprocess_crops(const uint8_t* src, const ibl_crop_desc* descs, int n_c
 
 /* ViT forward over a batch of crops.  Replaces the batch-1 torch forward of
  * utils/embeddings.py:46,69,93 and dator/model/backbones/vit_pytorch.py:422-443.
- *   patches [dev] fp16 [batch*(n_tokens-1)][patch_k_pad] (from ibl_preprocess_crops)
+ *   patches [dev] fp16 [batch*(n_tokens-1)][patch_k_pad] (from ibl_preprocess_crops; batch*n_tokens rows with IBL_VIT_NO_CLS)
  *   out     [dev] fp32 [batch][out_dim]  (CLS embedding; un-normalised, like the reference), or
  *           fp32 [batch][n_tokens][dim] with IBL_VIT_OUT_ALL_TOKENS */
 int64_t ibl_vit_workspace_bytes(const ibl_vit_desc* desc, int batch);
@@ -202,7 +207,10 @@ int ibl_linear_f16(const void* x, int64_t ldx, const void* W, int64_t ldw, const
  *   patches_per_crop, part of a crop, pos NULL without accumulate, an unknown epilogue, an activation other than 0 / 1 and a non-zero
  *   activation with an epilogue that has none are refused with a status before any launch.  The field lies in what was the tail padding
  *   of the struct (its size stays 112): zero the descriptor before filling it, a garbage tail is refused, not obeyed. */
-enum { IBL_ACT_GELU_ERF = 0, IBL_ACT_QUICK_GELU = 1 };
+/* IBL_ACT_GELU_TANH (0.5 v (1 + tanh(sqrt(2/pi) (v + 0.044715 v^3))), what IBL_VIT_TANH_GELU runs in the encoder) is NOT taken by
+ * ibl_linear_f16_ex, whose contract -- every activation other than 0 / 1 is refused -- stays as it was; it is an argument of
+ * ibl_linear_f16_act below. */
+enum { IBL_ACT_GELU_ERF = 0, IBL_ACT_QUICK_GELU = 1, IBL_ACT_GELU_TANH = 2 };
 typedef struct {
     const void* x;  int64_t ldx;       /* fp16 [rows][ldx]                                              */
     const void* W;  int64_t ldw;       /* fp16 [n_out][ldw]                                             */
@@ -218,6 +226,12 @@ typedef struct {
     int32_t activation;                /* IBL_ACT_* (IBL_LINEAR_GELU_F16 / _X2 / _X3), 0 elsewhere       */
 } ibl_linear_desc;
 int ibl_linear_f16_ex(const ibl_linear_desc* desc, void* stream);
+
+/* ibl_linear_f16_ex with the activation as an argument: IBL_ACT_GELU_ERF, IBL_ACT_QUICK_GELU or IBL_ACT_GELU_TANH.  Validation, kernel
+ * and launch are those of ibl_linear_f16_ex; with activation 0 or 1 the result is that entry's bit for bit.  desc->activation must be 0
+ * (the argument is the activation); a non-zero `activation` is accepted with IBL_LINEAR_GELU_F16 / _X2 / _X3 only; any other value, and
+ * everything ibl_linear_f16_ex refuses, is refused with a status before any launch. */
+int ibl_linear_f16_act(const ibl_linear_desc* desc, int activation, void* stream);
 
 /* The encoder's attention on its own: out = softmax(q k^T / 8) v per (crop, head), head_dim 64 -- what transformers'
  * ViTSelfAttention / Dinov2SelfAttention and open_clip's nn.MultiheadAttention compute inside the encoders of
@@ -298,6 +312,51 @@ enum {
 /* offsets [host] [n], n <= IBL_DATOR_WS_COUNT: byte offsets of the first n buffers above, relative to the workspace pointer
  * rounded up to 256 bytes.  No device call. */
 int ibl_dator_head_workspace_layout(int batch, int64_t* offsets, int n);
+
+/* ------------------------------------------------------------------------------------------ */
+/* SigLIP attention-pooling head (transformers' SiglipMultiheadAttentionPoolingHead)            */
+/* ------------------------------------------------------------------------------------------ */
+
+/* One learned probe attends over a crop's tokens.  The query is a constant, so the key and value projections over all tokens fold away:
+ *   score[b][h][t] = x[b][t] . u[h],  u[h] = W_k,h^T q_h / sqrt(head_dim)   (host, float64; q_h . b_k,h is constant over t and cancels)
+ *   p = softmax_t(score),  pooled[b][h] = sum_t p[b][h][t] x[b][t]           (then W_v,h pooled[b][h] + b_v,h per head)
+ * ibl_probe_pool_f32 is that kernel alone, fp32 throughout: one workgroup per crop, u and the probabilities in LDS, every reduction in a
+ * fixed order without floating-point atomics -- a crop's result does not depend on the batch it runs in, bit for bit.
+ *   x      [dev] fp32 [batch][n_tokens][dim], 16-byte aligned       u [dev] fp32 [heads][dim], 16-byte aligned
+ *   pooled [dev] fp32 [batch][heads][dim], 16-byte aligned          probs [dev] fp32 [batch][heads][n_tokens] or NULL (same pooled either way)
+ * batch >= 1, n_tokens >= 1, heads in 1..16, dim % 4 == 0, dim <= 1024, dim % heads == 0, heads * (dim + n_tokens) * 4 bytes within the
+ * 160 KiB of LDS; null pointers and everything else are refused with a status before any launch and leave the outputs untouched. */
+int ibl_probe_pool_f32(const float* x, int batch, int n_tokens, int dim, int heads, const float* u, float* pooled, float* probs, void* stream);
+
+typedef struct {
+    int32_t dim, heads, mlp_dim, n_tokens;
+    float ln_eps;
+} ibl_probe_head_desc;
+
+typedef struct {                   /* all [dev] fp32; linear weights [out][in] row-major (nn.Linear layout) */
+    const float* u;                /* [heads][dim], see above                                        */
+    const float* w_v; const float* b_v;       /* [dim][dim], [dim]: rows h*head_dim .. of in_proj_weight's value part (head h reads pooled[b][h]) */
+    const float* w_o; const float* b_o;       /* [dim][dim], [dim]: attention.out_proj                */
+    const float* ln_g; const float* ln_b;     /* [dim]: head.layernorm                                */
+    const float* w_fc1; const float* b_fc1;   /* [mlp_dim][dim], [mlp_dim]: head.mlp.fc1 (tanh GELU behind it) */
+    const float* w_fc2; const float* b_fc2;   /* [dim][mlp_dim], [dim]: head.mlp.fc2                  */
+} ibl_probe_head_weights;
+
+/* The whole head: tokens [dev] fp32 [batch][n_tokens][dim] (ibl_vit_forward with IBL_VIT_OUT_ALL_TOKENS | IBL_VIT_FINAL_LN) ->
+ * out [dev] fp32 [batch][dim] = a + fc2(gelu_tanh(fc1(LayerNorm(a)))), a = out_proj(concat_h(W_v,h pooled_h + b_v,h)): the model's
+ * pooler_output, un-normalised.  fp32 throughout (the head is the last arithmetic before the output).  A row's result does not depend on
+ * batch.  The limits of ibl_probe_pool_f32 apply; mlp_dim a positive multiple of 4; tokens, u and the four weight matrices 16-byte aligned; a
+ * workspace smaller than ibl_probe_head_workspace_bytes is refused. */
+int64_t ibl_probe_head_workspace_bytes(const ibl_probe_head_desc* desc, int batch);
+int ibl_probe_head_forward(const ibl_probe_head_desc* desc, const ibl_probe_head_weights* weights, const float* tokens, int batch,
+                           float* out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The fp32 buffers ibl_probe_head_forward carves out of its workspace, in carving order, and what each holds after a forward pass:
+ *   PROBS [batch][heads][n_tokens], POOLED [batch][heads][dim], VCAT [batch][dim] (per-head value projections, concatenated),
+ *   ATT [batch][dim] (out_proj: the residual), LN [batch][dim], HID [batch][mlp_dim] (after the activation)
+ * offsets [host] [n], n <= IBL_PROBE_WS_COUNT: byte offsets relative to the workspace pointer rounded up to 256 bytes.  No device call. */
+enum { IBL_PROBE_WS_PROBS = 0, IBL_PROBE_WS_POOLED, IBL_PROBE_WS_VCAT, IBL_PROBE_WS_ATT, IBL_PROBE_WS_LN, IBL_PROBE_WS_HID, IBL_PROBE_WS_COUNT };
+int ibl_probe_head_workspace_layout(const ibl_probe_head_desc* desc, int batch, int64_t* offsets, int n);
 
 /* Depth crops (float, [dev], crop i = sizes[2i] x sizes[2i+1] floats at src + offsets[i]) -> fp16 patch matrix of the
  * depth stream: bilinear resize to out_h x out_w (cv2.INTER_LINEAR convention), clip [dmin, dmax], (d - dmin)/(dmax - dmin),

@@ -47,6 +47,7 @@ _SIGS = {
     "ibl_vit_workspace_bytes": (C.c_int64, [vp, C.c_int]),
     "ibl_linear_f16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp]),
     "ibl_linear_f16_ex": (C.c_int, [vp, vp]),
+    "ibl_linear_f16_act": (C.c_int, [vp, C.c_int, vp]),
     "ibl_vit_forward": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp]),
     "ibl_attention_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ibl_attention_stream_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
@@ -81,6 +82,10 @@ _SIGS = {
     "ibl_dator_head_workspace_bytes": (C.c_int64, [C.c_int]),
     "ibl_dator_head_forward": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp]),
     "ibl_dator_head_workspace_layout": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "ibl_probe_pool_f32": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "ibl_probe_head_workspace_bytes": (C.c_int64, [vp, C.c_int]),
+    "ibl_probe_head_forward": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp]),
+    "ibl_probe_head_workspace_layout": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "ibl_preprocess_depth": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp, vp]),
     "ibl_assign_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int]),
     "ibl_assign_candidates": (C.c_int, [vp, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp,

@@ -59,7 +59,9 @@ enum { EPI_BIAS_H16 = 0, EPI_BIAS_GELU_H16 = 1, EPI_RESID_F32 = 2, EPI_PATCH_F32
        EPI_BIAS_GELU_H16KX2 = 6, EPI_BIAS_GELU_H16KX3 = 7,
        // internal (not in ibloc.h's enum; reached through ibl_linear_desc.activation and IBL_VIT_QUICK_GELU): epilogues 1, 6 and 7 with
        // QuickGELU, v * sigmoid(1.702 v), in place of the erf form -- everything after the activation is the same code
-       EPI_BIAS_QGELU_H16 = 8, EPI_BIAS_QGELU_H16KX2 = 9, EPI_BIAS_QGELU_H16KX3 = 10 };
+       EPI_BIAS_QGELU_H16 = 8, EPI_BIAS_QGELU_H16KX2 = 9, EPI_BIAS_QGELU_H16KX3 = 10,
+       // likewise internal (ibl_linear_f16_act's IBL_ACT_GELU_TANH and IBL_VIT_TANH_GELU): the three with the tanh form of GELU (SigLIP)
+       EPI_BIAS_TGELU_H16 = 11, EPI_BIAS_TGELU_H16KX2 = 12, EPI_BIAS_TGELU_H16KX3 = 13 };
 
 struct GemmEpi {
     const float* bias;      // [N] or null
@@ -69,6 +71,7 @@ struct GemmEpi {
     int64_t ldo;            // output row stride (elements)
     int tokens_per_crop;    // T (EPI_PATCH)
     int patches_per_crop;   // P (EPI_PATCH)
+    int patch_row0;         // EPI_PATCH: the row of a crop its patch 0 goes to, i.e. the crop's prefix rows (the encoder: T - P -- 1 with a class token, 0 without; ibl_linear_f16_ex: 1, whatever T)
     int accumulate;         // EPI_PATCH: x += alpha * acc instead of x = acc + bias + pos (second weight term of a two-term operand)
     float alpha;
     int algo_k;             // K the in-process timer counts as algorithmic (0: K itself; -1: none -- extra terms of a two-term operand are overhead, not model FLOPs)
@@ -139,6 +142,26 @@ __device__ __forceinline__ f32x2 quick_gelu2(f32x2 v) {
     return v * r;
 }
 
+// tanh GELU (gelu_pytorch_tanh: SigLIP), 0.5 v (1 + tanh(z)) with z = sqrt(2 / pi) (v + 0.044715 v^3).  1 + tanh(z) = 2 / (1 + exp(-2 z)), so the
+// value is v * rcp(1 + exp2(c w)) with w = v (1 + 0.044715 v^2) and c = -2 log2(e) sqrt(2 / pi): the shape of quick_gelu2 with a cubic in
+// front -- a packed multiply, a packed fma, two more packed multiplies, an exp2 and a rcp per element.  v << 0 (from v = -10.07 on, c w >= 128):
+// exp2 overflows to +inf, rcp gives 0 and the result is -0; v >> 0: exp2 underflows to 0 and the result is v.  v^2 may overflow to +inf
+// (|v| > 1.8e19): w is then +-inf with the sign of v and both ends behave as above.  r is in [0, 1] and v finite, so no finite v gives a NaN.
+__device__ __forceinline__ f32x2 tanh_gelu2(f32x2 v) {
+    const f32x2 u = v * v;
+    const f32x2 k = u * 0.044715f + 1.0f;
+    const f32x2 w = v * k;
+    const f32x2 a = w * -2.3022081985131374f;
+    f32x2 e;
+    e.x = __builtin_amdgcn_exp2f(a.x);
+    e.y = __builtin_amdgcn_exp2f(a.y);
+    const f32x2 d = e + 1.0f;
+    f32x2 r;
+    r.x = __builtin_amdgcn_rcpf(d.x);
+    r.y = __builtin_amdgcn_rcpf(d.y);
+    return v * r;
+}
+
 #ifdef IBL_GEMM_STAMPS     // lab builds only (tools/perf_gemm.py --stamps): phase clocks of every tile a (persistent) block walks
 // [block < 512][tile iteration < 16][4]: 0 = tile loop top, 1 = first stage landed (after the barrier), 2 = K loop done, 3 = epilogue issued
 __device__ long long ibl_gemm_stamps[512 * 16 * 4];
@@ -186,9 +209,10 @@ __global__ __launch_bounds__(T256 ? 512 : 256, T256 ? 1 : 2) void ibl_gemm_f16_t
     // fp16 epilogues: MFMA row 4 fg + r of n-tile j is weight row 32 (j / 2) + 8 fg + 4 (j % 2) + r: a lane owns 8 consecutive
     // columns (one 16-byte store) of n-tile pair j / 2 and the four lane groups cover 64 contiguous bytes of the row
     constexpr bool QGELU = EPI == EPI_BIAS_QGELU_H16 || EPI == EPI_BIAS_QGELU_H16KX2 || EPI == EPI_BIAS_QGELU_H16KX3;
-    constexpr int GT = (EPI == EPI_BIAS_GELU_H16KX3 || EPI == EPI_BIAS_QGELU_H16KX3) ? 3
-                       : ((EPI == EPI_BIAS_GELU_H16KX2 || EPI == EPI_BIAS_QGELU_H16KX2) ? 2 : 1);     // column blocks the fp16 epilogue writes
-    constexpr bool GELU = EPI == EPI_BIAS_GELU_H16 || GT > 1 || QGELU;
+    constexpr bool TGELU = EPI == EPI_BIAS_TGELU_H16 || EPI == EPI_BIAS_TGELU_H16KX2 || EPI == EPI_BIAS_TGELU_H16KX3;
+    constexpr int GT = (EPI == EPI_BIAS_GELU_H16KX3 || EPI == EPI_BIAS_QGELU_H16KX3 || EPI == EPI_BIAS_TGELU_H16KX3) ? 3
+                       : ((EPI == EPI_BIAS_GELU_H16KX2 || EPI == EPI_BIAS_QGELU_H16KX2 || EPI == EPI_BIAS_TGELU_H16KX2) ? 2 : 1);     // column blocks the fp16 epilogue writes
+    constexpr bool GELU = EPI == EPI_BIAS_GELU_H16 || GT > 1 || QGELU || TGELU;
     constexpr bool PAIR = EPI == EPI_BIAS_H16 || GELU;
     constexpr int PAIR_STORES = GT * 2 * MI;          // stores per lane of a full tile's fp16 epilogue
 #define KEYW(r) (NAT ? key_act(r) : (PAIR ? key_pair(r) : key_w(r)))
@@ -634,7 +658,7 @@ __global__ __launch_bounds__(T256 ? 512 : 256, T256 ? 1 : 2) void ibl_gemm_f16_t
             _Pragma("unroll") for (int t = 0; t < 8; t += 2) {                                                                      \
                 f32x2 x = {acc[I][2 * j2 + (t >> 2)][t & 3], acc[I][2 * j2 + (t >> 2)][(t & 3) + 1]};                               \
                 x += f32x2{bb[j2][t], bb[j2][t + 1]};                                                                               \
-                if (GELU) x = QGELU ? quick_gelu2(x) : gelu_erf2(x);                                                                \
+                if (GELU) x = QGELU ? quick_gelu2(x) : (TGELU ? tanh_gelu2(x) : gelu_erf2(x));                                      \
                 v[t] = x.x; v[t + 1] = x.y;                                                                                         \
             }                                                                                                                       \
             const uint4 hi4 = make_uint4(f2h_pk(v[0], v[1]), f2h_pk(v[2], v[3]), f2h_pk(v[4], v[5]), f2h_pk(v[6], v[7]));           \
@@ -688,7 +712,8 @@ __global__ __launch_bounds__(T256 ? 512 : 256, T256 ? 1 : 2) void ibl_gemm_f16_t
             for (int r = 0; r < 4; ++r) v[4 * j + r] = acc[i][j][r] + bias[4 * j + r];
         if (EPI == EPI_PATCH_F32) {
             const int b = row / epi.patches_per_crop, p = row - b * epi.patches_per_crop;
-            const int64_t orow = (int64_t)b * epi.tokens_per_crop + 1 + p;
+            // the patch rows follow the crop's prefix rows (the CLS token; none with IBL_VIT_NO_CLS)
+            const int64_t orow = (int64_t)b * epi.tokens_per_crop + epi.patch_row0 + p;
             float4* o = reinterpret_cast<float4*>(reinterpret_cast<float*>(epi.out) + orow * epi.ldo + n0);
             if (epi.accumulate) {
 #pragma unroll
@@ -1280,22 +1305,40 @@ static bool pow2_positive(float a) {
     return a >= 1.17549435e-38f && a <= 3.0e38f && frexpf(a, &e) == 0.5f;
 }
 
+// ibl_linear_f16_ex and ibl_linear_f16_act: one validation, one launch.  `act` is the activation the GELU epilogues apply (d->activation is
+// not read here), `act_max` the largest one the entry takes, `fn` the entry's name for the messages.
+static int linear_f16_run(const ibl_linear_desc* d, int act, int act_max, void* stream, const char* fn);
+
 extern "C" int ibl_linear_f16_ex(const ibl_linear_desc* d, void* stream) {
     if (!d) return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: null descriptor");
     if (d->rows == 0) return IBL_OK;
-    if (!d->x || !d->W || !d->out) return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: null operand");
-    if (d->rows < 0 || d->rows > 0x7fffffff) return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: rows out of range");
+    // 0 and 1 only, as before IBL_ACT_GELU_TANH existed: the tanh form comes through ibl_linear_f16_act
+    return linear_f16_run(d, d->activation, IBL_ACT_QUICK_GELU, stream, "ibl_linear_f16_ex");
+}
+
+extern "C" int ibl_linear_f16_act(const ibl_linear_desc* d, int activation, void* stream) {
+    if (!d) return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_act: null descriptor");
+    if (d->activation != 0)
+        return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_act: the descriptor's activation field (%d) must be 0: the activation is the argument", d->activation);
+    if (activation < IBL_ACT_GELU_ERF || activation > IBL_ACT_GELU_TANH)
+        return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_act: unknown activation %d (0, 1 or 2)", activation);
+    if (d->rows == 0) return IBL_OK;
+    return linear_f16_run(d, activation, IBL_ACT_GELU_TANH, stream, "ibl_linear_f16_act");
+}
+
+static int linear_f16_run(const ibl_linear_desc* d, int act, int act_max, void* stream, const char* fn) {
+    if (!d->x || !d->W || !d->out) return ibl_set_error(IBL_ERR_ARG, "%s: null operand", fn);
+    if (d->rows < 0 || d->rows > 0x7fffffff) return ibl_set_error(IBL_ERR_ARG, "%s: rows out of range", fn);
     const int n_out = d->n_out, n_in = d->n_in, epi = d->epilogue;
     if (n_out <= 0 || n_in <= 0 || n_out % 128 != 0 || n_in % GBK != 0)
-        return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: n_out (%d) must be a positive multiple of 128 and n_in (%d) of 64", n_out, n_in);
-    if (epi < EPI_BIAS_H16 || epi > EPI_BIAS_GELU_H16KX3) return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: unknown epilogue %d", epi);
+        return ibl_set_error(IBL_ERR_ARG, "%s: n_out (%d) must be a positive multiple of 128 and n_in (%d) of 64", fn, n_out, n_in);
+    if (epi < EPI_BIAS_H16 || epi > EPI_BIAS_GELU_H16KX3) return ibl_set_error(IBL_ERR_ARG, "%s: unknown epilogue %d", fn, epi);
     const bool gelu = epi == EPI_BIAS_GELU_H16 || epi == EPI_BIAS_GELU_H16KX2 || epi == EPI_BIAS_GELU_H16KX3;
-    if (d->activation != IBL_ACT_GELU_ERF && !(gelu && d->activation == IBL_ACT_QUICK_GELU))
-        return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: activation %d with epilogue %d (0, or 1 with a GELU epilogue)", d->activation, epi);
-    const bool quick = d->activation == IBL_ACT_QUICK_GELU;
+    if (act != IBL_ACT_GELU_ERF && !(gelu && act > 0 && act <= act_max))
+        return ibl_set_error(IBL_ERR_ARG, "%s: activation %d with epilogue %d (0, or a known one with a GELU epilogue)", fn, act, epi);
     const int terms = epi == EPI_BIAS_GELU_H16KX3 ? 3 : (epi == EPI_BIAS_GELU_H16KX2 ? 2 : 1);
     if ((d->ldx & 7) || (d->ldw & 7) || (d->ldo & 7) || d->ldx < n_in || d->ldw < n_in || d->ldo < (int64_t)terms * n_out)
-        return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: row strides must be >= the row length (%d in, %d out) and multiples of 8 elements",
+        return ibl_set_error(IBL_ERR_ARG, "%s: row strides must be >= the row length (%d in, %d out) and multiples of 8 elements", fn,
                              n_in, terms * n_out);
     GemmEpi e{};
     e.bias = d->bias;
@@ -1303,18 +1346,19 @@ extern "C" int ibl_linear_f16_ex(const ibl_linear_desc* d, void* stream) {
     e.ldo = d->ldo;
     if (epi == EPI_RESID_F32) e.scale = d->scale;
     if (epi == EPI_RESID_PRE_F32 || (epi == EPI_PATCH_F32 && d->accumulate)) {
-        if (!pow2_positive(d->alpha)) return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: alpha (%g) must be a positive power of two", (double)d->alpha);
+        if (!pow2_positive(d->alpha)) return ibl_set_error(IBL_ERR_ARG, "%s: alpha (%g) must be a positive power of two", fn, (double)d->alpha);
         e.alpha = d->alpha;
     }
     if (epi == EPI_PATCH_F32) {
         if (d->patches_per_crop <= 0 || d->tokens_per_crop <= d->patches_per_crop || d->rows % d->patches_per_crop != 0)
-            return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: patch scatter needs 0 < patches_per_crop (%d) < tokens_per_crop (%d) and whole crops (%lld rows)",
+            return ibl_set_error(IBL_ERR_ARG, "%s: patch scatter needs 0 < patches_per_crop (%d) < tokens_per_crop (%d) and whole crops (%lld rows)", fn,
                                  d->patches_per_crop, d->tokens_per_crop, (long long)d->rows);
-        if (d->accumulate != 0 && d->accumulate != 1) return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: accumulate must be 0 or 1");
-        if (!d->accumulate && !d->pos) return ibl_set_error(IBL_ERR_ARG, "ibl_linear_f16_ex: null position rows without accumulate");
+        if (d->accumulate != 0 && d->accumulate != 1) return ibl_set_error(IBL_ERR_ARG, "%s: accumulate must be 0 or 1", fn);
+        if (!d->accumulate && !d->pos) return ibl_set_error(IBL_ERR_ARG, "%s: null position rows without accumulate", fn);
         e.pos = d->pos;
         e.tokens_per_crop = d->tokens_per_crop;
         e.patches_per_crop = d->patches_per_crop;
+        e.patch_row0 = 1;                  // this entry's contract: row b * tokens_per_crop + 1 + p, also where tokens_per_crop > patches_per_crop + 1
         e.accumulate = d->accumulate;
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -1324,18 +1368,21 @@ extern "C" int ibl_linear_f16_ex(const ibl_linear_desc* d, void* stream) {
     switch (epi) {
         case EPI_BIAS_H16: return launch_gemm<EPI_BIAS_H16>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
         case EPI_BIAS_GELU_H16:
-            return quick ? launch_gemm<EPI_BIAS_QGELU_H16>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s)
-                         : launch_gemm<EPI_BIAS_GELU_H16>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
+            return act == IBL_ACT_QUICK_GELU  ? launch_gemm<EPI_BIAS_QGELU_H16>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s)
+                   : act == IBL_ACT_GELU_TANH ? launch_gemm<EPI_BIAS_TGELU_H16>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s)
+                                              : launch_gemm<EPI_BIAS_GELU_H16>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
         case EPI_RESID_F32: return launch_gemm<EPI_RESID_F32>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
         case EPI_PATCH_F32: return launch_gemm<EPI_PATCH_F32>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
         case EPI_BIAS_F32: return launch_gemm<EPI_BIAS_F32>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
         case EPI_RESID_PRE_F32: return launch_gemm<EPI_RESID_PRE_F32>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
         case EPI_BIAS_GELU_H16KX2:
-            return quick ? launch_gemm<EPI_BIAS_QGELU_H16KX2>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s)
-                         : launch_gemm<EPI_BIAS_GELU_H16KX2>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
+            return act == IBL_ACT_QUICK_GELU  ? launch_gemm<EPI_BIAS_QGELU_H16KX2>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s)
+                   : act == IBL_ACT_GELU_TANH ? launch_gemm<EPI_BIAS_TGELU_H16KX2>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s)
+                                              : launch_gemm<EPI_BIAS_GELU_H16KX2>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
         default:
-            return quick ? launch_gemm<EPI_BIAS_QGELU_H16KX3>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s)
-                         : launch_gemm<EPI_BIAS_GELU_H16KX3>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
+            return act == IBL_ACT_QUICK_GELU  ? launch_gemm<EPI_BIAS_QGELU_H16KX3>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s)
+                   : act == IBL_ACT_GELU_TANH ? launch_gemm<EPI_BIAS_TGELU_H16KX3>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s)
+                                              : launch_gemm<EPI_BIAS_GELU_H16KX3>(a, d->ldx, w, d->ldw, rows, n_out, n_in, e, s);
     }
 }
 
@@ -1475,7 +1522,13 @@ extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, 
                                float* out, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!d || !w || !patches || !out || !workspace) return ibl_set_error(IBL_ERR_ARG, "ibl_vit_forward: null pointer");
     if (batch <= 0) return ibl_set_error(IBL_ERR_ARG, "ibl_vit_forward: batch must be positive");
-    const int D = d->dim, T = d->n_tokens, P = T - 1, H = d->heads;
+    const bool no_cls = (d->flags & IBL_VIT_NO_CLS) != 0;
+    const int D = d->dim, T = d->n_tokens, P = no_cls ? T : T - 1, H = d->heads;
+    if (no_cls && !(d->flags & IBL_VIT_OUT_ALL_TOKENS))
+        return ibl_set_error(IBL_ERR_UNSUPPORTED, "ibl_vit_forward: IBL_VIT_NO_CLS needs IBL_VIT_OUT_ALL_TOKENS: without a class token there is no row to return");
+    if ((d->flags & IBL_VIT_QUICK_GELU) && (d->flags & IBL_VIT_TANH_GELU))
+        return ibl_set_error(IBL_ERR_ARG, "ibl_vit_forward: IBL_VIT_QUICK_GELU and IBL_VIT_TANH_GELU are both set");
+    if (no_cls && T < 1) return ibl_set_error(IBL_ERR_ARG, "ibl_vit_forward: n_tokens %d with IBL_VIT_NO_CLS", T);
     if (D != H * 64) return ibl_set_error(IBL_ERR_UNSUPPORTED, "ibl_vit_forward: head_dim must be 64");
     if (D % 128 || d->mlp_dim % 128 || d->patch_k_pad % 64 || D > 1024)
         return ibl_set_error(IBL_ERR_UNSUPPORTED, "ibl_vit_forward: dim/mlp_dim %% 128, patch_k_pad %% 64, dim <= 1024");
@@ -1506,6 +1559,7 @@ extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, 
     {
         GemmEpi e{};
         e.bias = w->b_patch; e.pos = w->pos_patch; e.out = x; e.ldo = D; e.tokens_per_crop = T; e.patches_per_crop = P;
+        e.patch_row0 = T - P;              // the prefix rows of a crop: general, so that a longer prefix (register tokens) needs no change here
         st = launch_gemm<EPI_PATCH_F32>(reinterpret_cast<const u16*>(patches), d->patch_k_pad,
                                         reinterpret_cast<const u16*>(w->w_patch), d->patch_k_pad, batch * P, D,
                                         d->patch_k_pad, e, s);
@@ -1518,10 +1572,12 @@ extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, 
                                             d->patch_k_pad, e2, s);
             if (st) return st;
         }
-        const int64_t n = (int64_t)batch * D;
-        hipLaunchKernelGGL(ibl_set_cls_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, w->cls_pos, batch,
-                           T, D);
-        IBL_LAUNCH_CHECK();
+        if (!no_cls) {
+            const int64_t n = (int64_t)batch * D;
+            hipLaunchKernelGGL(ibl_set_cls_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, w->cls_pos, batch,
+                               T, D);
+            IBL_LAUNCH_CHECK();
+        }
     }
     if (d->flags & IBL_VIT_PRE_LN) {
         // CLIP ln_pre: normalise the residual stream in place (through the fp16-free f32 path)
@@ -1596,6 +1652,10 @@ extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, 
                 if (f2t == 3) st = launch_gemm<EPI_BIAS_QGELU_H16KX3>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
                 else if (f2t == 2) st = launch_gemm<EPI_BIAS_QGELU_H16KX2>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
                 else st = launch_gemm<EPI_BIAS_QGELU_H16>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
+            } else if (d->flags & IBL_VIT_TANH_GELU) {
+                if (f2t == 3) st = launch_gemm<EPI_BIAS_TGELU_H16KX3>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
+                else if (f2t == 2) st = launch_gemm<EPI_BIAS_TGELU_H16KX2>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
+                else st = launch_gemm<EPI_BIAS_TGELU_H16>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
             } else if (f2t == 3) st = launch_gemm<EPI_BIAS_GELU_H16KX3>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
             else if (f2t == 2) st = launch_gemm<EPI_BIAS_GELU_H16KX2>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);
             else st = launch_gemm<EPI_BIAS_GELU_H16>(mlp_in, (int64_t)ft * D, w1, (int64_t)ft * D, mlp_rows, d->mlp_dim, ft * D, e, s);

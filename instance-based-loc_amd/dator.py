@@ -236,7 +236,7 @@ class DatorEncoder:
         d_sizes = torch.from_numpy(sizes).to(self.device)
         d_offs = torch.from_numpy(offs).to(self.device)
         cfg = STREAM_CFG
-        patches = torch.empty((n * (cfg.n_tokens - 1), cfg.patch_k_pad), dtype=torch.float16, device=self.device)
+        patches = torch.empty((n * cfg.n_patches, cfg.patch_k_pad), dtype=torch.float16, device=self.device)
         st = _lib.lib.ibl_preprocess_depth(flat.data_ptr(), d_offs.data_ptr(), d_sizes.data_ptr(), n, cfg.img_h, cfg.img_w, cfg.patch,
                                            cfg.patch_k_pad, float(MIN_DEPTH), float(MAX_DEPTH), patches.data_ptr(),
                                            torch.cuda.current_stream().cuda_stream)

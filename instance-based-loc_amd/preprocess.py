@@ -9,6 +9,7 @@ The per-model recipes mirror what the reference's embedding functions do on the 
   * CLIP    (utils/embeddings.py:41-42): swap, open_clip preprocess: shortest edge -> 224 (bicubic),
     centre crop 224, CLIP mean/std.
   * DATOR   (dator/get_embeds.py:80-87): resize to 256x128 (H x W, bilinear), mean = std = 0.5.
+  * SigLIP  (no reference function; transformers' SiglipImageProcessor): swap, resize to the model size (bicubic), mean = std = 0.5.
 
 The coefficient tables are Pillow's (`precompute_coeffs` + `normalize_coeffs_8bpc` of
 libImaging/Resample.c, restated here in float64 numpy): for every output sample a first tap, a tap
@@ -16,6 +17,7 @@ count and 22-bit fixed-point weights.  The device then does pure integer arithme
 u8 result bit-identical to PIL.Image.resize (checked against PIL in tests/).
 """
 import ctypes as C
+import dataclasses
 import math
 from dataclasses import dataclass
 
@@ -107,6 +109,17 @@ RECIPES = {
     "dinov2_518": PreprocessRecipe("dinov2_518", 518, 518, "shortest", 592, BICUBIC, True, IMAGENET_MEAN, IMAGENET_STD),
     "dator_rgb": PreprocessRecipe("dator_rgb", 256, 128, "exact", 0, BILINEAR, False, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)),
 }
+# SigLIP (transformers' SiglipImageProcessor through PIL): exact resize to the model size (bicubic), no crop, x / 255, mean = std = 0.5.
+# The entry is the 224 px form; `recipe_for` gives the 256 / 384 px towers the same recipe at their own size
+RECIPES["siglip"] = PreprocessRecipe("siglip", 224, 224, "exact", 0, BICUBIC, True, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5))
+
+
+def recipe_for(name: str, out_h: int, out_w: int) -> PreprocessRecipe:
+    """RECIPES[name]; "siglip" (an exact resize, no crop window) follows the model's input size where that differs from the entry's"""
+    r = RECIPES[name]
+    if name == "siglip" and (r.out_h, r.out_w) != (out_h, out_w):
+        r = dataclasses.replace(r, out_h=out_h, out_w=out_w)
+    return r
 
 
 def resized_size(recipe: PreprocessRecipe, in_h: int, in_w: int):

@@ -3,7 +3,7 @@
 The reference loads four encoders at import time by fetching checkpoints by name
 (/root/reference/utils/embeddings.py:13-28, 101-103) and embeds ONE crop per call.  Here the encoders are
 `ibloc_amd.vit.VitEncoder` objects (HIP kernels behind the C-ABI) registered once with `set_encoder(kind, encoder)`
-or built from a converted checkpoint with `load_encoder(kind, state_dict)` (kinds "dino" | "vit" | "clip" | "dator"); the four reference entry points keep
+or built from a converted checkpoint with `load_encoder(kind, state_dict)` (kinds "dino" | "vit" | "clip" | "dator" | "siglip"); the four reference entry points keep
 their names and `(**kwargs) -> torch.Tensor` signature:
 
     get_all_clip_embeddings   :31-50   L2-normalised 512-d
@@ -114,6 +114,32 @@ def hf_clip_to_weights(sd: dict, depth: int) -> dict:
     return w
 
 
+def hf_siglip_to_weights(sd: dict, depth: int):
+    """transformers `SiglipVisionModel.state_dict()` or `SiglipModel.state_dict()` (the text tower's keys and the logit scale / bias are
+    ignored), with or without the `vision_model.` prefix -> (trunk weights, head weights): the dicts `ibloc_amd.siglip.SiglipEncoder` takes.
+    The pooling head's fused `in_proj_weight` / `in_proj_bias` are split into q / k / v."""
+    v = "vision_model." if any(k.startswith("vision_model.") for k in sd) else ""
+    g = lambda k: np.asarray(sd[v + k].float().cpu() if hasattr(sd[v + k], "float") else sd[v + k], dtype=np.float32)
+    w = {"patch.w": g("embeddings.patch_embedding.weight"), "patch.b": g("embeddings.patch_embedding.bias"),
+         "pos": g("embeddings.position_embedding.weight"), "ln_f.g": g("post_layernorm.weight"), "ln_f.b": g("post_layernorm.bias")}
+    for l in range(depth):
+        p, q = f"encoder.layers.{l}.", f"l{l}."
+        w[q + "ln1.g"], w[q + "ln1.b"] = g(p + "layer_norm1.weight"), g(p + "layer_norm1.bias")
+        w[q + "ln2.g"], w[q + "ln2.b"] = g(p + "layer_norm2.weight"), g(p + "layer_norm2.bias")
+        for hf, mine in (("q_proj", "q"), ("k_proj", "k"), ("v_proj", "v"), ("out_proj", "o")):
+            w[q + mine + ".w"], w[q + mine + ".b"] = g(p + f"self_attn.{hf}.weight"), g(p + f"self_attn.{hf}.bias")
+        w[q + "fc1.w"], w[q + "fc1.b"] = g(p + "mlp.fc1.weight"), g(p + "mlp.fc1.bias")
+        w[q + "fc2.w"], w[q + "fc2.b"] = g(p + "mlp.fc2.weight"), g(p + "mlp.fc2.bias")
+    D = w["pos"].shape[1]
+    wi, bi = g("head.attention.in_proj_weight"), g("head.attention.in_proj_bias")
+    hw = {"probe": g("head.probe").reshape(-1), "o.w": g("head.attention.out_proj.weight"), "o.b": g("head.attention.out_proj.bias"),
+          "ln.g": g("head.layernorm.weight"), "ln.b": g("head.layernorm.bias"), "fc1.w": g("head.mlp.fc1.weight"),
+          "fc1.b": g("head.mlp.fc1.bias"), "fc2.w": g("head.mlp.fc2.weight"), "fc2.b": g("head.mlp.fc2.bias")}
+    for i, mine in enumerate("qkv"):
+        hw[mine + ".w"], hw[mine + ".b"] = wi[i * D:(i + 1) * D].copy(), bi[i * D:(i + 1) * D].copy()
+    return w, hw
+
+
 def clip_converter(state_dict):
     """the converter of a CLIP vision state dict, from its key layout: `vision_model.*` is transformers', `conv1.weight` open_clip's
     `model.visual` (OpenAI's released checkpoints use the same names)"""
@@ -138,7 +164,10 @@ def load_encoder(kind: str, state_dict, device="cuda", cfg: V.VitConfig = None):
     "dator": `state_dict` is a `build_FourDNet` checkpoint as the reference's `load_model('.../dator_best_tum.pth')` reads it
     (utils/embeddings.py:101-103, make_model.py:620-626) -- the dict itself or the path of the `.pth` file (loaded with
     `weights_only=True`: a checkpoint is data) -> `ibloc_amd.dator.DatorEncoder` (`module.` prefix stripped, `classifier*` skipped, LoRA
-    folded into the QKV weights)."""
+    folded into the QKV weights).
+
+    "siglip": a transformers `SiglipVisionModel` / `SiglipModel` state dict -> `ibloc_amd.siglip.SiglipEncoder` (trunk + attention-pooling
+    head); cfg defaults to "siglip_b16_224", the other towers are "siglip_b16_256" / "_384" and "siglip_l16_256" / "_384"."""
     if kind == "dator":
         from ibloc_amd import dator as D
         if isinstance(state_dict, (str, bytes)) or hasattr(state_dict, "__fspath__"):
@@ -149,6 +178,13 @@ def load_encoder(kind: str, state_dict, device="cuda", cfg: V.VitConfig = None):
         return enc
     if isinstance(cfg, str):
         cfg = V.CONFIGS[cfg]
+    if kind == "siglip":
+        from ibloc_amd import siglip as S
+        cfg = cfg or V.CONFIGS["siglip_b16_224"]
+        tw, hw = hf_siglip_to_weights(state_dict, cfg.depth)
+        enc = S.SiglipEncoder(cfg, tw, hw, device=device)
+        set_encoder(kind, enc)
+        return enc
     cfg = cfg or V.CONFIGS[_KIND_TO_CONFIG[kind]]
     conv = clip_converter(state_dict) if kind == "clip" else {"dino": hf_dinov2_to_weights, "vit": hf_vit_to_weights}[kind]
     enc = V.VitEncoder(cfg, conv(state_dict, cfg.depth), device=device)
@@ -183,6 +219,11 @@ def get_all_dino_embeddings(**kwargs) -> torch.Tensor:
 
 def get_all_vit_embeddings(**kwargs) -> torch.Tensor:
     return embed_batch("vit", [kwargs["current_obj_grounded_img"]])[0]
+
+
+def get_all_siglip_embeddings(**kwargs) -> torch.Tensor:
+    """SigLIP pooler_output of the crop, un-normalised (no counterpart in the reference: the crop is treated as the other three do)"""
+    return embed_batch("siglip", [kwargs["current_obj_grounded_img"]])[0]
 
 
 def get_dator_embeddings(**kwargs) -> torch.Tensor:

@@ -21,6 +21,8 @@ FLAG_PROJ = 16
 FLAG_OUT_ALL_TOKENS = 32
 FLAG_ACT_TERMS2 = 64         # IBL_VIT_ACT_TERMS2 / 3: some block takes the input of a residual GEMM as K-extended rows of 2 / 3 terms
 FLAG_ACT_TERMS3 = 128
+FLAG_NO_CLS = 256            # IBL_VIT_NO_CLS: the sequence is the patch tokens alone (SigLIP)
+FLAG_TANH_GELU = 512         # IBL_VIT_TANH_GELU: fc1 activation gelu_pytorch_tanh (SigLIP)
 MAX_LAYERS = 32
 
 
@@ -127,6 +129,8 @@ class VitConfig:
     recipe: str = "dinov2"
     pos_interp: str = "hf-4.44"    # how stored position embeddings are resampled to the run grid
     quick_gelu: bool = False       # fc1 activation x * sigmoid(1.702 x) (OpenAI CLIP) instead of erf GELU: IBL_VIT_QUICK_GELU
+    cls_token: bool = True         # False (SigLIP): no class token, `pos` is (gh * gw, D) and used as stored: IBL_VIT_NO_CLS
+    tanh_gelu: bool = False        # fc1 activation 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) (SigLIP): IBL_VIT_TANH_GELU
 
     @property
     def grid(self):
@@ -134,7 +138,11 @@ class VitConfig:
 
     @property
     def n_tokens(self):
-        return 1 + self.grid[0] * self.grid[1]
+        return int(self.cls_token) + self.grid[0] * self.grid[1]
+
+    @property
+    def n_patches(self):
+        return self.grid[0] * self.grid[1]
 
     @property
     def patch_k(self):
@@ -189,6 +197,25 @@ CONFIGS = {
 }
 
 
+def _siglip(name, dim, depth, heads, mlp, px):
+    """a SigLIP vision tower (google/siglip-*-patch16-*, the fixed-resolution SigLIP 2 checkpoints): ViT/16 without a class token, tanh
+    GELU, final LayerNorm over every token -- the trunk ibloc_amd.siglip.SiglipEncoder puts its attention-pooling head on"""
+    return VitConfig(name, dim, depth, heads, mlp, 16, px, px, (px // 16, px // 16), final_ln=True, ln_eps=1e-6, out_all_tokens=True,
+                     recipe="siglip", cls_token=False, tanh_gelu=True)
+
+
+CONFIGS.update({
+    # 196 / 256 tokens: the resident attention kernel; 576: the streaming one.  So400m (head_dim 72, mlp 4304) is not supported
+    "siglip_b16_224": _siglip("siglip_b16_224", 768, 12, 12, 3072, 224),
+    "siglip_b16_256": _siglip("siglip_b16_256", 768, 12, 12, 3072, 256),
+    "siglip_b16_384": _siglip("siglip_b16_384", 768, 12, 12, 3072, 384),
+    "siglip_l16_256": _siglip("siglip_l16_256", 1024, 24, 16, 4096, 256),
+    "siglip_l16_384": _siglip("siglip_l16_384", 1024, 24, 16, 4096, 384),
+    "tiny_siglip": _siglip("tiny_siglip", 128, 2, 2, 256, 224),
+    "tiny_siglip_384": _siglip("tiny_siglip_384", 128, 2, 2, 256, 384),
+})
+
+
 def random_weights(cfg: VitConfig, seed: int):
     """Seeded synthetic weights (no pretrained checkpoints exist offline): trunc-normal-ish N(0, 0.02)
     matrices, LayerNorm gains around 1, LayerScale around 1 -- numpy fp32, keyed like the oracle expects."""
@@ -201,7 +228,7 @@ def random_weights(cfg: VitConfig, seed: int):
         "patch.w": mat(cfg.dim, 3, cfg.patch, cfg.patch),
         "patch.b": mat(cfg.dim),
         "cls": mat(cfg.dim),
-        "pos": mat(1 + cfg.pos_grid[0] * cfg.pos_grid[1], cfg.dim),
+        "pos": mat(int(cfg.cls_token) + cfg.pos_grid[0] * cfg.pos_grid[1], cfg.dim),
         "ln_f.g": (1 + mat(cfg.dim, std=0.1)),
         "ln_f.b": mat(cfg.dim, std=0.1),
     }
@@ -306,7 +333,17 @@ class VitEncoder:
             self._keep.append(t)
             return t.data_ptr()
 
-        pos = interpolate_pos_embed(weights["pos"], cfg)
+        if cfg.quick_gelu and cfg.tanh_gelu:
+            raise ValueError("quick_gelu and tanh_gelu are both set")
+        if cfg.cls_token:
+            pos = interpolate_pos_embed(weights["pos"], cfg)
+        else:
+            # no class token: the table is (gh * gw, D) and used as stored (resampling it is not supported)
+            if not cfg.out_all_tokens:
+                raise ValueError("cls_token=False needs out_all_tokens: there is no class row to return")
+            pos = np.ascontiguousarray(weights["pos"], dtype=np.float32)
+            if tuple(cfg.pos_grid) != tuple(cfg.grid) or pos.shape != (cfg.n_patches, cfg.dim):
+                raise ValueError(f"cls_token=False: the position table {pos.shape} of grid {cfg.pos_grid} must be that of the run grid {cfg.grid}")
         wp = np.zeros((cfg.dim, cfg.patch_k_pad), dtype=np.float32)
         wp[:, :cfg.patch_k] = weights["patch.w"].reshape(cfg.dim, -1)
         W = VitWeights()
@@ -314,8 +351,11 @@ class VitEncoder:
         if patch_terms == 2:
             W.w_patch_lo = dev_f16(weight_lo(wp))
         W.b_patch = dev_f32(weights["patch.b"]) if "patch.b" in weights else None
-        W.cls_pos = dev_f32(weights["cls"].reshape(-1) + pos[0])
-        W.pos_patch = dev_f32(pos[1:])
+        if cfg.cls_token:
+            W.cls_pos = dev_f32(weights["cls"].reshape(-1) + pos[0])
+            W.pos_patch = dev_f32(pos[1:])
+        else:
+            W.pos_patch = dev_f32(pos)
         if cfg.pre_ln:
             W.ln_pre_g, W.ln_pre_b = dev_f32(weights["ln_pre.g"]), dev_f32(weights["ln_pre.b"])
         if cfg.final_ln:
@@ -380,11 +420,13 @@ class VitEncoder:
         flags |= FLAG_PROJ if cfg.proj_dim else 0
         flags |= FLAG_QUICK_GELU if cfg.quick_gelu else 0
         flags |= FLAG_OUT_ALL_TOKENS if cfg.out_all_tokens else 0
+        flags |= FLAG_TANH_GELU if cfg.tanh_gelu else 0
+        flags |= 0 if cfg.cls_token else FLAG_NO_CLS
         flags |= {1: 0, 2: FLAG_ACT_TERMS2, 3: FLAG_ACT_TERMS3}[getattr(self, "_act_terms", 1)]
         nrun = cfg.depth if cfg.n_blocks_run < 0 else cfg.n_blocks_run
         self.desc = VitDesc(cfg.dim, cfg.depth, cfg.heads, cfg.mlp_dim, cfg.patch, cfg.img_h, cfg.img_w, cfg.n_tokens,
                             cfg.patch_k_pad, flags, nrun, cfg.out_dim, cfg.ln_eps)
-        self.recipe = pp.RECIPES[cfg.recipe]
+        self.recipe = pp.recipe_for(cfg.recipe, cfg.img_h, cfg.img_w)
         self._ws = None
         self._plan_cache = {}
 
@@ -415,7 +457,7 @@ class VitEncoder:
         d_descs, d_tables, src_bytes, tmp_bytes, max_h = plan
         assert src.numel() == src_bytes
         n = len(shapes)
-        P = self.cfg.n_tokens - 1
+        P = self.cfg.n_patches
         tmp = torch.empty(max(tmp_bytes, 16), dtype=torch.uint8, device=self.device)
         patches = torch.empty((n * P, self.cfg.patch_k_pad), dtype=torch.float16, device=self.device)
         out_u8 = torch.empty((n, r.out_h, r.out_w, 3), dtype=torch.uint8, device=self.device) if want_u8 else None
@@ -432,7 +474,7 @@ class VitEncoder:
     # ---- forward -------------------------------------------------------------------------------
     def forward_patches(self, patches: torch.Tensor, lane: int = 0) -> torch.Tensor:
         """lane: which of the encoder's workspaces to use (concurrent forwards on different streams need their own)."""
-        P = self.cfg.n_tokens - 1
+        P = self.cfg.n_patches
         assert patches.dtype == torch.float16 and patches.is_cuda and patches.shape[1] == self.cfg.patch_k_pad
         batch = patches.shape[0] // P
         ws_bytes = _lib.lib.ibl_vit_workspace_bytes(C.byref(self.desc), batch)
@@ -507,6 +549,7 @@ class LinearDesc(C.Structure):              # ibl_linear_desc (include/ibloc.h)
 
 
 ACT_GELU_ERF, ACT_QUICK_GELU = 0, 1         # IBL_ACT_*: what LINEAR_GELU_F16 / _X2 / _X3 apply
+ACT_GELU_TANH = 2                           # through linear_f16_act only: ibl_linear_f16_ex refuses it
 
 
 def linear_f16(x: torch.Tensor, W: torch.Tensor, bias=None, epilogue=LINEAR_F16, out=None, scale=None) -> torch.Tensor:
@@ -551,6 +594,24 @@ def linear_f16_ex(x: torch.Tensor, W: torch.Tensor, out: torch.Tensor, epilogue,
                    out.stride(0), x.shape[0], W.shape[0], x.shape[1], int(epilogue), int(accumulate), int(tokens_per_crop),
                    int(patches_per_crop), float(alpha), int(activation))
     _lib.check(_lib.lib.ibl_linear_f16_ex(C.byref(d), torch.cuda.current_stream().cuda_stream), "ibl_linear_f16_ex")
+    return out
+
+
+def linear_f16_act(x: torch.Tensor, W: torch.Tensor, out: torch.Tensor, epilogue, activation, bias=None, scale=None, pos=None, alpha=1.0,
+                   accumulate=False, tokens_per_crop=0, patches_per_crop=0) -> torch.Tensor:
+    """`ibl_linear_f16_act`: `linear_f16_ex` with the activation as an argument of the call -- ACT_GELU_ERF, ACT_QUICK_GELU or
+    ACT_GELU_TANH (the tanh form of GELU, SigLIP's); the descriptor's own activation field stays 0.  Everything else as `linear_f16_ex`."""
+    for t in (x, W, out):
+        assert t.is_cuda and t.dim() == 2 and t.stride(1) == 1
+    assert x.dtype == torch.float16 and W.dtype == torch.float16
+    assert out.dtype == (torch.float16 if epilogue in (LINEAR_F16, LINEAR_GELU_F16, LINEAR_GELU_F16_X2, LINEAR_GELU_F16_X3) else torch.float32)
+    for t in (bias, scale, pos):
+        assert t is None or (t.dtype == torch.float32 and t.is_cuda and t.is_contiguous())
+    d = LinearDesc(x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), bias.data_ptr() if bias is not None else None,
+                   scale.data_ptr() if scale is not None else None, pos.data_ptr() if pos is not None else None, out.data_ptr(),
+                   out.stride(0), x.shape[0], W.shape[0], x.shape[1], int(epilogue), int(accumulate), int(tokens_per_crop),
+                   int(patches_per_crop), float(alpha), 0)
+    _lib.check(_lib.lib.ibl_linear_f16_act(C.byref(d), int(activation), torch.cuda.current_stream().cuda_stream), "ibl_linear_f16_act")
     return out
 
 
