@@ -20,7 +20,7 @@
  *     never synchronise.  Functions that return HOST results synchronise the stream -- how often is stated per function:
  *     ibl_radius_outlier_batch 1 (grid table size), ibl_instance_features_batch 2 (bounding boxes; end),
  *     ibl_register_jobs 2-4 (one per group of RANSAC rounds -- most calls need one -- plus the results; one more when
- *     instances of a job lie within the influence radius of each other), ibl_evaluate_batch 1, ibl_memgrid_overlap 1, ibl_memgrid_build / _append / _remove / _replace 2
+ *     instances of a job lie within the influence radius of each other), ibl_evaluate_batch 1, ibl_evaluate_information 1, ibl_memgrid_overlap 1, ibl_memgrid_build / _append / _remove / _replace 2
  *     (cell count; end; one more when the call has to reallocate the other point buffer).  Plan tables are staged through pinned host memory of the registration context, so uploads never wait.
  *   - plain C types only; no torch types in any signature.
  */
@@ -797,6 +797,29 @@ int ibl_memgrid_overlap(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const int32_t
 int ibl_evaluate_batch(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float* det_pts4, const int32_t* job_begin,
                        const int32_t* job_end, const double* T_global, int n_jobs, double threshold, float* d2_out /* [dev] or NULL */,
                        double* rmse_out, double* fitness_out, void* stream);
+
+/* get_information_matrix_from_point_clouds (the third member of Open3D's registration trio) for n_jobs poses against the whole
+ * memory: the 6 x 6 matrix sum G^T G over the correspondences of T_global[j], rotation first, then translation.
+ *   Correspondences: those of ibl_evaluate_batch -- q = (float)(T p) for the detected points [job_begin[j], job_end[j]), its match the
+ *   memory point m of the grid with the smallest fp32 d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)), accepted when d2 < (float)(threshold *
+ *   threshold).  n_corr_out[j] / (job_end[j] - job_begin[j]) is ibl_evaluate_batch's fitness exactly.  Among memory points at the same
+ *   minimal d2 the match is the one with the lexicographically smallest (x, y, z), compared as floats: the result depends on the SET
+ *   of memory points only, not on cell order, pruning or live edits (a live grid gives the bits of a grid built at once).
+ *   Matrix: with (x, y, z) = (double)m - about, rows G1 = [0, z, -y, 1, 0, 0], G2 = [-z, 0, x, 0, 1, 0], G3 = [y, -x, 0, 0, 0, 1];
+ *   the device reduces n, Sx, Sy, Sz, Sxx, Syy, Szz, Sxy, Sxz, Syz in fp64 in a fixed order (no atomics: two calls give the same bits)
+ *   and the host assembles rot-rot [[Syy+Szz, -Sxy, -Sxz], [., Sxx+Szz, -Syz], [., ., Sxx+Syy]], rot-trans [[0, -Sz, Sy], [Sz, 0, -Sx],
+ *   [-Sy, Sx, 0]], trans-trans n I.  It belongs to the LEFT perturbation T' = exp(xi^) T_global, xi = (omega, v).
+ *   about [HOST] 3 doubles or NULL = the origin (Open3D's convention); a scene far from the origin conditions better about its centroid.
+ *   nn_out [dev, 16-byte aligned] or NULL: 4 floats per (job, point), jobs back to back as d2_out of ibl_evaluate_batch: the matched
+ *   x, y, z and d2; (0, 0, 0, +inf) when none.  info_out [HOST] 36 per job, row-major, symmetric bit for bit; n_corr_out [HOST] per
+ *   job.  An empty job gives a zero matrix and 0.
+ *   IBL_ERR_ARG, decided before anything is launched and leaving the outputs untouched: null pointers (about and nn_out may be
+ *   null), threshold <= 0, n_jobs <= 0, a range that descends or begins below 0.  More than 65 535 jobs go in several launches.
+ *   Scratch from ctx's arena, released on return.  The call synchronises `stream` before it returns; the grid is only read. */
+int ibl_evaluate_information(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float* det_pts4, const int32_t* job_begin,
+                             const int32_t* job_end, const double* T_global, int n_jobs, double threshold,
+                             const double* about /* 3 doubles, host; NULL = origin */, float* nn_out /* [dev] or NULL */,
+                             double* info_out /* host, 36 per job */, int64_t* n_corr_out /* host, per job */, void* stream);
 
 /* Stage B of localise() for a batch of frames in ONE call (SURVEY 8b's fused driver; csrc/localise.hip): radius-outlier removal of
  * every detected cloud and ordered compaction (object_memory/object_memory.py:992-998), the detections' instance features, one

@@ -77,6 +77,7 @@ _SIGS = {
     "ibl_memgrid_export": (C.c_int, [vp, vp, vp, vp, vp]),
     "ibl_memgrid_overlap": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_double, C.c_int32, vp, vp, vp, vp]),
     "ibl_evaluate_batch": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp]),
+    "ibl_evaluate_information": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp, vp]),
     "ibl_register_evaluate_batch": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_double, C.c_int, C.c_double, C.c_int,
                                               vp, vp, vp, vp, vp, vp, vp, vp]),
     "ibl_dator_head_workspace_bytes": (C.c_int64, [C.c_int]),

@@ -947,3 +947,157 @@ extern "C" int ibl_memgrid_overlap(ibl_reg_ctx* ctx, const ibl_memgrid* grid, co
     ibl_stage_reset(ctx);                                    // the pinned staging of the offsets is recycled by the next call
     return st;
 }
+
+// ------------------------------------------------------------------------------------------------
+// information matrix of a pose from its whole-memory correspondences (ibl_evaluate_information)
+// ------------------------------------------------------------------------------------------------
+// Open3D's get_information_matrix_from_point_clouds: sum over the correspondences of G^T G, G = [-[m]x | I] of the matched MEMORY
+// point m (taken about `about`).  The 36 entries depend on ten sums only -- n, the first and the second moments of m -- which is what
+// the kernel reduces; the host assembles the matrix.
+#define INFO_SUMS 10       // n, Sx, Sy, Sz, Sxx, Syy, Szz, Sxy, Sxz, Syz
+
+// (x, y, z) of a before that of b, compared as floats
+__device__ __forceinline__ bool mg_lex_less(float ax, float ay, float az, float bx, float by, float bz) {
+    return ax < bx || (ax == bx && (ay < by || (ay == by && az < bz)));
+}
+
+// grid (ICP_BPJ, J).  The walk of ibl_evaluate_kernel -- the same transformed point, padded box, own cell first, face bounds -- that
+// keeps the matched point next to its distance.  Which of several memory points at the same minimal fp32 d2 is the match must not
+// depend on the order they are met in (cell order, live edits, pruning): it is the one with the lexicographically smallest
+// (x, y, z).  So a cell is skipped only when its bound lies strictly ABOVE the best distance (a cell that can only tie is read), and
+// the table probe is bounded (mg_find_cell).  The ten sums are reduced in the evaluation kernel's fixed order: no atomics.
+__global__ __launch_bounds__(256) void ibl_information_kernel(MemGridView g, const float4* __restrict__ det, const EvalJob* __restrict__ jobs,
+                                                              float thr, float thr2, double ox, double oy, double oz,
+                                                              double* __restrict__ partial /* [J][BPJ][INFO_SUMS] */,
+                                                              float4* __restrict__ nn_out /* per (job, point) or null */, int prune) {
+    const int j = blockIdx.y;
+    const EvalJob job = jobs[j];
+    double acc[INFO_SUMS];
+#pragma unroll
+    for (int t = 0; t < INFO_SUMS; ++t) acc[t] = 0.0;
+    for (int i = job.begin + blockIdx.x * 256 + threadIdx.x; i < job.end; i += ICP_BPJ * 256) {
+        const float4 s4 = det[i];
+        double p[3];
+        xform_d(job.T, s4.x, s4.y, s4.z, p);
+        const float qx = (float)p[0], qy = (float)p[1], qz = (float)p[2];
+        float best = thr2, bx = 0.0f, by = 0.0f, bz = 0.0f;
+        bool found = false;
+        // the padded box of ibl_evaluate_kernel (see there)
+        const float px = thr * 1.000001f + 2.4e-7f * fabsf(qx), py = thr * 1.000001f + 2.4e-7f * fabsf(qy), pz = thr * 1.000001f + 2.4e-7f * fabsf(qz);
+        const int x0 = (int)floorf((qx - px) * g.inv), x1 = (int)floorf((qx + px) * g.inv);
+        const int y0 = (int)floorf((qy - py) * g.inv), y1 = (int)floorf((qy + py) * g.inv);
+        const int z0 = (int)floorf((qz - pz) * g.inv), z1 = (int)floorf((qz + pz) * g.inv);
+        const int hx = (int)floorf(qx * g.inv), hy = (int)floorf(qy * g.inv), hz = (int)floorf(qz * g.inv);
+        auto scan_cell = [&](int ix, int iy, int iz) {
+            const int c = mg_find_cell(g, mg_key(ix, iy, iz));
+            if (c < 0) return;
+            const int b = g.ustart[c], e = g.ustart[c + 1];
+            for (int t = b; t < e; t += 4) {           // four points in flight (past the end: the last point again -- it neither beats nor precedes itself)
+                float4 m[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) m[u] = g.sorted[min(t + u, e - 1)];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float d2 = dist2f(qx, qy, qz, m[u].x, m[u].y, m[u].z);
+                    if (d2 < best || (found && d2 == best && mg_lex_less(m[u].x, m[u].y, m[u].z, bx, by, bz))) {
+                        best = d2; bx = m[u].x; by = m[u].y; bz = m[u].z; found = true;
+                    }
+                }
+            }
+        };
+        auto face_gap = [&](int i, int hcell, float q) {   // as in ibl_evaluate_kernel: a lower bound of the distance to cell i on this axis
+            if (i == hcell) return 0.0f;
+            const float face = (float)(i < hcell ? hcell : hcell + 1) * g.cell;
+            return fmaxf(fabsf(q - face) - (1e-3f * g.cell + 5e-7f * fabsf(face)), 0.0f);
+        };
+        scan_cell(hx, hy, hz);
+        for (int ix = x0; ix <= x1; ++ix) {
+            const float gx = face_gap(ix, hx, qx);
+            for (int iy = y0; iy <= y1; ++iy) {
+                const float gy = face_gap(iy, hy, qy);
+                for (int iz = z0; iz <= z1; ++iz) {
+                    if (ix == hx && iy == hy && iz == hz) continue;
+                    const float gz = face_gap(iz, hz, qz);
+                    if (prune && gx * gx + gy * gy + gz * gz > best) continue;      // strictly above: a cell that can tie is read
+                    scan_cell(ix, iy, iz);
+                }
+            }
+        }
+        if (found) {
+            const double x = (double)bx - ox, y = (double)by - oy, z = (double)bz - oz;
+            acc[0] += 1.0; acc[1] += x; acc[2] += y; acc[3] += z;
+            acc[4] += x * x; acc[5] += y * y; acc[6] += z * z;
+            acc[7] += x * y; acc[8] += x * z; acc[9] += y * z;
+        }
+        if (nn_out) nn_out[job.out + (i - job.begin)] = found ? make_float4(bx, by, bz, best) : make_float4(0.0f, 0.0f, 0.0f, INFINITY);
+    }
+    __shared__ double sh[INFO_SUMS][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int t = 0; t < INFO_SUMS; ++t) {
+        const double v = wave_sum_d(acc[t]);
+        if (lane == 0) sh[t][wave] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < INFO_SUMS)
+        partial[((int64_t)j * ICP_BPJ + blockIdx.x) * INFO_SUMS + threadIdx.x] =
+            ((sh[threadIdx.x][0] + sh[threadIdx.x][1]) + sh[threadIdx.x][2]) + sh[threadIdx.x][3];
+}
+
+extern "C" int ibl_evaluate_information(ibl_reg_ctx* ctx, const ibl_memgrid* grid, const float* det_pts4, const int32_t* job_begin,
+                                        const int32_t* job_end, const double* T_global, int n_jobs, double threshold, const double* about,
+                                        float* nn_out, double* info_out, int64_t* n_corr_out, void* stream) {
+    if (!ctx || !grid || !det_pts4 || !job_begin || !job_end || !T_global || !info_out || !n_corr_out || n_jobs <= 0 || !(threshold > 0))
+        return ibl_set_error(IBL_ERR_ARG, "ibl_evaluate_information: bad argument");
+    if (((uintptr_t)det_pts4 | (uintptr_t)nn_out) & 15) return ibl_set_error(IBL_ERR_ARG, "ibl_evaluate_information: det_pts4 / nn_out not 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    ArenaMark mark(ctx);
+    const int J = n_jobs;
+    std::vector<EvalJob> jobs(J);
+    for (int j = 0; j < J; ++j) {
+        for (int t = 0; t < 12; ++t) jobs[j].T[t] = T_global[16 * j + t];
+        jobs[j].begin = job_begin[j]; jobs[j].end = job_end[j];
+        if (job_begin[j] < 0 || job_end[j] < job_begin[j]) return ibl_set_error(IBL_ERR_ARG, "ibl_evaluate_information: bad point range");
+        jobs[j].out = j == 0 ? 0 : jobs[j - 1].out + (jobs[j - 1].end - jobs[j - 1].begin);
+    }
+    const double ox = about ? about[0] : 0.0, oy = about ? about[1] : 0.0, oz = about ? about[2] : 0.0;
+    EvalJob* d_jobs; double* partial;
+    IBL_ARENA(d_jobs, EvalJob, J);
+    IBL_ARENA(partial, double, (int64_t)J * ICP_BPJ * INFO_SUMS);
+    IBL_HIP_CHECK(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(EvalJob) * J, hipMemcpyHostToDevice, s));
+    const int prune = !ctx->diag.eval_fullscan;
+    std::vector<double> h((size_t)J * ICP_BPJ * INFO_SUMS);
+    auto run = [&]() -> int {
+        // at most 65 535 jobs per launch, as ibl_evaluate_batch: a launch gets its part of the jobs and of the partials
+        const int max_rows = 65535;
+        for (int j0 = 0; j0 < J; j0 += max_rows)
+            hipLaunchKernelGGL(ibl_information_kernel, dim3(ICP_BPJ, std::min(J - j0, max_rows)), dim3(256), 0, s, grid->v,
+                               reinterpret_cast<const float4*>(det_pts4), d_jobs + j0, (float)threshold, (float)(threshold * threshold), ox, oy, oz,
+                               partial + (int64_t)j0 * ICP_BPJ * INFO_SUMS, reinterpret_cast<float4*>(nn_out), prune);
+        IBL_LAUNCH_CHECK();
+        IBL_HIP_CHECK(hipMemcpyAsync(h.data(), partial, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
+        IBL_HIP_CHECK(hipStreamSynchronize(s));
+        return IBL_OK;
+    };
+    const int st = run();
+    if (st != IBL_OK) { (void)hipStreamSynchronize(s); return st; }      // (nothing queued may outlive the scratch or `jobs`)
+    for (int j = 0; j < J; ++j) {
+        double S[INFO_SUMS];
+        for (int t = 0; t < INFO_SUMS; ++t) {
+            S[t] = 0.0;
+            for (int b = 0; b < ICP_BPJ; ++b) S[t] += h[((size_t)j * ICP_BPJ + b) * INFO_SUMS + t];
+        }
+        const double n = S[0], sx = S[1], sy = S[2], sz = S[3], sxx = S[4], syy = S[5], szz = S[6], sxy = S[7], sxz = S[8], syz = S[9];
+        double* A = info_out + 36 * (size_t)j;
+        const double upper[6][6] = {{syy + szz, 0.0 - sxy, 0.0 - sxz, 0.0, 0.0 - sz, sy},
+                                    {0.0, sxx + szz, 0.0 - syz, sz, 0.0, 0.0 - sx},
+                                    {0.0, 0.0, sxx + syy, 0.0 - sy, sx, 0.0},
+                                    {0.0, 0.0, 0.0, n, 0.0, 0.0},
+                                    {0.0, 0.0, 0.0, 0.0, n, 0.0},
+                                    {0.0, 0.0, 0.0, 0.0, 0.0, n}};
+        for (int r = 0; r < 6; ++r)
+            for (int c = 0; c < 6; ++c) A[6 * r + c] = r <= c ? upper[r][c] : upper[c][r];
+        n_corr_out[j] = (int64_t)n;
+    }
+    return IBL_OK;
+}

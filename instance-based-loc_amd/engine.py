@@ -29,9 +29,9 @@ from scipy.spatial.transform import Rotation
 from . import match
 from .assign import K_HI, K_LO, assign_batch, assign_candidates
 from .parallel import ShardExchange, shard_range, sharded_candidates
-from .registration import (CloudBatch, InstanceFeatures, MemGrid, RegContext, compact_rows, compact_scratch, evaluate_batch, evaluate_points, grow_rows,
-                           instance_features_batch, kept_runs, merged_ranges, radius_outlier_batch, register_batch, register_evaluate_batch,
-                           replaced_ranges, splice_rows)
+from .registration import (CloudBatch, InstanceFeatures, MemGrid, RegContext, compact_rows, compact_scratch, evaluate_batch, evaluate_information,
+                           evaluate_points, grow_rows, instance_features_batch, kept_runs, merged_ranges, radius_outlier_batch, register_batch,
+                           register_evaluate_batch, replaced_ranges, splice_rows)
 
 IBL_ST_GRID_OVERFLOW = 1          # ibl_reg_ctx_status bits (include/ibloc.h)
 
@@ -311,6 +311,13 @@ class FrameResult:
     records: list = field(default_factory=list)
     best: int = -1
     n_clean: int = 0                      # detected points of the frame left after the radius-outlier removal (:992-998)
+    # localise_batch(information=True) only; None otherwise.  The 6 x 6 information matrix sum G^T G (Open3D's
+    # get_information_matrix_from_point_clouds: rotation first, then translation; about the world origin) of the best record's T_global
+    # over the frame's cleaned points against the whole memory.  It belongs to the LEFT perturbation T' = exp(xi^) T_global, and
+    # T_global = [R | t_fix]: it goes with pose_corrected, not with pose.
+    information: np.ndarray = None
+    n_correspondences: int = None         # its correspondences: round(full_fitness * n_clean) of the best record
+    inlier_centroid: np.ndarray = None    # mean of the matched memory points (None without correspondences): a better-conditioned `about`
 
 
 @dataclass
@@ -644,12 +651,16 @@ class LocaliseEngine:
     def localise_batch(self, det: CloudBatch, q_per_frame, crops=None, det_emb=None, fpfh_voxel_size=0.05,
                        fpfh_global_dist_factor=2, fpfh_local_dist_factor=0.4, outlier_radius=0.05, outlier_nb_points=8,
                        seed=0, job_id_base=0, ransac_max_iter=4000000, num_per_length=4, eval_threshold=None, timings=None,
-                       assns=None, _slot=None, register=True, ransac_fixed_budget=False):
+                       assns=None, _slot=None, register=True, ransac_fixed_budget=False, information=False):
         """det: detected clouds of all frames (segments in frame order, <= 7 per frame); crops: uint8 tensor
         (sum Q, H, W, 3) or list of arrays (DATOR: the (rgb, depth) pair), or det_emb: (sum Q, D) precomputed embeddings (or
         assns: the assignment lists stage A of `localise_stream` produced).  register=False stops after the assignment search
-        (embedding-only memories): the results carry the assignment lists, `best` = 0 and identity poses; `det` may be None."""
+        (embedding-only memories): the results carry the assignment lists, `best` = 0 and identity poses; `det` may be None.
+        information=True: every frame with best >= 0 also gets `information`, `n_correspondences` and `inlier_centroid` (FrameResult)
+        -- one more library call for all frames, after everything else; unsharded memories only."""
         mem = self.memory
+        if information and (self.route is not None or mem.shard_clouds):
+            raise ValueError("information: unsharded memories only")
         ctx, lane = (self.ctx, 0) if _slot is None else (_slot.ctx, _slot.lane)
         q_per_frame = np.asarray(q_per_frame, dtype=np.int32)
         F = len(q_per_frame)
@@ -697,6 +708,11 @@ class LocaliseEngine:
             tick("stage_b")              # (the split of stage B into its stages: the library's in-process stage timer, prof.stage_rooflines)
             self._assemble(results, assns, row0, r["clean_off"], r, r["T_global"], r["full_rmse"], r["full_fitness"])
             tick("select")
+            if information:
+                # the cleaned points stayed inside the library: recomputed as the staged path below forms them
+                keepb = radius_outlier_batch(ctx, det, outlier_radius, outlier_nb_points).bool()
+                self._information(ctx, results, det.pts4[keepb].contiguous(), r["clean_off"], row0, thr)
+                tick("information")
             close_timings()
             return results
         # ---- clean the detected clouds (:992-998) ---------------------------------------------------
@@ -757,8 +773,28 @@ class LocaliseEngine:
         tick("evaluate")
         self._assemble(results, assns, row0, new_off_h, reg, G, full_rmse, full_fit)
         tick("select")
+        if information:
+            self._information(ctx, results, clean.pts4, new_off_h, row0, thr)
+            tick("information")
         close_timings()
         return results
+
+    def _information(self, ctx, results, clean_pts4, new_off_h, row0, thr):
+        """information matrix, correspondence count and inlier centroid of every frame that has a best record: its T_global over the
+        frame's cleaned points, all frames in one call"""
+        frames = [f for f, r in enumerate(results) if r.best >= 0 and r.records]
+        if not frames:
+            return
+        jb = [int(new_off_h[row0[f]]) for f in frames]
+        je = [int(new_off_h[row0[f + 1]]) for f in frames]
+        G = np.stack([results[f].records[results[f].best]["T_global"] for f in frames])
+        info, n_corr = evaluate_information(ctx, self.memory.grid, clean_pts4, jb, je, G, thr)
+        for k, f in enumerate(frames):
+            n = int(n_corr[k])
+            results[f].information = info[k]
+            results[f].n_correspondences = n
+            # about the origin the rot-trans block is [[0, -Sz, Sy], [Sz, 0, -Sx], [-Sy, Sx, 0]]
+            results[f].inlier_centroid = np.array([info[k, 2, 4], info[k, 0, 5], info[k, 1, 3]]) / n if n else None
 
     @staticmethod
     def _assemble(results, assns, row0, new_off_h, reg, G, full_rmse, full_fit):

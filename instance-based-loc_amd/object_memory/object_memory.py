@@ -554,9 +554,10 @@ class ObjectMemory():
         return phrases, embs, clouds
 
     def localise_detections(self, detected_embs, detected_clouds, outlier_removal_config=None, fpfh_global_dist_factor=2,
-                            fpfh_local_dist_factor=0.4, fpfh_voxel_size=0.05, max_detected_object_num=7):
+                            fpfh_local_dist_factor=0.4, fpfh_voxel_size=0.05, max_detected_object_num=7, information=False):
         """The body of localise() after perception (object_memory.py:899-1131) for one frame: embeddings (Q, D) and
-        clouds [(points, colors), ...] -> FrameResult."""
+        clouds [(points, colors), ...] -> FrameResult.  information=True: with the pose's 6 x 6 information matrix, its
+        correspondence count and inlier centroid (FrameResult.information; LocaliseEngine.localise_batch)."""
         if outlier_removal_config is None:
             outlier_removal_config = {"radius_nb_points": 8, "radius": 0.05}
         if isinstance(detected_clouds, CloudBatch):
@@ -579,7 +580,7 @@ class ObjectMemory():
         return eng.localise_batch(det, [n_det], det_emb=embs, fpfh_voxel_size=fpfh_voxel_size,
                                   fpfh_global_dist_factor=fpfh_global_dist_factor, fpfh_local_dist_factor=fpfh_local_dist_factor,
                                   outlier_radius=outlier_removal_config["radius"], outlier_nb_points=outlier_removal_config["radius_nb_points"],
-                                  seed=self.ransac_seed, job_id_base=16 * self._n_queries)[0]
+                                  seed=self.ransac_seed, job_id_base=16 * self._n_queries, information=information)[0]
 
     def localise(self, image_path, depth_image_path, testname="", subtest_name="", save_point_clouds=False,
                  outlier_removal_config=None, fpfh_global_dist_factor=2, fpfh_local_dist_factor=0.4, fpfh_voxel_size=0.05,

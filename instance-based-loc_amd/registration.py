@@ -747,3 +747,32 @@ def evaluate_points(ctx: RegContext, grid: MemGrid, det_pts4: torch.Tensor, job_
                                      J, float(threshold), d2.data_ptr(), rmse.ctypes.data, fit.ctypes.data, _stream())
     _lib.check(st, "ibl_evaluate_batch")
     return d2[:int((je - jb).sum())], rmse, fit
+
+
+def evaluate_information(ctx: RegContext, grid: MemGrid, det_pts4: torch.Tensor, job_begin, job_end, T_global, threshold=0.02, about=None,
+                         points=False):
+    """Open3D's get_information_matrix_from_point_clouds for J poses against the whole memory (`ibl_evaluate_information`): the 6 x 6
+    matrix sum G^T G, G = [-[m]x | I], over the correspondences of `evaluate_batch` -- every detected point of the job whose nearest
+    memory point m lies within `threshold`; among memory points at the same fp32 distance the lexicographically smallest (x, y, z).
+    Rotation first, then translation; it belongs to the LEFT perturbation T' = exp(xi^) T_global, xi = (omega, v).  about: 3 doubles
+    subtracted from m (None: the origin, Open3D's convention).  Returns (info (J, 6, 6) float64, n_corr (J,) int64) and, with
+    points=True, the (N, 4) float32 device tensor of the matched x, y, z and d2 per point (jobs back to back; (0, 0, 0, +inf) when
+    none).  n_corr / (job_end - job_begin) is `evaluate_batch`'s fitness exactly."""
+    jb = np.ascontiguousarray(job_begin, dtype=np.int32)
+    je = np.ascontiguousarray(job_end, dtype=np.int32)
+    T = np.ascontiguousarray(T_global, dtype=np.float64).reshape(-1, 16)
+    J = len(jb)
+    assert len(je) == J and len(T) == J
+    assert det_pts4.is_cuda and det_pts4.dtype == torch.float32 and det_pts4.dim() == 2 and det_pts4.shape[1] == 4 and det_pts4.is_contiguous()
+    if J and int(je.max()) > det_pts4.shape[0]:
+        raise ValueError("evaluate_information: a job ends behind the rows of det_pts4")
+    ab = None if about is None else np.ascontiguousarray(about, dtype=np.float64).reshape(3)
+    total = int((je.astype(np.int64) - jb).sum()) if J else 0
+    nn = torch.empty((max(total, 1), 4), dtype=torch.float32, device=det_pts4.device) if points else None
+    info = np.zeros((J, 6, 6), dtype=np.float64)
+    n_corr = np.zeros(J, dtype=np.int64)
+    st = _lib.lib.ibl_evaluate_information(ctx.handle, grid.handle, det_pts4.data_ptr(), jb.ctypes.data, je.ctypes.data, T.ctypes.data, J,
+                                           float(threshold), None if ab is None else ab.ctypes.data, None if nn is None else nn.data_ptr(),
+                                           info.ctypes.data, n_corr.ctypes.data, _stream())
+    _lib.check(st, "ibl_evaluate_information")
+    return (info, n_corr, nn[:max(total, 0)]) if points else (info, n_corr)

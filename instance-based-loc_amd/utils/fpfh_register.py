@@ -4,6 +4,7 @@ Same function names, argument meaning and return shapes as /root/reference/utils
   downsample_and_compute_fpfh(pcd, voxel_size)                     :86-98
   register_point_clouds(source, target, voxel_size, gdf, ldf)      :100-143
   evaluate_transform(source, target, trans_init, threshold)        :145-150
+  get_information_matrix(source, target, max_dist, transformation) Open3D's get_information_matrix_from_point_clouds (not in the reference)
   get_transformation / get_SVD_transform (numpy Kabsch helpers)    :24-82
 The arithmetic the reference delegates to Open3D runs in libibloc_hip.so (csrc/reg_*.hip).  Clouds may be
 Open3D point clouds (anything exposing `.points` / `.colors`) or plain (N, 3) arrays / (points, colors) tuples;
@@ -13,7 +14,7 @@ import numpy as np
 import torch
 
 from ibloc_amd.engine import intensity_from_colors
-from ibloc_amd.registration import CloudBatch, MemGrid, RegContext, evaluate_batch, normals_fpfh_batch, register_batch
+from ibloc_amd.registration import CloudBatch, MemGrid, RegContext, evaluate_batch, evaluate_information, normals_fpfh_batch, register_batch
 
 _CTX = {"reg": None, "calls": 0}
 RANSAC_SEED = 0          # Open3D draws from an unseeded global RNG; here the draw sequence is a function of (seed, call #)
@@ -122,3 +123,18 @@ def evaluate_transform(source, target, trans_init, threshold=0.02):
     rmse, fit = evaluate_batch(ctx, grid, sb.pts4, [0], [sb.n], np.asarray(trans_init, dtype=np.float64).reshape(1, 16), threshold)
     grid.close()
     return float(rmse[0]), float(fit[0])
+
+
+def get_information_matrix(source, target, max_correspondence_distance, transformation):
+    """open3d.pipelines.registration.get_information_matrix_from_point_clouds: the 6 x 6 matrix sum G^T G, G = [-[m]x | I], over the
+    target points m matched by the transformed source points within max_correspondence_distance (rotation first, then translation,
+    about the origin; the left perturbation exp(xi^) `transformation`).  Its [3, 3] entry is the number of correspondences."""
+    s, t = _as_cloud(source), _as_cloud(target)
+    ctx = _ctx()
+    tb = _batch(t)
+    grid = MemGrid(ctx, tb.pts4, cell=2 * max_correspondence_distance)
+    sb = _batch(s)
+    info, _ = evaluate_information(ctx, grid, sb.pts4, [0], [sb.n], np.asarray(transformation, dtype=np.float64).reshape(1, 16),
+                                   max_correspondence_distance)
+    grid.close()
+    return info[0]
