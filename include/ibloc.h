@@ -171,6 +171,23 @@ int ibl_preprocess_crops(const uint8_t* src, const ibl_crop_desc* descs, int n_c
  *   out     [dev] fp32 [batch][out_dim]  (CLS embedding; un-normalised, like the reference), or
  *           fp32 [batch][n_tokens][dim] with IBL_VIT_OUT_ALL_TOKENS */
 int64_t ibl_vit_workspace_bytes(const ibl_vit_desc* desc, int batch);
+/* Where ibl_vit_forward keeps its intermediates in the caller's workspace (no device call): offsets [host] [n], n <= IBL_VIT_WS_COUNT,
+ * byte offsets of the first n buffers below relative to the workspace pointer rounded up to 256 bytes; each on a 256-byte boundary, none
+ * overlapping, the last one ending inside ibl_vit_workspace_bytes.  Refused (IBL_ERR_ARG): batch <= 0, a null pointer, n outside
+ * 0..IBL_VIT_WS_COUNT.  With Rn = batch * n_tokens rows, D = dim, and k = n_blocks_run - 1 the last block run, a forward leaves:
+ *   X    fp32 [Rn][D]           the residual stream after block k (after the patch embedding / ln_pre with n_blocks_run = 0)
+ *   XN   fp16 [Rn][ft * D]      block k's second LayerNorm output in ft = fc1_terms column blocks [a | a / S] or [a | a_lo * S | a / S]
+ *   QKV  fp16 [Rn][3 * D]       block k's [q | k | v]
+ *   ATT  fp16 [Rn][ot * D]      block k's attention output in ot = o_terms column blocks
+ *   HID  fp16 [Rn][f2t * mlp]   block k's hidden layer after the activation in f2t = fc2_terms column blocks
+ *   FIN  fp16 [batch][D]        not written by an all-token run
+ * Where block k runs on the class rows alone (no IBL_VIT_OUT_ALL_TOKENS; one term everywhere, whatever the layer's *_terms say): XN
+ * is the block's FIRST LayerNorm output [Rn][D]; QKV holds k and v of every row but q of the class rows (row b * n_tokens) only; ATT
+ * [Rn][D] is written in the class rows only, in place; FIN is the second LayerNorm of the class rows, the MLP input; HID is
+ * [batch][mlp], its first `batch` rows.  The projection then overwrites the head of a buffer: with w_proj_x XN becomes [batch][3 * D],
+ * the final LayerNorm of the class rows in three terms; without it FIN becomes that LayerNorm in one term. */
+enum { IBL_VIT_WS_X = 0, IBL_VIT_WS_XN, IBL_VIT_WS_QKV, IBL_VIT_WS_ATT, IBL_VIT_WS_HID, IBL_VIT_WS_FIN, IBL_VIT_WS_COUNT };
+int ibl_vit_workspace_layout(const ibl_vit_desc* desc, int batch, int64_t* offsets, int n);
 int ibl_vit_forward(const ibl_vit_desc* desc, const ibl_vit_weights* weights, const void* patches, int batch,
                     float* out, void* workspace, int64_t workspace_bytes, void* stream);
 

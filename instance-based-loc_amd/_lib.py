@@ -45,6 +45,7 @@ _SIGS = {
     "ibl_preprocess_crops": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        vp, vp, vp, vp, vp]),
     "ibl_vit_workspace_bytes": (C.c_int64, [vp, C.c_int]),
+    "ibl_vit_workspace_layout": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "ibl_linear_f16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp]),
     "ibl_linear_f16_ex": (C.c_int, [vp, vp]),
     "ibl_linear_f16_act": (C.c_int, [vp, C.c_int, vp]),

@@ -1399,18 +1399,45 @@ extern "C" int ibl_linear_f16(const void* x, int64_t ldx, const void* W, int64_t
     return ibl_linear_f16_ex(&d, stream);
 }
 
+// The workspace layout, in one place: byte offsets of the IBL_VIT_WS_* buffers from the 256-byte-aligned workspace base, each buffer on a
+// 256-byte boundary.  ibl_vit_workspace_bytes, ibl_vit_workspace_layout and the forward pass all read this table.  Returns the end.
+static int64_t vit_layout(const ibl_vit_desc* d, int batch, int64_t offs[IBL_VIT_WS_COUNT], int64_t* payload = nullptr) {
+    const int64_t R = rows_pad((int64_t)batch * d->n_tokens);
+    const int at = (d->flags & IBL_VIT_ACT_TERMS3) ? 3 : ((d->flags & IBL_VIT_ACT_TERMS2) ? 2 : 1);   // widest K-extended input of a residual GEMM
+    int64_t bytes[IBL_VIT_WS_COUNT];
+    bytes[IBL_VIT_WS_X] = R * d->dim * 4;              // residual stream, fp32
+    bytes[IBL_VIT_WS_XN] = R * d->dim * 2 * 3;         // LayerNorm output (up to three terms per row, two-term operands of the early blocks)
+    bytes[IBL_VIT_WS_QKV] = R * 3 * d->dim * 2;
+    bytes[IBL_VIT_WS_ATT] = R * d->dim * 2 * at;       // attention output
+    bytes[IBL_VIT_WS_HID] = R * d->mlp_dim * 2 * at;   // MLP hidden layer
+    bytes[IBL_VIT_WS_FIN] = rows_pad(batch) * d->dim * 2;      // CLS rows after a LayerNorm (fp16)
+    int64_t p = 0, sum = 0;
+    for (int i = 0; i < IBL_VIT_WS_COUNT; ++i) {
+        p = (p + 255) & ~(int64_t)255;
+        offs[i] = p;
+        p += bytes[i];
+        sum += bytes[i];
+    }
+    if (payload) *payload = sum;      // the buffers without their alignment gaps
+    return p;
+}
+
 extern "C" int64_t ibl_vit_workspace_bytes(const ibl_vit_desc* d, int batch) {
     if (!d || batch <= 0) return -1;
-    const int64_t R = rows_pad((int64_t)batch * d->n_tokens);
-    int64_t bytes = 0;
-    bytes += R * d->dim * 4;          // x
-    bytes += R * d->dim * 2 * 3;      // xn (up to three terms per row, two-term operands of the early blocks)
-    bytes += R * 3 * d->dim * 2;      // qkv
-    const int at = (d->flags & IBL_VIT_ACT_TERMS3) ? 3 : ((d->flags & IBL_VIT_ACT_TERMS2) ? 2 : 1);   // widest K-extended input of a residual GEMM
-    bytes += R * d->dim * 2 * at;     // attn out
-    bytes += R * d->mlp_dim * 2 * at; // mlp hidden
-    bytes += rows_pad(batch) * d->dim * 2 + rows_pad(batch) * d->dim * 4;  // final rows (fp16 + f32)
-    return bytes + 9 * 256;
+    int64_t offs[IBL_VIT_WS_COUNT], sum = 0;
+    vit_layout(d, batch, offs, &sum);
+    // the size callers have always been asked for: the buffers, fp32 final rows (reserved; nothing is carved for them) and nine alignment
+    // gaps -- the base's and the five between the buffers fit in those
+    return sum + rows_pad(batch) * d->dim * 4 + 9 * 256;
+}
+
+extern "C" int ibl_vit_workspace_layout(const ibl_vit_desc* d, int batch, int64_t* offsets, int n) {
+    if (!d || batch <= 0 || !offsets || n < 0 || n > IBL_VIT_WS_COUNT)
+        return ibl_set_error(IBL_ERR_ARG, "ibl_vit_workspace_layout: bad argument");
+    int64_t offs[IBL_VIT_WS_COUNT];
+    vit_layout(d, batch, offs);
+    for (int i = 0; i < n; ++i) offsets[i] = offs[i];
+    return IBL_OK;
 }
 
 // any 1 <= T <= IBL_ATT_STREAM_MAX_TOKENS; the caller has checked that the grid fits
@@ -1539,20 +1566,18 @@ extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, 
     hipStream_t s = (hipStream_t)stream;
     const int64_t Rn = (int64_t)batch * T, R = rows_pad(Rn);
 
-    auto carve = [](unsigned char*& p, int64_t bytes) {
-        p = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(p) + 255) & ~(uintptr_t)255);
-        unsigned char* r = p;
-        p += bytes;
-        return r;
-    };
-    unsigned char* p = reinterpret_cast<unsigned char*>(workspace);
-    float* x = reinterpret_cast<float*>(carve(p, R * D * 4));
-    u16* xn = reinterpret_cast<u16*>(carve(p, R * D * 2 * 3));
-    u16* qkv = reinterpret_cast<u16*>(carve(p, R * 3 * D * 2));
+    int64_t offs[IBL_VIT_WS_COUNT];
+    const int64_t end = vit_layout(d, batch, offs);
+    unsigned char* base = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    if ((base - reinterpret_cast<unsigned char*>(workspace)) + end > workspace_bytes)
+        return ibl_set_error(IBL_ERR_ARG, "ibl_vit_forward: workspace too small");
+    float* x = reinterpret_cast<float*>(base + offs[IBL_VIT_WS_X]);
+    u16* xn = reinterpret_cast<u16*>(base + offs[IBL_VIT_WS_XN]);
+    u16* qkv = reinterpret_cast<u16*>(base + offs[IBL_VIT_WS_QKV]);
     const int at = (d->flags & IBL_VIT_ACT_TERMS3) ? 3 : ((d->flags & IBL_VIT_ACT_TERMS2) ? 2 : 1);
-    u16* att = reinterpret_cast<u16*>(carve(p, R * D * 2 * at));
-    u16* hid = reinterpret_cast<u16*>(carve(p, R * d->mlp_dim * 2 * at));
-    u16* fin_bf = reinterpret_cast<u16*>(carve(p, rows_pad(batch) * D * 2));
+    u16* att = reinterpret_cast<u16*>(base + offs[IBL_VIT_WS_ATT]);
+    u16* hid = reinterpret_cast<u16*>(base + offs[IBL_VIT_WS_HID]);
+    u16* fin_bf = reinterpret_cast<u16*>(base + offs[IBL_VIT_WS_FIN]);
 
     int st;
     // patch embedding (conv as GEMM over im2col'ed patches) + position embedding, scattered into x

@@ -24,6 +24,8 @@ FLAG_ACT_TERMS3 = 128
 FLAG_NO_CLS = 256            # IBL_VIT_NO_CLS: the sequence is the patch tokens alone (SigLIP)
 FLAG_TANH_GELU = 512         # IBL_VIT_TANH_GELU: fc1 activation gelu_pytorch_tanh (SigLIP)
 MAX_LAYERS = 32
+# workspace buffers of ibl_vit_forward in the order of include/ibloc.h's IBL_VIT_WS_* enum
+WS_TAPS = ("x", "xn", "qkv", "att", "hid", "fin")
 
 
 class VitDesc(C.Structure):
@@ -472,8 +474,9 @@ class VitEncoder:
         return (patches, out_u8) if want_u8 else patches
 
     # ---- forward -------------------------------------------------------------------------------
-    def forward_patches(self, patches: torch.Tensor, lane: int = 0) -> torch.Tensor:
-        """lane: which of the encoder's workspaces to use (concurrent forwards on different streams need their own)."""
+    def forward_patches(self, patches: torch.Tensor, lane: int = 0, taps: bool = False):
+        """lane: which of the encoder's workspaces to use (concurrent forwards on different streams need their own).
+        taps=True: -> (out, dict) with a view of every workspace buffer of this forward under its WS_TAPS name (`workspace_taps`)."""
         P = self.cfg.n_patches
         assert patches.dtype == torch.float16 and patches.is_cuda and patches.shape[1] == self.cfg.patch_k_pad
         batch = patches.shape[0] // P
@@ -490,6 +493,30 @@ class VitEncoder:
         st = _lib.lib.ibl_vit_forward(C.byref(self.desc), C.byref(self.W), patches.data_ptr(), batch, out.data_ptr(),
                                       ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
         _lib.check(st, "ibl_vit_forward")
+        return (out, self.workspace_taps(batch, lane)) if taps else out
+
+    def workspace_taps(self, batch: int, lane: int = 0) -> dict:
+        """Views of what the last forward of `batch` crops on `lane` left in its workspace (include/ibloc.h, IBL_VIT_WS_*), each at the
+        widest shape the descriptor allows; what a run fills of it is in the header: x fp32 (B, T, dim); xn fp16 (B * T, 3 * dim) -- a row
+        of `terms` column blocks is at [i * terms * dim, (i + 1) * terms * dim) of the flattened view; qkv fp16 (B, T, 3 * dim); att fp16
+        (B * T, at * dim) and hid fp16 (B * T, at * mlp_dim), flat in the same way, at = the workspace's term flag; fin fp16 (B, dim).
+        The next forward on the lane overwrites them."""
+        ws = self._ws_lanes[lane]
+        c = self.cfg
+        offs = (C.c_int64 * len(WS_TAPS))()
+        _lib.check(_lib.lib.ibl_vit_workspace_layout(C.byref(self.desc), batch, offs, len(WS_TAPS)), "ibl_vit_workspace_layout")
+        at = getattr(self, "_act_terms", 1)
+        R = batch * c.n_tokens
+        shapes = {"x": (torch.float32, (batch, c.n_tokens, c.dim)), "xn": (torch.float16, (R, 3 * c.dim)),
+                  "qkv": (torch.float16, (batch, c.n_tokens, 3 * c.dim)), "att": (torch.float16, (R, at * c.dim)),
+                  "hid": (torch.float16, (R, at * c.mlp_dim)), "fin": (torch.float16, (batch, c.dim))}
+        base = (-ws.data_ptr()) % 256
+        out = {}
+        for name, off in zip(WS_TAPS, offs):
+            dtype, shape = shapes[name]
+            n = int(np.prod(shape)) * (4 if dtype == torch.float32 else 2)
+            assert base + off + n <= ws.numel()
+            out[name] = ws[base + off:base + off + n].view(dtype).view(shape)
         return out
 
     def patches_from_pixels(self, x: torch.Tensor) -> torch.Tensor:
