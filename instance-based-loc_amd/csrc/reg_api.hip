@@ -1,7 +1,7 @@
 // reg_api.hip -- C-ABI entry points of the registration path: context (device arena, diagnostic switches), batched radius-outlier
 // removal, normals + FPFH, the instance-feature driver (ibl_instance_features_batch and what the registration shares with it) and the
 // whole unproject path (depth + masks -> coloured clouds).  The register driver lives in reg_register.hip (its stages in
-// reg_match.hip, reg_ransac.hip, reg_icp.hip), the evaluation against the whole memory in reg_eval.hip.
+// reg_match.hip, reg_ransac.hip, reg_icp.hip), the evaluation against the whole memory in reg_eval.hip, its grid in reg_memgrid.hip.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // reg_stages.h -- internals of the registration driver: the call as the C-ABI passes it in, the tables the stages share, and the stage
 // functions of one pass (reg_register.hip: job assembly, grid C, read-back; reg_match.hip: features + matching; reg_ransac.hip;
-// reg_icp.hip).  reg_eval.hip (whole-memory evaluation) shares only ICP_BPJ.
+// reg_icp.hip).  reg_eval.hip (whole-memory evaluation, information matrix; the grid itself is reg_memgrid.h / .hip) shares only ICP_BPJ.
 #pragma once
 #include <algorithm>
 #include <array>

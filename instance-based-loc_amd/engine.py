@@ -29,9 +29,9 @@ from scipy.spatial.transform import Rotation
 from . import match
 from .assign import K_HI, K_LO, assign_batch, assign_candidates
 from .parallel import ShardExchange, shard_range, sharded_candidates
-from .registration import (CloudBatch, InstanceFeatures, MemGrid, RegContext, compact_rows, compact_scratch, evaluate_batch, evaluate_information,
-                           evaluate_points, grow_rows, instance_features_batch, kept_runs, merged_ranges, radius_outlier_batch, register_batch,
-                           register_evaluate_batch, replaced_ranges, splice_rows)
+from .registration import (CloudBatch, InstanceFeatures, MemGrid, RegContext, _spliced_rows, appended, compact_scratch, evaluate_batch,
+                           evaluate_information, evaluate_points, instance_features_batch, offsets_of, radius_outlier_batch, register_batch,
+                           register_evaluate_batch, removed, replaced, row_edits, spliced_host)
 
 IBL_ST_GRID_OVERFLOW = 1          # ibl_reg_ctx_status bits (include/ibloc.h)
 
@@ -115,6 +115,80 @@ class MemoryShard:
                                                           compact=self.compact_features, reserve_points=room)
         return self._features[key]
 
+    def _check_live(self, verb, change):
+        if self.shard is not None:
+            raise ValueError(f"MemoryShard.{verb}: sharded memories cannot {change} while resident")
+        if not self.live:
+            raise ValueError(f"MemoryShard.{verb}: construct the shard with live=True")
+
+    def _check_instances(self, verb, instances):
+        """the distinct, valid instance indices `instances` as a list"""
+        given = [int(i) for i in instances]
+        if len(set(given)) != len(given):
+            raise ValueError(f"MemoryShard.{verb}: an instance is named twice")
+        if given and (min(given) < 0 or max(given) >= self.M):
+            raise ValueError(f"MemoryShard.{verb}: instance index out of range (the memory holds {self.M})")
+        return given
+
+    def _check_new(self, verb, n, embeddings, clouds, colors, intensities, points_leaving=0):
+        """the embeddings of n new instances as float32 arrays, their clouds checked"""
+        if (clouds is None) != (self.clouds is None):
+            raise ValueError(f"MemoryShard.{verb}: an embedding-only memory takes no clouds, a memory with clouds needs them")
+        embs = [np.asarray(e, dtype=np.float32) for e in embeddings]
+        dim = self.mem_emb.shape[1]
+        if n is not None and len(embs) != n:
+            raise ValueError(f"MemoryShard.{verb}: as many embedding arrays as instances")
+        if any(e.ndim != 2 or e.shape[1] != dim or len(e) == 0 for e in embs):
+            raise ValueError(f"MemoryShard.{verb}: every instance needs an (E, {dim}) array of embeddings")
+        if clouds is not None:
+            if len(clouds) != len(embs) or any(x is not None and len(x) != len(embs) for x in (colors, intensities)):
+                raise ValueError(f"MemoryShard.{verb}: as many clouds (colours, intensities) as instances")
+            if any(np.asarray(c).ndim != 2 or np.asarray(c).shape[1] != 3 or len(c) == 0 for c in clouds):
+                raise ValueError(f"MemoryShard.{verb}: every cloud is a non-empty (n, 3) array")
+            if self.clouds.n - points_leaving + sum(len(c) for c in clouds) > 0x7FFFFFF0:
+                raise ValueError(f"MemoryShard.{verb}: more than 0x7FFFFFF0 memory points")
+        return embs
+
+    def _splice(self, verb, seg_edits, embs=(), clouds=None, colors=None, intensities=None):
+        """The one edit behind `append`, `remove` and `replace`, its arguments checked: the instance edits `seg_edits`
+        (registration.row_edits) with the new instances `embs` / `clouds` / ..., in the order of their places.  The new instances'
+        features first, then the grid, then the buffers; the offsets follow from the sizes."""
+        torch.cuda.synchronize(self.device)
+        # one scratch chunk for every row splice below, allocated before anything is changed (132 B: the widest row, fpfh); an edit
+        # that only adds behind the last row moves nothing
+        scratch = None
+        if any(se > sb for sb, se, _, _ in seg_edits):
+            scratch = compact_scratch(self.device, max(self.mem_emb.numel() * 4, 0 if self.clouds is None else self.clouds.n * 132))
+        if self.clouds is not None:
+            new, new_feat = None, {key: None for key in self._features}
+            if clouds is not None:
+                if intensities is None:
+                    intensities = [intensity_from_colors(c) for c in colors] if colors is not None else None
+                new = CloudBatch.from_numpy(clouds, intensities, device=self.device)
+                # the new instances' features first, from their own batch: nothing resident has changed if this raises
+                new_feat = {key: instance_features_batch(self.ctx, new, key[0], 2.0 * (key[0] * key[1]), compact=self.compact_features)
+                            for key in self._features}
+            # then the grid: the only step that can fail in the library, and it leaves the grid as it was when it does.  Points behind
+            # all resident ones are an append: the grid merges them without reading the resident points' indices.
+            edits = row_edits(self.clouds.seg_off_host, seg_edits, (0,) if new is None else new.seg_off_host)
+            if new is None:
+                self.grid.remove([(b, e) for b, e, _, _ in edits])
+            elif len(edits) == 1 and edits[0][0] == self.clouds.n:
+                self.grid.append(new.pts4)
+            else:
+                self.grid.replace([(b, e) for b, e, _, _ in edits], [ne - nb for _, _, nb, ne in edits], new.pts4)
+            self.clouds._splice(seg_edits, new, scratch=scratch)
+            for key, feat in self._features.items():
+                feat._splice(verb, seg_edits, edits, new_feat[key], scratch=scratch)
+        rows = match.normalize_rows(torch.from_numpy(np.ascontiguousarray(np.concatenate(embs))).to(self.device)) if len(embs) else None
+        new_off = offsets_of([len(e) for e in embs])
+        self._emb_buf, self.mem_emb = _spliced_rows(self._emb_buf, self.mem_emb.shape[0], row_edits(self.emb_offsets_host, seg_edits, new_off),
+                                                    rows, scratch)
+        self.emb_offsets_host = offsets_of(spliced_host(np.diff(self.emb_offsets_host), seg_edits, np.diff(new_off)))
+        self.emb_offsets = torch.from_numpy(self.emb_offsets_host).to(self.device)
+        self.M = self.hi = len(self.emb_offsets_host) - 1
+        torch.cuda.synchronize(self.device)
+
     def append(self, embeddings, clouds=None, colors=None, intensities=None):
         """Adds the instances M .. M + k - 1 to a live memory: `embeddings` a list of k (E_i, D) arrays, `clouds` / `colors` /
         `intensities` lists of k arrays as the constructor takes them.  Their embeddings are normalised and attached, their clouds are
@@ -124,87 +198,27 @@ class MemoryShard:
         copied unless a buffer has run out of headroom (it then grows by 1.5).  Synchronises the device first: no localisation may
         be in flight.  Raises ValueError, before anything is touched, for a sharded or non-live memory, clouds given to an embedding-only
         memory (or withheld from one with clouds), a count mismatch or another embedding dimension."""
-        if self.shard is not None:
-            raise ValueError("MemoryShard.append: sharded memories cannot grow while resident")
-        if not self.live:
-            raise ValueError("MemoryShard.append: construct the shard with live=True")
-        if (clouds is None) != (self.clouds is None):
-            raise ValueError("MemoryShard.append: an embedding-only memory takes no clouds, a memory with clouds needs them")
-        embs = [np.asarray(e, dtype=np.float32) for e in embeddings]
-        dim = self.mem_emb.shape[1]
-        if any(e.ndim != 2 or e.shape[1] != dim or len(e) == 0 for e in embs):
-            raise ValueError(f"MemoryShard.append: every instance needs an (E, {dim}) array of embeddings")
-        if clouds is not None:
-            if len(clouds) != len(embs) or any(x is not None and len(x) != len(embs) for x in (colors, intensities)):
-                raise ValueError("MemoryShard.append: as many clouds (colours, intensities) as instances")
-            if any(np.asarray(c).ndim != 2 or np.asarray(c).shape[1] != 3 or len(c) == 0 for c in clouds):
-                raise ValueError("MemoryShard.append: every cloud is a non-empty (n, 3) array")
-            if self.clouds.n + sum(len(c) for c in clouds) > 0x7FFFFFF0:
-                raise ValueError("MemoryShard.append: more than 0x7FFFFFF0 memory points")
-        if not embs:
-            return
-        torch.cuda.synchronize(self.device)
-        if clouds is not None:
-            if intensities is None:
-                intensities = [intensity_from_colors(c) for c in colors] if colors is not None else None
-            new = CloudBatch.from_numpy(clouds, intensities, device=self.device)
-            # the new instances' features first, from their own batch: nothing resident has changed if this raises
-            new_feat = {key: instance_features_batch(self.ctx, new, key[0], 2.0 * (key[0] * key[1]), compact=self.compact_features)
-                        for key in self._features}
-            self.grid.append(new.pts4)
-            self.clouds.append(new)
-            for key, feat in self._features.items():
-                feat.append(new_feat[key])
-        rows = match.normalize_rows(torch.from_numpy(np.ascontiguousarray(np.concatenate(embs))).to(self.device))
-        self._emb_buf, self.mem_emb = grow_rows(self._emb_buf, self.mem_emb.shape[0], rows)
-        counts = np.cumsum([len(e) for e in embs]).astype(np.int32)
-        self.emb_offsets_host = np.concatenate([self.emb_offsets_host, self.emb_offsets_host[-1] + counts]).astype(np.int32)
-        self.emb_offsets = torch.from_numpy(self.emb_offsets_host).to(self.device)
-        self.M += len(embs)
-        self.hi = self.M
-        torch.cuda.synchronize(self.device)
+        self._check_live("append", "grow")
+        embs = self._check_new("append", None, embeddings, clouds, colors, intensities)
+        if embs:
+            self._splice("append", appended(self.M, len(embs)), embs, clouds, colors, intensities)
 
     def remove(self, instances):
         """Takes the instances `instances` (any iterable of distinct indices, not all of them) out of a live memory; the later
         instances move down and take the lower indices, as `del memory[i]` moves them.  The spatial hash drops their points by one
         compaction (ibl_memgrid_remove: no sort), the clouds, every resident feature set and the embedding rows are compacted in
-        place in their buffers (registration.compact_rows) -- nothing is uploaded, normalised, sorted or recomputed, and the
+        place in their buffers (registration.splice_rows) -- nothing is uploaded, normalised, sorted or recomputed, and the
         InstanceFeatures objects stay the same objects.  The state afterwards is, array for array, that of a MemoryShard constructed
         from the kept instances; the buffers keep their sizes, the freed room is headroom.  Synchronises the device first: no
         localisation may be in flight (LocaliseEngine keeps nothing sized by M for an unsharded memory; it reads M on every call).
         Raises ValueError, before anything is touched, for a sharded or non-live memory, an index out of range, a duplicate index or
         a request to remove every instance.  An empty list is a no-op."""
-        if self.shard is not None:
-            raise ValueError("MemoryShard.remove: sharded memories cannot shrink while resident")
-        if not self.live:
-            raise ValueError("MemoryShard.remove: construct the shard with live=True")
-        given = [int(i) for i in instances]
-        idx = sorted(set(given))
-        if len(idx) != len(given):
-            raise ValueError("MemoryShard.remove: an instance is named twice")
-        if idx and (idx[0] < 0 or idx[-1] >= self.M):
-            raise ValueError(f"MemoryShard.remove: instance index out of range (the memory holds {self.M})")
+        self._check_live("remove", "shrink")
+        idx = sorted(self._check_instances("remove", instances))
         if len(idx) == self.M and idx:
             raise ValueError("MemoryShard.remove: a resident memory is never empty (drop the shard instead)")
-        if not idx:
-            return
-        torch.cuda.synchronize(self.device)
-        # one scratch chunk for every row compaction below, allocated before anything is changed (132 B: the widest row, fpfh)
-        scratch = compact_scratch(self.device, max(self.mem_emb.numel() * 4, 0 if self.clouds is None else self.clouds.n * 132))
-        if self.clouds is not None:
-            # the grid first: the only step that can fail in the library, and it leaves the grid as it was when it does
-            self.grid.remove(merged_ranges(self.clouds.seg_off_host, idx))
-            ranges = self.clouds.remove(idx, scratch=scratch)
-            for feat in self._features.values():
-                feat.remove(idx, ranges, scratch=scratch)
-        rows = self.mem_emb.shape[0]
-        self.mem_emb = compact_rows(self._emb_buf, rows, kept_runs(rows, merged_ranges(self.emb_offsets_host, idx)), scratch=scratch)
-        counts = np.delete(np.diff(self.emb_offsets_host), idx)
-        self.emb_offsets_host = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
-        self.emb_offsets = torch.from_numpy(self.emb_offsets_host).to(self.device)
-        self.M -= len(idx)
-        self.hi = self.M
-        torch.cuda.synchronize(self.device)
+        if idx:
+            self._splice("remove", removed(idx))
 
     def replace(self, instances, embeddings, clouds=None, colors=None, intensities=None):
         """Gives the instances `instances` (distinct indices, any subset, in any order) of a live memory new embeddings
@@ -219,63 +233,15 @@ class MemoryShard:
         be in flight.  Raises ValueError, before anything is touched, for a sharded or non-live memory, an index out of range, a
         duplicate index, a count or dimension mismatch, clouds given to an embedding-only memory (or withheld from one with clouds)
         or more than 0x7FFFFFF0 points.  An empty list is a no-op."""
-        if self.shard is not None:
-            raise ValueError("MemoryShard.replace: sharded memories cannot change while resident")
-        if not self.live:
-            raise ValueError("MemoryShard.replace: construct the shard with live=True")
-        if (clouds is None) != (self.clouds is None):
-            raise ValueError("MemoryShard.replace: an embedding-only memory takes no clouds, a memory with clouds needs them")
-        given = [int(i) for i in instances]
-        if len(set(given)) != len(given):
-            raise ValueError("MemoryShard.replace: an instance is named twice")
-        if given and (min(given) < 0 or max(given) >= self.M):
-            raise ValueError(f"MemoryShard.replace: instance index out of range (the memory holds {self.M})")
-        embs = [np.asarray(e, dtype=np.float32) for e in embeddings]
-        dim = self.mem_emb.shape[1]
-        if len(embs) != len(given):
-            raise ValueError("MemoryShard.replace: as many embedding arrays as instances")
-        if any(e.ndim != 2 or e.shape[1] != dim or len(e) == 0 for e in embs):
-            raise ValueError(f"MemoryShard.replace: every instance needs an (E, {dim}) array of embeddings")
-        if clouds is not None:
-            if len(clouds) != len(embs) or any(x is not None and len(x) != len(embs) for x in (colors, intensities)):
-                raise ValueError("MemoryShard.replace: as many clouds (colours, intensities) as instances")
-            if any(np.asarray(c).ndim != 2 or np.asarray(c).shape[1] != 3 or len(c) == 0 for c in clouds):
-                raise ValueError("MemoryShard.replace: every cloud is a non-empty (n, 3) array")
-            sizes = np.diff(self.clouds.seg_off_host)
-            if self.clouds.n - int(sizes[given].sum()) + sum(len(c) for c in clouds) > 0x7FFFFFF0:
-                raise ValueError("MemoryShard.replace: more than 0x7FFFFFF0 memory points")
+        self._check_live("replace", "change")
+        given = self._check_instances("replace", instances)
+        leaving = 0 if self.clouds is None else int(np.diff(self.clouds.seg_off_host)[given].sum())
+        embs = self._check_new("replace", len(given), embeddings, clouds, colors, intensities, leaving)
         if not given:
             return
         by_index = np.argsort(given)                        # the library and the buffers take the instances in ascending order
-        idx = [given[i] for i in by_index]
-        embs = [embs[i] for i in by_index]
-        torch.cuda.synchronize(self.device)
-        # one scratch chunk for every splice below, allocated before anything is changed (132 B: the widest row, fpfh)
-        scratch = compact_scratch(self.device, max(self.mem_emb.numel() * 4, 0 if self.clouds is None else self.clouds.n * 132))
-        if clouds is not None:
-            if intensities is None:
-                intensities = [intensity_from_colors(c) for c in colors] if colors is not None else None
-            new = CloudBatch.from_numpy([clouds[i] for i in by_index], None if intensities is None else [intensities[i] for i in by_index],
-                                        device=self.device)
-            # the new instances' features first, from their own batch: nothing resident has changed if this raises
-            new_feat = {key: instance_features_batch(self.ctx, new, key[0], 2.0 * (key[0] * key[1]), compact=self.compact_features)
-                        for key in self._features}
-            # then the grid: the only step that can fail in the library, and it leaves the grid as it was when it does
-            edits = replaced_ranges(self.clouds.seg_off_host, idx, new.seg_off_host)
-            self.grid.replace([(b, e) for b, e, _, _ in edits], [ne - nb for _, _, nb, ne in edits], new.pts4)
-            self.clouds.replace(idx, new, scratch=scratch)
-            for key, feat in self._features.items():
-                feat.replace(idx, edits, new_feat[key], scratch=scratch)
-        rows = match.normalize_rows(torch.from_numpy(np.ascontiguousarray(np.concatenate(embs))).to(self.device))
-        new_off = np.concatenate([[0], np.cumsum([len(e) for e in embs])])
-        self._emb_buf, self.mem_emb = splice_rows(self._emb_buf, self.mem_emb.shape[0],
-                                                  [(b, e, rows[nb:ne]) for b, e, nb, ne in replaced_ranges(self.emb_offsets_host, idx, new_off)],
-                                                  scratch=scratch)
-        counts = np.diff(self.emb_offsets_host)
-        counts[idx] = np.diff(new_off)
-        self.emb_offsets_host = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
-        self.emb_offsets = torch.from_numpy(self.emb_offsets_host).to(self.device)
-        torch.cuda.synchronize(self.device)
+        ordered = [None if x is None else [x[i] for i in by_index] for x in (embs, clouds, colors, intensities)]
+        self._splice("replace", replaced([given[i] for i in by_index]), *ordered)
 
     def overlap(self, det: CloudBatch, radius=None, k=8):
         """Which resident instances does each detection overlap: `det` the detection clouds in the WORLD frame, radius the distance
@@ -286,10 +252,7 @@ class MemoryShard:
         hits = the detection's points with some point of the instance within radius (MemGrid.overlap, ibl_memgrid_overlap), and the
         uncut number of such instances.  Changes nothing; synchronises the current stream.  Raises ValueError for a sharded or
         non-live memory (the grid of a live memory alone knows the instance of a resident point) and for one without clouds."""
-        if self.shard is not None:
-            raise ValueError("MemoryShard.overlap: sharded memories cannot be associated with while resident")
-        if not self.live:
-            raise ValueError("MemoryShard.overlap: construct the shard with live=True")
+        self._check_live("overlap", "be associated with")
         if self.clouds is None:
             raise ValueError("MemoryShard.overlap: an embedding-only memory has no clouds to overlap")
         return self.grid.overlap(det.pts4, det.seg_off_host, self.clouds.seg_off, self.eval_threshold if radius is None else radius, k,

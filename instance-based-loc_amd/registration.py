@@ -70,68 +70,13 @@ class RegContext:
                 self.diag_set(name, value)
 
 
-def grow_rows(buf: torch.Tensor, n_used: int, rows: torch.Tensor):
-    """Rows appended to a device buffer with headroom (live memory): `rows` are copied behind the first n_used rows of `buf`; a buffer
-    that is too small is replaced by one 1.5 times as large (one copy of the used rows).  Returns (buffer, view of its used rows)."""
-    n = n_used + rows.shape[0]
-    if n > buf.shape[0]:
-        grown = torch.empty((max(n, buf.shape[0] + buf.shape[0] // 2),) + tuple(buf.shape[1:]), dtype=buf.dtype, device=buf.device)
-        grown[:n_used].copy_(buf[:n_used])
-        buf = grown
-    buf[n_used:n].copy_(rows)
-    return buf, buf[:n]
-
-
 COMPACT_SCRATCH_BYTES = 64 << 20
 
 
-def kept_runs(n, removed):
-    """the runs [(begin, end), ...] of 0 .. n - 1 that the ascending, disjoint half-open ranges `removed` leave"""
-    runs, at = [], 0
-    for b, e in removed:
-        if b > at:
-            runs.append((at, b))
-        at = e
-    if at < n:
-        runs.append((at, n))
-    return runs
-
-
-def merged_ranges(off, segments):
-    """the row ranges off[s] .. off[s + 1] of the ascending `segments`, neighbours joined and empty ones left out"""
-    out = []
-    for s in segments:
-        b, e = int(off[s]), int(off[s + 1])
-        if e == b:
-            continue
-        if out and out[-1][1] == b:
-            out[-1] = (out[-1][0], e)
-        else:
-            out.append((b, e))
-    return out
-
-
 def compact_scratch(device, bytes_needed=COMPACT_SCRATCH_BYTES):
-    """the scratch chunk of `compact_rows` as a tensor of its own (at most COMPACT_SCRATCH_BYTES): allocated once, before anything is
-    changed, by a caller that compacts several buffers in a row"""
+    """the scratch chunk of `splice_rows` as a tensor of its own (at most COMPACT_SCRATCH_BYTES): allocated once, before anything is
+    changed, by a caller that splices several buffers in a row"""
     return torch.empty((max(1, min(int(bytes_needed), COMPACT_SCRATCH_BYTES)),), dtype=torch.uint8, device=device)
-
-
-def compact_rows(buf: torch.Tensor, n_used: int, keep_runs, scratch_bytes=COMPACT_SCRATCH_BYTES, scratch=None):
-    """Rows taken out of a device buffer (live memory): the ascending, disjoint row runs `keep_runs` = [(begin, end), ...] of the
-    first n_used rows move to the front of `buf` IN PLACE -- a resident feature set is tens of GB and is never duplicated.  A run that
-    moves down by at least its length is one copy.  A run that overlaps its destination goes in ascending pieces: of the shift's
-    length, copied directly, when the shift is at least the scratch chunk, else through a scratch chunk of scratch_bytes (source
-    piece -> scratch -> destination), so the number of copies follows the chunk, never a small shift.  No copy is between overlapping
-    views.  Everything is queued on the current stream.  scratch: a `compact_scratch` tensor to use (its size then stands for
-    scratch_bytes) instead of allocating one when a run needs it.  Returns the view of the kept rows."""
-    chunk, scratch = _scratch_rows(buf, n_used, scratch_bytes, scratch)
-    at = 0
-    for b, e in keep_runs:
-        assert at <= b < e <= n_used
-        scratch = _move_rows(buf, b, at, e - b, chunk, scratch)
-        at += e - b
-    return buf[:at]
 
 
 def _scratch_rows(buf, n_used, scratch_bytes, scratch):
@@ -149,7 +94,8 @@ def _move_rows(buf, src, dst, length, chunk, scratch):
     """The rows [src, src + length) of `buf` move to [dst, dst + length), down or up.  A run that moves by at least its length is one
     copy.  A run that overlaps its destination goes in pieces, ascending when it moves down and descending when it moves up, so that
     no piece lands on rows still to be read: pieces of the shift's length, copied directly, when the shift is at least `chunk`
-    rows, else of `chunk` rows through `scratch` (allocated here when None).  No copy is between overlapping views.  Returns scratch."""
+    rows, else of `chunk` rows through `scratch` (allocated here when None), so the number of copies follows the chunk, never a
+    small shift.  No copy is between overlapping views.  Returns scratch."""
     shift = abs(src - dst)
     if shift >= length:
         buf[dst:dst + length].copy_(buf[src:src + length])
@@ -170,16 +116,17 @@ def _move_rows(buf, src, dst, length, chunk, scratch):
 
 
 def splice_rows(buf: torch.Tensor, n_used: int, edits, scratch=None, scratch_bytes=COMPACT_SCRATCH_BYTES):
-    """Rows replaced in the middle of a buffer with headroom (live memory): `edits` = [(begin, end, new_rows), ...], ascending and
-    disjoint over the first n_used rows of `buf`; the rows [begin, end) give way to new_rows (a tensor of any number of rows of
-    buf's row shape: none is a removal, begin == end an insertion).  IN PLACE while the result fits -- a resident array is never
-    duplicated: the kept runs between the edits move first, those that move down in ascending and then those that move up in
-    descending order (`_move_rows`: through one bounded scratch chunk, as `compact_rows`), and the new rows are written last.  In
-    that order no run lands on rows another run has yet to leave: a run that moves down lands below its own end, which lies below
-    every later run; a run that moves up lands above its own begin, above every earlier run; and the later runs that move up, and
-    every run that moves down, have left by then.  A result that does not fit is built once into a buffer 1.5 times as large.
-    Any device; everything is queued on the current stream.  scratch / scratch_bytes: see `compact_rows`.
-    Returns (buffer, view of its used rows)."""
+    """The one way rows enter, leave or change place in a buffer with headroom (live memory): `edits` = [(begin, end, new_rows), ...],
+    ascending and disjoint over the first n_used rows of `buf`; the rows [begin, end) give way to new_rows (a tensor of any number
+    of rows of buf's row shape: none is a removal, begin == end an insertion, one insertion at n_used an append).  IN PLACE while
+    the result fits -- a resident feature set is tens of GB and is never duplicated: the kept runs between the edits move first,
+    those that move down in ascending and then those that move up in descending order (`_move_rows`: through one bounded scratch
+    chunk of scratch_bytes), and the new rows are written last.  In that order no run lands on rows another run has yet to leave: a
+    run that moves down lands below its own end, which lies below every later run; a run that moves up lands above its own begin,
+    above every earlier run; and the later runs that move up, and every run that moves down, have left by then.  A result that does
+    not fit is built once into a buffer 1.5 times as large (one copy of the kept rows).  Any device; everything is queued on the
+    current stream.  scratch: a `compact_scratch` tensor to use (its size then stands for scratch_bytes) instead of allocating one
+    when a run needs it.  Returns (buffer, view of its used rows)."""
     moves, fresh, at, to = [], [], 0, 0                  # (source, destination, length) of kept runs, (destination, rows) of new ones
     for b, e, rows in edits:
         assert at <= b <= e <= n_used and tuple(rows.shape[1:]) == tuple(buf.shape[1:])
@@ -211,18 +158,54 @@ def splice_rows(buf: torch.Tensor, n_used: int, edits, scratch=None, scratch_byt
     return buf, buf[:to]
 
 
-def replaced_ranges(off, segments, new_off):
-    """the edits [(begin, end, new_begin, new_end), ...] that put segment i of a batch with offsets `new_off` in the place of
-    segment segments[i] (ascending, distinct) of a batch with offsets `off`: row ranges of the old and of the new batch, neighbours
-    joined, edits of nothing by nothing left out"""
+# An edit of a live batch is written once, on its segments: [(seg_begin, seg_end, new_begin, new_end), ...] -- ascending and disjoint;
+# the segments [seg_begin, seg_end) give way to the segments [new_begin, new_end) of a batch of new clouds.  The three verbs:
+def appended(n_seg, n_new):
+    """the segment edit that puts n_new new segments behind the n_seg resident ones"""
+    return [(n_seg, n_seg, 0, n_new)]
+
+
+def removed(segments):
+    """the segment edits that take the ascending `segments` out"""
+    return [(s, s + 1, 0, 0) for s in segments]
+
+
+def replaced(segments):
+    """the segment edits that put new segment i in the place of segments[i] (ascending)"""
+    return [(s, s + 1, i, i + 1) for i, s in enumerate(segments)]
+
+
+def row_edits(off, seg_edits, new_off=(0,)):
+    """the row edits [(begin, end, new_begin, new_end), ...] of the segment edits `seg_edits` on a batch with offsets `off`, the new
+    batch's being `new_off`: row ranges of the old and of the new batch, neighbours joined, edits of nothing by nothing left out"""
     out = []
-    for i, s in enumerate(segments):
-        b, e, nb, ne = int(off[s]), int(off[s + 1]), int(new_off[i]), int(new_off[i + 1])
+    for sb, se, snb, sne in seg_edits:
+        b, e, nb, ne = int(off[sb]), int(off[se]), int(new_off[snb]), int(new_off[sne])
         if out and out[-1][1] == b:
             out[-1] = (out[-1][0], e, out[-1][2], ne)
         elif e > b or ne > nb:
             out.append((b, e, nb, ne))
     return [x for x in out if x[1] > x[0] or x[3] > x[2]]
+
+
+def spliced_host(per_seg, seg_edits, new_per_seg):
+    """the per-segment host array (sizes, bounding boxes) after the segment edits: rows [seg_begin, seg_end) give way to
+    new_per_seg[new_begin:new_end]"""
+    parts, at = [], 0
+    for sb, se, nb, ne in seg_edits:
+        parts += [per_seg[at:sb], new_per_seg[nb:ne]]
+        at = se
+    return np.ascontiguousarray(np.concatenate(parts + [per_seg[at:]]))
+
+
+def offsets_of(sizes):
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+
+
+def _spliced_rows(buf, n_used, edits, rows, scratch):
+    """`splice_rows` for row edits whose new rows are rows[new_begin:new_end] (rows = None: nothing new)"""
+    rows = buf[:0] if rows is None else rows
+    return splice_rows(buf, n_used, [(b, e, rows[nb:ne]) for b, e, nb, ne in edits], scratch=scratch)
 
 
 class CloudBatch:
@@ -273,49 +256,45 @@ class CloudBatch:
         batch._buf = buf
         return batch
 
+    def _splice(self, seg_edits, new: "CloudBatch" = None, scratch=None):
+        """The one edit behind `append`, `remove` and `replace`: the segment edits `seg_edits` (above `row_edits`) with the clouds of
+        `new` (None: nothing new).  The rows move in the backing buffer (`splice_rows`), the offsets follow from the sizes.  Returns
+        the row edits."""
+        new_off = (0,) if new is None else new.seg_off_host
+        edits = row_edits(self.seg_off_host, seg_edits, new_off)
+        if self.n + sum((ne - nb) - (e - b) for b, e, nb, ne in edits) > 0x7FFFFFF0:
+            raise ValueError("more than 0x7FFFFFF0 points in a cloud batch")
+        self._buf, self.pts4 = _spliced_rows(self._buf, self.n, edits, None if new is None else new.pts4, scratch)
+        self.seg_off_host = offsets_of(spliced_host(np.diff(self.seg_off_host), seg_edits, np.diff(new_off)))
+        self.seg_off = torch.from_numpy(self.seg_off_host).to(self.pts4.device)
+        return edits
+
     def append(self, clouds, intensities=None):
         """Further clouds behind the last one (segments n_seg ..): `clouds` / `intensities` as `from_numpy` takes them, or a CloudBatch
         on the same device.  Only the new points are copied unless the buffer has to grow (by 1.5).  `pts4` and `seg_off` are NEW
         tensor objects afterwards (pts4 a longer view of the same buffer when it did not grow)."""
         new = clouds if isinstance(clouds, CloudBatch) else CloudBatch.from_numpy(clouds, intensities, device=self.pts4.device)
-        if int(self.seg_off_host[-1]) + new.n > 0x7FFFFFF0:
-            raise ValueError("more than 0x7FFFFFF0 points in a cloud batch")
-        self._buf, self.pts4 = grow_rows(self._buf, self.n, new.pts4[:new.n])
-        self.seg_off_host = np.concatenate([self.seg_off_host, self.seg_off_host[-1] + new.seg_off_host[1:]]).astype(np.int32)
-        self.seg_off = torch.from_numpy(self.seg_off_host).to(self.pts4.device)
+        self._splice(appended(self.n_seg, new.n_seg), new)
         return new
 
     def remove(self, segments, scratch=None):
         """Takes the clouds `segments` (ascending, distinct segment indices; not all of them) out of the batch: the later clouds move
-        down in the backing buffer (`compact_rows`, in place) and take the lower segment indices.  `pts4` and `seg_off` are NEW tensor
+        down in the backing buffer (`splice_rows`, in place) and take the lower segment indices.  `pts4` and `seg_off` are NEW tensor
         objects afterwards.  Returns the point ranges [(begin, end), ...] that were removed, in the numbering before the call
-        (neighbouring clouds joined) -- what `MemGrid.remove` and `InstanceFeatures.remove` take.  scratch: see `compact_rows`."""
+        (neighbouring clouds joined) -- what `MemGrid.remove` and `InstanceFeatures.remove` take.  scratch: see `splice_rows`."""
         segments = [int(s) for s in segments]
         assert all(a < b for a, b in zip([-1] + segments, segments + [self.n_seg])) and len(segments) < self.n_seg
-        ranges = merged_ranges(self.seg_off_host, segments)
-        self.pts4 = compact_rows(self._buf, self.n, kept_runs(self.n, ranges), scratch=scratch)
-        sizes = np.delete(np.diff(self.seg_off_host), segments)
-        self.seg_off_host = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-        self.seg_off = torch.from_numpy(self.seg_off_host).to(self.pts4.device)
-        return ranges
+        return [(b, e) for b, e, _, _ in self._splice(removed(segments), scratch=scratch)]
 
     def replace(self, segments, new_batch: "CloudBatch", scratch=None):
         """Puts cloud i of `new_batch` (a CloudBatch on the same device with len(segments) clouds) in the place of the cloud
         segments[i] (ascending, distinct segment indices): every cloud keeps its segment index, the clouds behind a replaced one move
         in the backing buffer (`splice_rows`: in place unless it has to grow by 1.5).  `pts4` and `seg_off` are NEW tensor objects
-        afterwards.  Returns the edits [(begin, end, new_begin, new_end), ...] (`replaced_ranges`: point ranges in the numbering
+        afterwards.  Returns the edits [(begin, end, new_begin, new_end), ...] (`row_edits`: point ranges in the numbering
         before the call and the rows of new_batch that took their place) -- what `InstanceFeatures.replace` takes."""
         segments = [int(s) for s in segments]
         assert all(a < b for a, b in zip([-1] + segments, segments + [self.n_seg])) and new_batch.n_seg == len(segments)
-        edits = replaced_ranges(self.seg_off_host, segments, new_batch.seg_off_host)
-        if self.n + sum((ne - nb) - (e - b) for b, e, nb, ne in edits) > 0x7FFFFFF0:
-            raise ValueError("more than 0x7FFFFFF0 points in a cloud batch")
-        self._buf, self.pts4 = splice_rows(self._buf, self.n, [(b, e, new_batch.pts4[nb:ne]) for b, e, nb, ne in edits], scratch=scratch)
-        sizes = np.diff(self.seg_off_host)
-        sizes[segments] = np.diff(new_batch.seg_off_host)
-        self.seg_off_host = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-        self.seg_off = torch.from_numpy(self.seg_off_host).to(self.pts4.device)
-        return edits
+        return self._splice(replaced(segments), new_batch, scratch=scratch)
 
 
 def unproject_masks(ctx: RegContext, depth: torch.Tensor, rgb: torch.Tensor, masks: torch.Tensor, fx: float, fy: float,
@@ -417,67 +396,48 @@ class InstanceFeatures:
         self.n, self.n_seg = n, n_seg          # points / clouds described (instance_features_batch sets them; `append` needs them)
         self._bufs = {}                        # backing buffers of arrays that are views with headroom behind them
 
+    def _splice(self, verb, seg_edits, edits, new: "InstanceFeatures" = None, scratch=None):
+        """The one edit behind `append`, `remove` and `replace`: the segment edits `seg_edits` and their row edits `edits` (those of
+        the clouds' batch) with the features `new` (None: nothing new).  Every device array that is present is spliced in its backing
+        buffer (`splice_rows`), the bounding-box rows of the clouds follow the segments."""
+        if self.n is None or (new is not None and new.n is None):
+            raise ValueError(f"InstanceFeatures.{verb}: point counts unknown (features not made by instance_features_batch)")
+        if new is not None:
+            if (self.voxel_size, self.grad_radius) != (new.voxel_size, new.grad_radius):
+                raise ValueError(f"InstanceFeatures.{verb}: the features were computed with other parameters")
+            for name in self.DEVICE_ARRAYS:
+                if (getattr(self, name) is None) != (getattr(new, name) is None):
+                    raise ValueError(f"InstanceFeatures.{verb}: `{name}` is present on one side only")
+            if new.n_seg != sum(ne - nb for _, _, nb, ne in seg_edits):
+                raise ValueError(f"InstanceFeatures.{verb}: as many new clouds as segments")
+        for name in self.DEVICE_ARRAYS:
+            cur = getattr(self, name)
+            if cur is not None:
+                self._bufs[name], view = _spliced_rows(self._bufs.get(name, cur), self.n, edits, None if new is None else getattr(new, name), scratch)
+                setattr(self, name, view)
+        self.bbox = spliced_host(self.bbox[:self.n_seg], seg_edits, self.bbox[:0] if new is None else new.bbox[:new.n_seg])
+        self.n += sum((ne - nb) - (e - b) for b, e, nb, ne in edits)
+        self.n_seg = len(self.bbox)
+
     def append(self, new: "InstanceFeatures"):
         """Attaches the features of further clouds (computed on their own: a feature depends on its own cloud only, DESIGN (c)
         conventions 5 and 7) behind the resident ones.  Same parameters and same form (compact or not, with gradients or not) only.
         The arrays are views of buffers with headroom; only the new rows are copied unless a buffer has to grow (by 1.5)."""
-        if self.n is None or new.n is None:
-            raise ValueError("InstanceFeatures.append: point counts unknown (features not made by instance_features_batch)")
-        if (self.voxel_size, self.grad_radius) != (new.voxel_size, new.grad_radius):
-            raise ValueError("InstanceFeatures.append: the features were computed with other parameters")
-        for name in self.DEVICE_ARRAYS:
-            if (getattr(self, name) is None) != (getattr(new, name) is None):
-                raise ValueError(f"InstanceFeatures.append: `{name}` is present on one side only")
-        for name in self.DEVICE_ARRAYS:
-            cur = getattr(self, name)
-            if cur is not None:
-                self._bufs[name], view = grow_rows(self._bufs.get(name, cur), self.n, getattr(new, name)[:new.n])
-                setattr(self, name, view)
-        self.bbox = np.ascontiguousarray(np.concatenate([self.bbox[:self.n_seg], new.bbox[:new.n_seg]]))
-        self.n += new.n
-        self.n_seg += new.n_seg
+        self._splice("append", appended(self.n_seg, new.n_seg), [(self.n, self.n, 0, new.n)], new)
 
     def remove(self, segments, point_ranges, scratch=None):
         """Takes the features of the clouds `segments` (ascending, distinct) out: `point_ranges` are the point ranges of those clouds
         as `CloudBatch.remove` returns them.  Every device array that is present is compacted in its backing buffer
-        (`compact_rows`: in place, nothing is duplicated or recomputed -- a feature depends on its own cloud only), the bounding-box
-        rows of the clouds are dropped.  scratch: see `compact_rows`."""
-        if self.n is None:
-            raise ValueError("InstanceFeatures.remove: point counts unknown (features not made by instance_features_batch)")
-        runs = kept_runs(self.n, point_ranges)
-        for name in self.DEVICE_ARRAYS:
-            cur = getattr(self, name)
-            if cur is not None:
-                self._bufs[name] = self._bufs.get(name, cur)
-                setattr(self, name, compact_rows(self._bufs[name], self.n, runs, scratch=scratch))
-        self.bbox = np.ascontiguousarray(np.delete(self.bbox[:self.n_seg], list(segments), axis=0))
-        self.n = sum(e - b for b, e in runs)
-        self.n_seg -= len(segments)
+        (`splice_rows`: in place, nothing is duplicated or recomputed -- a feature depends on its own cloud only), the bounding-box
+        rows of the clouds are dropped.  scratch: see `splice_rows`."""
+        self._splice("remove", removed(list(segments)), [(b, e, 0, 0) for b, e in point_ranges], scratch=scratch)
 
     def replace(self, segments, point_ranges, new: "InstanceFeatures", scratch=None):
         """Puts the features `new` of len(segments) clouds (computed on their own, as for `append`) in the place of those of the
         clouds `segments` (ascending, distinct): `point_ranges` are the edits `CloudBatch.replace` returns.  Same parameters and same
         form only, as `append`.  Every device array that is present is spliced in its backing buffer (`splice_rows`: in place
         unless it has to grow, nothing resident is recomputed), the bounding-box rows of the clouds are replaced."""
-        if self.n is None or new.n is None:
-            raise ValueError("InstanceFeatures.replace: point counts unknown (features not made by instance_features_batch)")
-        if (self.voxel_size, self.grad_radius) != (new.voxel_size, new.grad_radius):
-            raise ValueError("InstanceFeatures.replace: the features were computed with other parameters")
-        for name in self.DEVICE_ARRAYS:
-            if (getattr(self, name) is None) != (getattr(new, name) is None):
-                raise ValueError(f"InstanceFeatures.replace: `{name}` is present on one side only")
-        if new.n_seg != len(segments):
-            raise ValueError("InstanceFeatures.replace: as many new clouds as segments")
-        for name in self.DEVICE_ARRAYS:
-            cur = getattr(self, name)
-            if cur is not None:
-                rows = getattr(new, name)
-                self._bufs[name], view = splice_rows(self._bufs.get(name, cur), self.n, [(b, e, rows[nb:ne]) for b, e, nb, ne in point_ranges],
-                                                     scratch=scratch)
-                setattr(self, name, view)
-        self.bbox = np.array(self.bbox[:self.n_seg], order="C")
-        self.bbox[list(segments)] = new.bbox[:new.n_seg]
-        self.n += sum((ne - nb) - (e - b) for b, e, nb, ne in point_ranges)
+        self._splice("replace", replaced(list(segments)), point_ranges, new, scratch=scratch)
 
     def as_struct(self):
         return _FeatStruct(self.normals.data_ptr(), self.fpfh.data_ptr(), self.fpfh_split.data_ptr() if self.fpfh_split is not None else None,

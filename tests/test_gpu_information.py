@@ -12,7 +12,7 @@ tests/information_cases.py (tests/test_information_model.py shows with the refer
                 (n - 1) 2^-53 sum |t|, and an entry adds up to two such sums), about = None, the inlier centroid and, on slab_far,
                 BASES["far"]; symmetric bit for bit; an empty job gives zeros
     determinism a second call gives the same bytes; a live grid built in two appends, with a range removed and put back, gives the
-                bytes of the grid built at once (slab_far, where the ties are)
+                bytes of the grid built at once (slab_far, where the ties are), and so does `evaluate_points` on it
     jobs        empty jobs first, in the middle and last and overlapping ranges (`jobs`); 65 539 jobs across the launch boundary
     refusals    null pointers, threshold <= 0, n_jobs <= 0, a descending range: IblError, outputs untouched
     engine      localise_batch(information=True) equals a direct call on the staged path's cleaned points, fused and staged alike
@@ -123,12 +123,22 @@ def test_every_point_and_every_matrix(ctx, name):
 
 def test_live_grid_after_edits_gives_the_bytes_of_a_fresh_grid(ctx):
     """slab_far (its ties are between distinct coordinates): a live grid built from the first 40 000 points, the rest appended, a
-    range taken out and put back in its place -- the order inside the cells has been rebuilt three times"""
-    from ibloc_amd.registration import MemGrid
+    range taken out and put back in its place -- the order inside the cells has been rebuilt three times.  The information matrix
+    and the evaluation (`evaluate_points`: every d2, rmse and fitness) give the bytes of the grid built at once, pruned scan and
+    eval_fullscan alike."""
+    from ibloc_amd.registration import MemGrid, evaluate_points
+
+    def evaluated(grid, full):
+        with ctx.diag(eval_fullscan=1 if full else 0):
+            d2, rmse, fit = evaluate_points(ctx, grid, det4, fam["jb"], fam["je"], fam["T"], fam["thr"])
+        return d2.cpu().numpy().tobytes(), rmse.tobytes(), fit.tobytes()
+
     fam = ec.get(ic.TIE_FAMILY)
     mem4, det4 = pts4(fam["mem"]), pts4(fam["det"])
     fresh = MemGrid(ctx, mem4, fam["cell"])
     info, n_corr, nn = run(ctx, fam, fresh, det4)
+    ev = evaluated(fresh, False)
+    assert evaluated(fresh, True) == ev
     fresh.close()
     live = MemGrid(ctx, mem4[:40000].contiguous(), fam["cell"], live=True, reserve_points=30000)
     live.append(mem4[40000:].contiguous())
@@ -136,11 +146,13 @@ def test_live_grid_after_edits_gives_the_bytes_of_a_fresh_grid(ctx):
     assert live.info()["n"] == len(mem4) - 15000
     info_r, _, _ = run(ctx, fam, live, det4)
     assert info_r.tobytes() != info.tobytes()                       # (the removed points were matched by something)
+    assert evaluated(live, False) != ev
     live.replace([(10000, 10000)], [15000], mem4[10000:25000].contiguous())
     assert live.info()["n"] == len(mem4)
     for full in (False, True):
         info_l, n_l, nn_l = run(ctx, fam, live, det4, full=full)
         assert info_l.tobytes() == info.tobytes() and n_l.tobytes() == n_corr.tobytes() and nn_l.tobytes() == nn.tobytes()
+        assert evaluated(live, full) == ev
     live.close()
 
 

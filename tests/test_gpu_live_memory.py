@@ -9,6 +9,9 @@ import pytest
 import torch
 from scipy.spatial import cKDTree
 
+from tests.live_memory_helpers import (assert_same_features, assert_same_grid, assert_same_results, point_distances, pts4_of, run_frames,
+                                       same_bits)
+
 pytestmark = pytest.mark.gpu
 
 SIZES = (300, 520, 800, 410, 650, 380, 740, 560)          # points per instance: the first is the smallest (growth test)
@@ -43,12 +46,6 @@ def ctx():
     c.close()
 
 
-def pts4_of(clouds, colors):
-    from ibloc_amd.engine import intensity_from_colors
-    from ibloc_amd.registration import CloudBatch
-    return CloudBatch.from_numpy(clouds, [intensity_from_colors(c) for c in colors]).pts4
-
-
 def cells_of(p, cell=CELL):
     """cell triples as the grid computes them: floorf(float(p) * (1.0f / float(cell)))"""
     inv = np.float32(1.0) / np.float32(cell)
@@ -72,25 +69,6 @@ def queries(pts, n_old):
                   mixed_cell=sum(c in old_cells and c in new_cells for c in qc),
                   new_cell=sum(c in new_cells and c not in old_cells for c in qc), none=int((dmin > THR * 1.001).sum()))
     return q, counts
-
-
-def point_distances(ctx, grid, q, thr=THR):
-    from ibloc_amd.registration import evaluate_points
-    q4 = torch.from_numpy(np.concatenate([q, np.zeros((len(q), 1), np.float32)], axis=1)).cuda().contiguous()
-    d2, rmse, fit = evaluate_points(ctx, grid, q4, [0], [len(q)], np.eye(4)[None], thr)
-    return d2.cpu().numpy(), float(rmse[0]), float(fit[0])
-
-
-def assert_same_grid(ctx, live, fresh, q, thr=THR):
-    a, b = live.info(), fresh.info()
-    assert (a["n"], a["n_cells"], a["table_slots"]) == (b["n"], b["n_cells"], b["table_slots"]), (a, b)
-    assert a["ustart_end"] == a["n"] == b["ustart_end"]
-    da, rmse_a, fit_a = point_distances(ctx, live, q, thr)
-    db, rmse_b, fit_b = point_distances(ctx, fresh, q, thr)
-    assert np.array_equal(np.isinf(da), np.isinf(db))
-    assert da.tobytes() == db.tobytes()
-    assert (rmse_a, fit_a) == (rmse_b, fit_b)
-    return da
 
 
 @pytest.mark.parametrize("first,steps", [(7, (1,)), (1, (7,)), (4, (1, 1, 1, 1))], ids=["7+1", "1+7", "4+1+1+1+1"])
@@ -151,24 +129,6 @@ def test_growth_noop_and_arena_refusal(ctx):
     live.close()
 
 
-def same_bits(a, b):
-    if a is None or b is None:
-        return a is None and b is None
-    a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    b = b.cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def assert_same_features(fa, fb, n, n_seg, compact):
-    assert (fa.fpfh_split is None) == compact == (fb.fpfh_split is None)
-    for name in ("normals", "fpfh", "fpfh_split", "fpfh_norm", "grad"):
-        a, b = getattr(fa, name), getattr(fb, name)
-        assert same_bits(None if a is None else a[:n], None if b is None else b[:n]), name
-    assert fa.grad is not None
-    assert same_bits(fa.bbox[:n_seg], fb.bbox[:n_seg])
-    assert (fa.voxel_size, fa.grad_radius) == (fb.voxel_size, fb.grad_radius)
-
-
 @pytest.mark.parametrize("compact", [False, True], ids=["full", "compact"])
 def test_resident_state_equals_rebuilt(ctx, compact):
     from ibloc_amd.engine import MemoryShard
@@ -190,26 +150,6 @@ def test_resident_state_equals_rebuilt(ctx, compact):
     assert live.grid.info()["n"] == plain.grid.info()["n"] == n and live.grid.info()["n_cells"] == plain.grid.info()["n_cells"]
     live.close()
     plain.close()
-
-
-def run_frames(eng, frames):
-    from ibloc_amd.engine import intensity_from_colors
-    from ibloc_amd.registration import CloudBatch
-    det = CloudBatch.from_numpy([c[0] for f in frames for c in f["clouds"]], [intensity_from_colors(c[1]) for f in frames for c in f["clouds"]])
-    return eng.localise_batch(det, [len(f["ids"]) for f in frames], det_emb=np.concatenate([f["det_emb"] for f in frames]),
-                              fpfh_voxel_size=0.05, fpfh_global_dist_factor=1.5, fpfh_local_dist_factor=1.5, seed=7)
-
-
-def assert_same_results(ra, rb):
-    assert len(ra) == len(rb)
-    for a, b in zip(ra, rb):
-        assert a.assignments == b.assignments and a.best == b.best and a.n_clean == b.n_clean
-        assert a.pose.tobytes() == b.pose.tobytes() and a.pose_corrected.tobytes() == b.pose_corrected.tobytes()
-        assert len(a.records) == len(b.records)
-        for x, y in zip(a.records, b.records):
-            assert x["fitness"] == y["fitness"] and x["rmse"] == y["rmse"]
-            assert x["full_fitness"] == y["full_fitness"] and x["full_rmse"] == y["full_rmse"]
-            assert x["T"].tobytes() == y["T"].tobytes() and x["T_global"].tobytes() == y["T_global"].tobytes()
 
 
 def test_localise_after_append_equals_rebuilt(ctx):

@@ -2,7 +2,6 @@
 MemoryShard(live=True).remove, ObjectMemory.remove_objects) holds, array for array, what a memory built from the kept instances holds,
 and localises to the same results bit for bit.  Every comparison is with an object built fresh from the kept instances.
 tests/test_live_remove_model.py shows that the removal sets contain the cases they are named for."""
-import copy
 import ctypes as C
 
 import numpy as np
@@ -12,6 +11,8 @@ from scipy.spatial import cKDTree
 
 from tests import live_remove_cases as lc
 from tests.live_remove_cases import CELL, SIZES, THR
+from tests.live_memory_helpers import (assert_same_features, assert_same_grid, assert_same_results, exported, frame_of, grid_state, pick,
+                                       point_distances, pts4_of, queries, run_frames, same_bits)
 
 pytestmark = pytest.mark.gpu
 
@@ -22,57 +23,6 @@ def ctx():
     c = RegContext(2 << 30)
     yield c
     c.close()
-
-
-def pts4_of(clouds, colors):
-    from ibloc_amd.engine import intensity_from_colors
-    from ibloc_amd.registration import CloudBatch
-    return CloudBatch.from_numpy(clouds, [intensity_from_colors(c) for c in colors]).pts4
-
-
-def pick(xs, idx):
-    return [xs[i] for i in idx]
-
-
-def queries(pts):
-    """~4 000 query points: 3 600 around the points of `pts` (2 mm-1 cm off them) and 400 far from everything"""
-    rng = np.random.default_rng(73)
-    allp = np.concatenate(pts).astype(np.float32)
-    near = allp[rng.choice(len(allp), 3600)] + rng.normal(0, 0.004, size=(3600, 3)).astype(np.float32)
-    far = allp[rng.choice(len(allp), 400)] + np.array([0, 0, 25.0], dtype=np.float32)
-    return np.concatenate([near, far]).astype(np.float32)
-
-
-def point_distances(ctx, grid, q, thr=THR):
-    from ibloc_amd.registration import evaluate_points
-    q4 = torch.from_numpy(np.concatenate([q, np.zeros((len(q), 1), np.float32)], axis=1)).cuda().contiguous()
-    d2, rmse, fit = evaluate_points(ctx, grid, q4, [0], [len(q)], np.eye(4)[None], thr)
-    return d2.cpu().numpy(), float(rmse[0]), float(fit[0])
-
-
-def exported(grid):
-    return {k: v.cpu().numpy() for k, v in grid.export().items()}
-
-
-def grid_state(ctx, grid, q, thr=THR):
-    """everything a refused call must leave alone"""
-    return grid.info(), {k: v.tobytes() for k, v in exported(grid).items()}, point_distances(ctx, grid, q, thr)[0].tobytes()
-
-
-def assert_same_grid(ctx, live, fresh, q, thr=THR):
-    a, b = live.info(), fresh.info()
-    assert (a["n"], a["n_cells"], a["table_slots"]) == (b["n"], b["n_cells"], b["table_slots"]), (a, b)
-    assert a["ustart_end"] == a["n"] == b["ustart_end"]
-    ea, eb = exported(live), exported(fresh)
-    for name in ("sorted", "ukeys", "ustart"):
-        assert ea[name].shape == eb[name].shape and ea[name].tobytes() == eb[name].tobytes(), name
-    assert ea["sorted"].shape == (a["n"], 4) and ea["ukeys"].shape == (a["n_cells"],) and ea["ustart"][-1] == a["n"]
-    da, rmse_a, fit_a = point_distances(ctx, live, q, thr)
-    db, rmse_b, fit_b = point_distances(ctx, fresh, q, thr)
-    assert np.array_equal(np.isinf(da), np.isinf(db))
-    assert da.tobytes() == db.tobytes()
-    assert (rmse_a, fit_a) == (rmse_b, fit_b)
-    return da
 
 
 @pytest.mark.parametrize("name", sorted(lc.REMOVAL_SETS))
@@ -211,26 +161,6 @@ def test_grid_refusals_touch_nothing(ctx):
     live.close()
 
 
-def same_bits(a, b):
-    if a is None or b is None:
-        return a is None and b is None
-    a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    b = b.cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def assert_same_features(fa, fb, n, n_seg, compact):
-    assert (fa.fpfh_split is None) == compact == (fb.fpfh_split is None)
-    assert (fa.n, fa.n_seg) == (fb.n, fb.n_seg) == (n, n_seg)
-    for name in ("normals", "fpfh", "fpfh_split", "fpfh_norm", "grad"):
-        a, b = getattr(fa, name), getattr(fb, name)
-        assert same_bits(None if a is None else a[:n], None if b is None else b[:n]), name
-        assert a is None or a.shape[0] == n, name
-    assert fa.grad is not None
-    assert same_bits(fa.bbox[:n_seg], fb.bbox[:n_seg])
-    assert (fa.voxel_size, fa.grad_radius) == (fb.voxel_size, fb.grad_radius)
-
-
 @pytest.mark.parametrize("compact", [False, True], ids=["full", "compact"])
 def test_resident_state_equals_rebuilt(ctx, compact):
     from ibloc_amd.engine import MemoryShard
@@ -257,30 +187,31 @@ def test_resident_state_equals_rebuilt(ctx, compact):
 
 @pytest.mark.parametrize("shape", [(64, 3), (64,), (64, 2, 5)], ids=["rows", "scalars", "blocks"])
 def test_compact_rows_in_place(shape):
-    from ibloc_amd.registration import compact_rows, compact_scratch, kept_runs
+    from ibloc_amd.registration import compact_scratch, splice_rows
     host = np.arange(int(np.prod(shape)), dtype=np.float32).reshape(shape) + 0.5
     row_bytes = host[0].nbytes
+
+    def removed_leaving(n_used, runs):
+        """the row ranges of 0 .. n_used - 1 outside the ascending, disjoint `runs`"""
+        ends, begins = [0] + [e for _, e in runs], [b for b, _ in runs] + [n_used]
+        return [(b, e) for b, e in zip(ends, begins) if e > b]
+
+    assert removed_leaving(50, [(2, 9), (11, 20), (33, 50)]) == [(0, 2), (9, 11), (20, 33)]
     # with a scratch chunk of 4 rows: a run shorter than its shift (one copy), runs that overlap their destination with a shift below
     # the chunk (through the scratch) and with a shift of at least the chunk (direct pieces), and a prefix that stays where it is
     for n_used, runs in ((60, [(1, 4), (10, 40), (45, 47), (50, 60)]), (64, [(0, 5), (7, 30), (31, 64)]), (64, [(3, 64)]), (64, [(40, 64)]),
-                         (50, kept_runs(50, [(0, 2), (9, 11), (20, 33)]))):
+                         (50, [(2, 9), (11, 20), (33, 50)])):
         for scratch_bytes in (4 * row_bytes, 1, 64 << 20, -4 * row_bytes, -1):
             buf = torch.from_numpy(host).cuda()
             keep_index = np.concatenate([np.arange(b, e) for b, e in runs])
+            edits = [(b, e, buf[:0]) for b, e in removed_leaving(n_used, runs)]
             if scratch_bytes < 0:                                 # the caller's own scratch tensor, of that many bytes
-                out = compact_rows(buf, n_used, runs, scratch=compact_scratch(buf.device, -scratch_bytes))
+                out_buf, out = splice_rows(buf, n_used, edits, scratch=compact_scratch(buf.device, -scratch_bytes))
             else:
-                out = compact_rows(buf, n_used, runs, scratch_bytes=scratch_bytes)
-            assert out.data_ptr() == buf.data_ptr() and out.shape == (len(keep_index),) + tuple(shape[1:])
+                out_buf, out = splice_rows(buf, n_used, edits, scratch_bytes=scratch_bytes)
+            assert out_buf is buf and out.data_ptr() == buf.data_ptr() and out.shape == (len(keep_index),) + tuple(shape[1:])
             assert out.cpu().numpy().tobytes() == host[keep_index].tobytes(), (n_used, runs, scratch_bytes)
             assert buf[n_used:].cpu().numpy().tobytes() == host[n_used:].tobytes()         # nothing behind the used rows is touched
-
-
-def frame_of(w, rng, ids):
-    """a query frame that sees exactly the objects `ids` (SynthWorld.make_frame picks an anchor's neighbours: here they are given)"""
-    seen = copy.copy(w)
-    seen.neighbours = lambda anchor, q: list(ids)
-    return seen.make_frame(rng, q=len(ids), pts_per_object=800, anchor=ids[0])
 
 
 def surviving_frames(removed):
@@ -289,26 +220,6 @@ def surviving_frames(removed):
     frames = [frame_of(w, rng, ids) for ids in ([7, 4, 6], [5, 2, 0], [2, 4], [6, 0, 5])]
     assert not any(i in removed for f in frames for i in f["ids"])
     return frames
-
-
-def run_frames(eng, frames):
-    from ibloc_amd.engine import intensity_from_colors
-    from ibloc_amd.registration import CloudBatch
-    det = CloudBatch.from_numpy([c[0] for f in frames for c in f["clouds"]], [intensity_from_colors(c[1]) for f in frames for c in f["clouds"]])
-    return eng.localise_batch(det, [len(f["ids"]) for f in frames], det_emb=np.concatenate([f["det_emb"] for f in frames]),
-                              fpfh_voxel_size=0.05, fpfh_global_dist_factor=1.5, fpfh_local_dist_factor=1.5, seed=7)
-
-
-def assert_same_results(ra, rb):
-    assert len(ra) == len(rb)
-    for a, b in zip(ra, rb):
-        assert a.assignments == b.assignments and a.best == b.best and a.n_clean == b.n_clean
-        assert a.pose.tobytes() == b.pose.tobytes() and a.pose_corrected.tobytes() == b.pose_corrected.tobytes()
-        assert len(a.records) == len(b.records)
-        for x, y in zip(a.records, b.records):
-            assert x["fitness"] == y["fitness"] and x["rmse"] == y["rmse"]
-            assert x["full_fitness"] == y["full_fitness"] and x["full_rmse"] == y["full_rmse"]
-            assert x["T"].tobytes() == y["T"].tobytes() and x["T_global"].tobytes() == y["T_global"].tobytes()
 
 
 def test_localise_after_remove_equals_rebuilt(ctx):

@@ -105,6 +105,15 @@ EDITS = [  # (rows used, [(begin, end, new rows)]) in a buffer of 64 rows
     (50, [(50, 50, 14)]),                                   # an append
     (40, [(0, 40, 64)]),                                    # everything, to the last row of the buffer
     (60, [(0, 0, 1), (1, 2, 0), (20, 22, 5)]),
+    # removals alone (the scratch chunks of the test are 1 and 4 rows, and the default, which holds everything):
+    (64, [(5, 7, 0), (30, 31, 0)]),                         # a kept prefix that does not move; shifts of 2 and 3 rows, below a chunk of 4
+    (60, [(0, 1, 0), (4, 10, 0), (40, 45, 0), (47, 50, 0)]),  # runs of 3 and 2 rows shorter than their shifts of 7 and 12: one copy each
+    (64, [(0, 40, 0)]),                                     # 24 rows move down by 40; (0, 3): 61 rows by 3, through the chunk or in pieces
+    (64, [(0, 3, 0)]),
+    (50, [(0, 2, 0), (9, 11, 0), (20, 33, 0)]),             # shifts of 2, 4 and 17 rows: below, at and above a chunk of 4
+    # appends alone
+    (64, [(64, 64, 0)]),                                    # nothing, behind a buffer without headroom: it stays
+    (63, [(63, 63, 1)]),                                    # the last row of the buffer
 ]
 
 
@@ -136,7 +145,8 @@ def test_splice_rows_in_place(shape):
 def test_splice_rows_grows_by_half(shape):
     from ibloc_amd.registration import splice_rows
     host = np.arange(int(np.prod(shape)), dtype=np.float32).reshape(shape) + 0.5
-    for n_used, b, e, k, rows_after in ((60, 10, 12, 10, 96), (64, 64, 64, 1, 96), (64, 0, 4, 100, 160)):
+    # (the second and third: appends to a buffer without headroom, by less and by more than half of it)
+    for n_used, b, e, k, rows_after in ((60, 10, 12, 10, 96), (64, 64, 64, 1, 96), (64, 64, 64, 40, 104), (64, 0, 4, 100, 160)):
         new = np.full((k,) + shape[1:], -1.0, dtype=np.float32)
         buf = torch.from_numpy(host.copy())
         out_buf, out = splice_rows(buf, n_used, [(b, e, torch.from_numpy(new))])
