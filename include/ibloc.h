@@ -70,12 +70,15 @@ int ibl_prof_read(int id, double* ms, double* units, int64_t* launches);
 typedef struct {
     int32_t dim, depth, heads, mlp_dim;
     int32_t patch, img_h, img_w;   /* model input size after preprocessing                          */
-    int32_t n_tokens;              /* 1 + (img_h/patch)*(img_w/patch); without the 1 with IBL_VIT_NO_CLS */
+    int32_t n_tokens;              /* 1 + n_registers + (img_h/patch)*(img_w/patch); the patches alone with IBL_VIT_NO_CLS */
     int32_t patch_k_pad;           /* 3*patch*patch rounded up to a multiple of 64 (zero padded)    */
     int32_t flags;                 /* IBL_VIT_*                                                     */
     int32_t n_blocks_run;          /* blocks actually executed (DATOR runs depth-1)                 */
     int32_t out_dim;               /* dim, or the projection width                                  */
     float ln_eps;
+    int32_t n_registers;           /* register tokens between the class row and the patch rows (DINOv2-reg, DINOv3: 4): a crop's rows are
+                                      [cls, reg_0 .. reg_{R-1}, patch_0 ..].  0 = none, the forward of before the field existed bit for bit.
+                                      Negative, or non-zero with IBL_VIT_NO_CLS, is refused before any launch */
 } ibl_vit_desc;
 
 typedef struct {                   /* all [dev]; weights fp16 [N][K] row-major (nn.Linear layout)   */
@@ -118,8 +121,8 @@ typedef struct {
     const void* w_patch;           /* fp16 [dim][patch_k_pad]: conv weight flattened (c, kh, kw)     */
     const float* b_patch;          /* [dim] or NULL                                                  */
     const float* cls_pos;          /* [dim]: cls_token + position_embedding[0]; not read with IBL_VIT_NO_CLS */
-    const float* pos_patch;        /* [n_tokens-1][dim] ([n_tokens][dim] with IBL_VIT_NO_CLS): position embeddings of the patch tokens,
-                                      already interpolated to the (img_h/patch, img_w/patch) grid    */
+    const float* pos_patch;        /* [P][dim], P = n_tokens - 1 - n_registers patch tokens (n_tokens with IBL_VIT_NO_CLS): their position
+                                      embeddings, already interpolated to the (img_h/patch, img_w/patch) grid.  Registers get none */
     const float* ln_pre_g; const float* ln_pre_b;
     const float* ln_f_g;   const float* ln_f_b;
     const void* w_proj;            /* fp16 [out_dim][dim] or NULL                                    */
@@ -129,6 +132,10 @@ typedef struct {
                                       projection is the last arithmetic before the output, so its fp16 roundings are not attenuated
                                       by anything downstream (4e-4 of the embedding with plain operands) and it costs nothing     */
     ibl_vit_layer layers[IBL_VIT_MAX_LAYERS];
+    const float* reg_tokens;       /* fp32 [n_registers][dim]: rows 1 .. n_registers of every crop; not read with n_registers = 0 */
+    const float* rope_table;       /* fp32 [P][64] = [cos(32) | sin(32)] per patch, 16-byte aligned, or NULL: no rotation.  With a table
+                                      every block rotates q and k of the patch rows in place between its QKV projection and its
+                                      attention (ibl_rope_f16 below; DINOv3) */
 } ibl_vit_weights;
 
 /* One crop of a preprocessing batch.  The separable resample coefficient tables are the
@@ -167,7 +174,7 @@ int ibl_preprocess_crops(const uint8_t* src, const ibl_crop_desc* descs, int n_c
 
 /* ViT forward over a batch of crops.  Replaces the batch-1 torch forward of
  * utils/embeddings.py:46,69,93 and dator/model/backbones/vit_pytorch.py:422-443.
- *   patches [dev] fp16 [batch*(n_tokens-1)][patch_k_pad] (from ibl_preprocess_crops; batch*n_tokens rows with IBL_VIT_NO_CLS)
+ *   patches [dev] fp16 [batch*P][patch_k_pad], P = n_tokens - 1 - n_registers (from ibl_preprocess_crops; P = n_tokens with IBL_VIT_NO_CLS)
  *   out     [dev] fp32 [batch][out_dim]  (CLS embedding; un-normalised, like the reference), or
  *           fp32 [batch][n_tokens][dim] with IBL_VIT_OUT_ALL_TOKENS */
 int64_t ibl_vit_workspace_bytes(const ibl_vit_desc* desc, int batch);
@@ -177,7 +184,7 @@ int64_t ibl_vit_workspace_bytes(const ibl_vit_desc* desc, int batch);
  * 0..IBL_VIT_WS_COUNT.  With Rn = batch * n_tokens rows, D = dim, and k = n_blocks_run - 1 the last block run, a forward leaves:
  *   X    fp32 [Rn][D]           the residual stream after block k (after the patch embedding / ln_pre with n_blocks_run = 0)
  *   XN   fp16 [Rn][ft * D]      block k's second LayerNorm output in ft = fc1_terms column blocks [a | a / S] or [a | a_lo * S | a / S]
- *   QKV  fp16 [Rn][3 * D]       block k's [q | k | v]
+ *   QKV  fp16 [Rn][3 * D]       block k's [q | k | v]; with a rope_table q and k of the patch rows are the ROTATED ones the attention read
  *   ATT  fp16 [Rn][ot * D]      block k's attention output in ot = o_terms column blocks
  *   HID  fp16 [Rn][f2t * mlp]   block k's hidden layer after the activation in f2t = fc2_terms column blocks
  *   FIN  fp16 [batch][D]        not written by an all-token run
@@ -260,6 +267,19 @@ int ibl_linear_f16_act(const ibl_linear_desc* desc, int activation, void* stream
  *   dim == 64 * heads, 0 <= n_tokens <= 272, terms 1..3; batch or n_tokens 0 returns IBL_OK without a launch.  Everything else is
  *   refused with a status before anything is launched.  Longer rows run through ibl_attention_stream_f16 below. */
 int ibl_attention_f16(const void* qkv, void* out, int batch, int n_tokens, int dim, int heads, int cls_only, int terms, void* stream);
+
+/* Rotary position embedding of the encoder on its own (transformers' DINOv3 apply_rotary_pos_emb: rotate_half with the table tiled
+ * twice), in place on the QKV buffer.  For every crop b, patch p (row b * n_tokens + n_prefix + p), head h, i in 0..31 and x in {q, k}:
+ *     x'[i] = x[i] cos[p][i] - x[i + 32] sin[p][i]        x'[i + 32] = x[i + 32] cos[p][i] + x[i] sin[p][i]
+ * in fp32 (one product rounded, then one fma), rounded once to fp16 and clamped to +-65504 like every other conversion here.
+ *   qkv   [dev] fp16 [batch*n_tokens][3*dim] = [q | k | v], each [heads][64]; 16-byte aligned
+ *   table [dev] fp32 [n_tokens - n_prefix][64] = [cos(32) | sin(32)] per patch; 16-byte aligned
+ *   k_only 1: the q columns are left alone (the encoder's class-rows-only last block has q of the class rows only)
+ * The n_prefix first rows of every crop, the v columns and everything past row batch * n_tokens are neither read nor written.  A crop's
+ * result does not depend on the batch it runs in.  batch 0 or n_prefix == n_tokens returns IBL_OK without a launch.  Refused with a
+ * status before any launch: dim != 64 * heads, n_prefix outside 0..n_tokens, negative sizes, k_only other than 0 / 1, null or
+ * misaligned pointers, more work than one grid holds. */
+int ibl_rope_f16(void* qkv, const float* table, int batch, int n_tokens, int n_prefix, int dim, int heads, int k_only, void* stream);
 
 /* The same product for rows of any length up to IBL_ATT_STREAM_MAX_TOKENS: keys and values pass through LDS in chunks of 128 under an fp32
  * online softmax, one workgroup per (crop, head, block of 64 queries) -- the kernel ibl_vit_forward runs where n_tokens > 272 (CLIP

@@ -51,6 +51,7 @@ _SIGS = {
     "ibl_linear_f16_act": (C.c_int, [vp, C.c_int, vp]),
     "ibl_vit_forward": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp]),
     "ibl_attention_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ibl_rope_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ibl_attention_stream_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ibl_layernorm_f32": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_float, vp, C.c_int64, C.c_int, vp]),
     "ibl_reg_ctx_create": (C.c_int, [C.POINTER(vp), C.c_int64]),

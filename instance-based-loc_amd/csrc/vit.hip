@@ -13,7 +13,7 @@
 // bias / bias+GELU / bias*layerscale+residual / patch-embed scatter+pos-embed), layernorm (one
 // wave per row), attention (one workgroup per (crop, head), K and V^T of the head staged in LDS,
 // S^T = K Q^T so that the softmaxed probabilities are already the A operand of P V), CLS/final
-// LayerNorm.
+// LayerNorm, prefix rows (class token + register tokens), rope (rotary position embedding of DINOv3, in place on q and k).
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
@@ -916,12 +916,69 @@ static int launch_layernorm(const float* x, int64_t ld_x, int64_t n_rows, int di
     return IBL_OK;
 }
 
-// x[b*T + 0][:] = cls_pos[:]   (cls token + its position embedding)
-__global__ void ibl_set_cls_kernel(float* __restrict__ x, const float* __restrict__ cls_pos, int B, int T, int dim) {
+// the prefix rows of every crop: x[b*T + 0][:] = cls_pos[:] (cls token + its position embedding), x[b*T + 1 + r][:] = reg[r][:] (register
+// tokens, no position embedding); n_prefix = 1 + registers
+__global__ void ibl_set_prefix_kernel(float* __restrict__ x, const float* __restrict__ cls_pos, const float* __restrict__ reg, int B, int T,
+                                      int n_prefix, int dim) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)B * dim) return;
-    const int b = (int)(i / dim), c = (int)(i % dim);
-    x[(int64_t)b * T * dim + c] = cls_pos[c];
+    if (i >= (int64_t)B * n_prefix * dim) return;
+    const int c = (int)(i % dim);
+    const int64_t br = i / dim;
+    const int b = (int)(br / n_prefix), r = (int)(br % n_prefix);
+    x[((int64_t)b * T + r) * dim + c] = r == 0 ? cls_pos[c] : reg[(int64_t)(r - 1) * dim + c];
+}
+
+// ------------------------------------------------------------------------------------------------
+// Rotary position embedding (DINOv3), in place on q and k of the patch rows of qkv fp16 [B*T][3*D].  table fp32 [P][64] = [cos(32) | sin(32)].
+// One lane owns the eight pairs (i, i + 32), i = 8c .. 8c + 7, of one (patch row, head) -- of q and of k, which share the table row -- so
+// the in-place update has no cross-lane hazard: two 16-byte loads and two 16-byte stores per operand, four lanes cover a head's 128 bytes.
+// Streaming: no LDS, no reuse but the table (P * 256 bytes, cache resident).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ibl_rope_kernel(u16* __restrict__ qkv, const float* __restrict__ table, unsigned n_items, int T,
+                                                       int n_prefix, int D, int heads, int x0) {
+    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= n_items) return;
+    const unsigned c = idx & 3u, rh = idx >> 2;
+    const unsigned r = rh / (unsigned)heads, h = rh - r * (unsigned)heads;       // r = b * P + p
+    const unsigned P = (unsigned)(T - n_prefix);
+    const unsigned b = r / P, p = r - b * P;
+    const float4* tc = reinterpret_cast<const float4*>(table + (int64_t)p * 64 + 8 * c);
+    const float4 c0 = tc[0], c1 = tc[1], s0 = tc[8], s1 = tc[9];
+    const float cs[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+    const float sn[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    u16* row = qkv + ((int64_t)b * T + n_prefix + p) * (3 * (int64_t)D) + h * 64 + 8 * c;
+    for (int x = x0; x < 2; ++x) {
+        uint4* plo = reinterpret_cast<uint4*>(row + (int64_t)x * D);
+        uint4* phi = reinterpret_cast<uint4*>(row + (int64_t)x * D + 32);
+        const uint4 vlo = *plo, vhi = *phi;
+        const unsigned lo[4] = {vlo.x, vlo.y, vlo.z, vlo.w}, hi[4] = {vhi.x, vhi.y, vhi.z, vhi.w};
+        unsigned olo[4], ohi[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float ra[2], rb[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const float a = h2f((u16)(lo[j] >> (16 * e))), bb = h2f((u16)(hi[j] >> (16 * e)));
+                const float cc = cs[2 * j + e], ss = sn[2 * j + e];
+                ra[e] = fmaf(a, cc, -(bb * ss));       // x[i] cos - x[i + 32] sin
+                rb[e] = fmaf(bb, cc, a * ss);          // x[i + 32] cos + x[i] sin
+            }
+            olo[j] = f2h_pk(ra[0], ra[1]);
+            ohi[j] = f2h_pk(rb[0], rb[1]);
+        }
+        *plo = make_uint4(olo[0], olo[1], olo[2], olo[3]);
+        *phi = make_uint4(ohi[0], ohi[1], ohi[2], ohi[3]);
+    }
+}
+
+// no argument checks: ibl_rope_f16 and ibl_vit_forward validate what they pass.  P >= 1, batch >= 1
+static int run_rope(u16* qkv, const float* table, int B, int T, int n_prefix, int D, int heads, int k_only, hipStream_t s) {
+    const int64_t items = (int64_t)B * (T - n_prefix) * heads * 4;
+    if (items > 0x7fffffff) return ibl_set_error(IBL_ERR_ARG, "rope: batch * patches * heads * 4 exceeds the grid");
+    hipLaunchKernelGGL(ibl_rope_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, qkv, table, (unsigned)items, T, n_prefix, D,
+                       heads, k_only ? 1 : 0);
+    IBL_LAUNCH_CHECK();
+    return IBL_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1503,6 +1560,22 @@ extern "C" int ibl_attention_f16(const void* qkv, void* out, int batch, int n_to
                          reinterpret_cast<hipStream_t>(stream), terms);
 }
 
+extern "C" int ibl_rope_f16(void* qkv, const float* table, int batch, int n_tokens, int n_prefix, int dim, int heads, int k_only,
+                            void* stream) {
+    if (batch < 0 || n_tokens < 0) return ibl_set_error(IBL_ERR_ARG, "ibl_rope_f16: negative batch (%d) or n_tokens (%d)", batch, n_tokens);
+    if (n_prefix < 0 || n_prefix > n_tokens)
+        return ibl_set_error(IBL_ERR_ARG, "ibl_rope_f16: n_prefix %d outside 0..n_tokens (%d)", n_prefix, n_tokens);
+    if (k_only != 0 && k_only != 1) return ibl_set_error(IBL_ERR_ARG, "ibl_rope_f16: k_only must be 0 or 1");
+    if (heads <= 0 || dim != heads * 64)
+        return ibl_set_error(IBL_ERR_UNSUPPORTED, "ibl_rope_f16: dim (%d) must be 64 * heads (%d): head_dim is 64", dim, heads);
+    if ((int64_t)batch * n_tokens > 0x7fffffff) return ibl_set_error(IBL_ERR_ARG, "ibl_rope_f16: batch * n_tokens out of range");
+    if (batch == 0 || n_prefix == n_tokens) return IBL_OK;
+    if (!qkv || !table) return ibl_set_error(IBL_ERR_ARG, "ibl_rope_f16: null pointer");
+    if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(table) & 15))
+        return ibl_set_error(IBL_ERR_ARG, "ibl_rope_f16: qkv and table must be 16-byte aligned");
+    return run_rope(reinterpret_cast<u16*>(qkv), table, batch, n_tokens, n_prefix, dim, heads, k_only, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int ibl_attention_stream_f16(const void* qkv, void* out, int batch, int n_tokens, int dim, int heads, int cls_only, int terms,
                                         void* stream) {
     if (batch < 0 || n_tokens < 0)
@@ -1550,7 +1623,14 @@ extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, 
     if (!d || !w || !patches || !out || !workspace) return ibl_set_error(IBL_ERR_ARG, "ibl_vit_forward: null pointer");
     if (batch <= 0) return ibl_set_error(IBL_ERR_ARG, "ibl_vit_forward: batch must be positive");
     const bool no_cls = (d->flags & IBL_VIT_NO_CLS) != 0;
-    const int D = d->dim, T = d->n_tokens, P = no_cls ? T : T - 1, H = d->heads;
+    const int D = d->dim, T = d->n_tokens, H = d->heads;
+    const int n_reg = d->n_registers, n_prefix = no_cls ? 0 : 1 + n_reg, P = T - n_prefix;
+    if (n_reg < 0 || (no_cls && n_reg != 0))
+        return ibl_set_error(IBL_ERR_ARG, "ibl_vit_forward: n_registers %d%s", n_reg, no_cls ? " with IBL_VIT_NO_CLS: registers follow a class token" : " is negative");
+    if (P < 1) return ibl_set_error(IBL_ERR_ARG, "ibl_vit_forward: n_tokens %d leaves no patch row after a prefix of %d", T, n_prefix);
+    if (n_reg > 0 && !w->reg_tokens) return ibl_set_error(IBL_ERR_ARG, "ibl_vit_forward: n_registers %d without reg_tokens", n_reg);
+    if (w->rope_table && (reinterpret_cast<uintptr_t>(w->rope_table) & 15))
+        return ibl_set_error(IBL_ERR_ARG, "ibl_vit_forward: rope_table must be 16-byte aligned");
     if (no_cls && !(d->flags & IBL_VIT_OUT_ALL_TOKENS))
         return ibl_set_error(IBL_ERR_UNSUPPORTED, "ibl_vit_forward: IBL_VIT_NO_CLS needs IBL_VIT_OUT_ALL_TOKENS: without a class token there is no row to return");
     if ((d->flags & IBL_VIT_QUICK_GELU) && (d->flags & IBL_VIT_TANH_GELU))
@@ -1584,7 +1664,7 @@ extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, 
     {
         GemmEpi e{};
         e.bias = w->b_patch; e.pos = w->pos_patch; e.out = x; e.ldo = D; e.tokens_per_crop = T; e.patches_per_crop = P;
-        e.patch_row0 = T - P;              // the prefix rows of a crop: general, so that a longer prefix (register tokens) needs no change here
+        e.patch_row0 = n_prefix;           // the patch rows follow the crop's prefix rows: class token and registers
         st = launch_gemm<EPI_PATCH_F32>(reinterpret_cast<const u16*>(patches), d->patch_k_pad,
                                         reinterpret_cast<const u16*>(w->w_patch), d->patch_k_pad, batch * P, D,
                                         d->patch_k_pad, e, s);
@@ -1598,9 +1678,9 @@ extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, 
             if (st) return st;
         }
         if (!no_cls) {
-            const int64_t n = (int64_t)batch * D;
-            hipLaunchKernelGGL(ibl_set_cls_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, w->cls_pos, batch,
-                               T, D);
+            const int64_t n = (int64_t)batch * n_prefix * D;
+            hipLaunchKernelGGL(ibl_set_prefix_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, w->cls_pos, w->reg_tokens, batch,
+                               T, n_prefix, D);
             IBL_LAUNCH_CHECK();
         }
     }
@@ -1645,6 +1725,10 @@ extern "C" int ibl_vit_forward(const ibl_vit_desc* d, const ibl_vit_weights* w, 
         const int f2t = (!cls_only && L->w_fc2_x && L->fc2_terms > 1) ? L->fc2_terms : 1;
         if (ot > at || f2t > at || ot > 3 || f2t > 3)
             return ibl_set_error(IBL_ERR_ARG, "ibl_vit_forward: layer %d: o_terms / fc2_terms %d / %d need IBL_VIT_ACT_TERMS%d in the descriptor", l, ot, f2t, ot > f2t ? ot : f2t);
+        if (w->rope_table) {      // DINOv3: q and k of the patch rows rotated in place; the class-rows-only block has no patch-row q to rotate
+            st = run_rope(qkv, w->rope_table, batch, T, n_prefix, D, H, cls_only ? 1 : 0, s);
+            if (st) return st;
+        }
         st = run_attention(qkv, att, batch, T, D, H, cls_only ? 1 : 0, s, ot);
         if (st) return st;
         {

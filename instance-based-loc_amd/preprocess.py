@@ -114,10 +114,14 @@ RECIPES = {
 RECIPES["siglip"] = PreprocessRecipe("siglip", 224, 224, "exact", 0, BICUBIC, True, (0.5, 0.5, 0.5), (0.5, 0.5, 0.5))
 
 
+# DINOv3 (transformers' DINOv3ViTImageProcessor settings through PIL): exact bilinear resize to the model size, no crop, ImageNet mean / std
+RECIPES["dinov3"] = PreprocessRecipe("dinov3", 224, 224, "exact", 0, BILINEAR, True, IMAGENET_MEAN, IMAGENET_STD)
+
+
 def recipe_for(name: str, out_h: int, out_w: int) -> PreprocessRecipe:
-    """RECIPES[name]; "siglip" (an exact resize, no crop window) follows the model's input size where that differs from the entry's"""
+    """RECIPES[name]; "siglip" and "dinov3" (an exact resize, no crop window) follow the model's input size where that differs from the entry's"""
     r = RECIPES[name]
-    if name == "siglip" and (r.out_h, r.out_w) != (out_h, out_w):
+    if name in ("siglip", "dinov3") and (r.out_h, r.out_w) != (out_h, out_w):
         r = dataclasses.replace(r, out_h=out_h, out_w=out_w)
     return r
 

@@ -3,7 +3,7 @@
 The reference loads four encoders at import time by fetching checkpoints by name
 (/root/reference/utils/embeddings.py:13-28, 101-103) and embeds ONE crop per call.  Here the encoders are
 `ibloc_amd.vit.VitEncoder` objects (HIP kernels behind the C-ABI) registered once with `set_encoder(kind, encoder)`
-or built from a converted checkpoint with `load_encoder(kind, state_dict)` (kinds "dino" | "vit" | "clip" | "dator" | "siglip"); the four reference entry points keep
+or built from a converted checkpoint with `load_encoder(kind, state_dict)` (kinds "dino" | "dinov3" | "vit" | "clip" | "dator" | "siglip"); the four reference entry points keep
 their names and `(**kwargs) -> torch.Tensor` signature:
 
     get_all_clip_embeddings   :31-50   L2-normalised 512-d
@@ -20,16 +20,25 @@ from ibloc_amd import match
 from ibloc_amd import vit as V
 
 _ENCODERS = {}
-_KIND_TO_CONFIG = {"dino": "dinov2_vitb14", "vit": "vit_b16", "clip": "clip_b32"}
+_KIND_TO_CONFIG = {"dino": "dinov2_vitb14", "dinov3": "dinov3_vitb16", "vit": "vit_b16", "clip": "clip_b32"}
 
 
 def set_encoder(kind: str, encoder: V.VitEncoder) -> None:
     _ENCODERS[kind] = encoder
 
 
+def _refuse_gated_mlp(sd: dict, what: str) -> None:
+    gated = [k for k in sd if ".mlp.gate_proj." in k or ".mlp.weights_in." in k or ".mlp.w12." in k]
+    if gated:
+        raise ValueError(f"{what}: a gated MLP ({gated[0]}; use_gated_mlp / SwiGLU checkpoints: DINOv3 ViT-S+ / H+, DINOv2-g) is not supported")
+
+
 def hf_dinov2_to_weights(sd: dict, depth: int) -> dict:
-    """transformers Dinov2Model.state_dict() (4.44 naming) -> the weight dict VitEncoder takes."""
+    """transformers Dinov2Model.state_dict() (4.44 naming) or Dinov2WithRegistersModel.state_dict() -> the weight dict VitEncoder takes.
+    Register tokens (`embeddings.register_tokens`, or `register_tokens` as the hub checkpoints name them) become "reg" (R, dim); a SwiGLU
+    checkpoint is refused."""
     g = lambda k: np.asarray(sd[k].float().cpu() if hasattr(sd[k], "float") else sd[k], dtype=np.float32)
+    _refuse_gated_mlp(sd, "hf_dinov2_to_weights")
     w = {"patch.w": g("embeddings.patch_embeddings.projection.weight"), "patch.b": g("embeddings.patch_embeddings.projection.bias"),
          "cls": g("embeddings.cls_token").reshape(-1), "pos": g("embeddings.position_embeddings")[0],
          "ln_f.g": g("layernorm.weight"), "ln_f.b": g("layernorm.bias")}
@@ -43,7 +52,45 @@ def hf_dinov2_to_weights(sd: dict, depth: int) -> dict:
         w[q + "fc1.w"], w[q + "fc1.b"] = g(p + "mlp.fc1.weight"), g(p + "mlp.fc1.bias")
         w[q + "fc2.w"], w[q + "fc2.b"] = g(p + "mlp.fc2.weight"), g(p + "mlp.fc2.bias")
         w[q + "ls1"], w[q + "ls2"] = g(p + "layer_scale1.lambda1"), g(p + "layer_scale2.lambda1")
+    for k in ("embeddings.register_tokens", "register_tokens"):
+        if k in sd and g(k).size:
+            w["reg"] = g(k).reshape(-1, w["cls"].shape[0])
     return w
+
+
+def hf_dinov3_to_weights(sd: dict, depth: int) -> dict:
+    """transformers DINOv3ViTModel.state_dict() -> the weight dict VitEncoder takes.  The separate q_proj / k_proj / v_proj become the
+    "q" / "k" / "v" entries VitEncoder packs into w_qkv; k_proj has no bias (key_bias False), so its slice of b_qkv is zeros.  There is no
+    position table (rotary embedding: the configuration's rope_theta); mask_token is ignored; a gated-MLP checkpoint is refused."""
+    g = lambda k: np.asarray(sd[k].float().cpu() if hasattr(sd[k], "float") else sd[k], dtype=np.float32)
+    _refuse_gated_mlp(sd, "hf_dinov3_to_weights")
+    w = {"patch.w": g("embeddings.patch_embeddings.weight"), "patch.b": g("embeddings.patch_embeddings.bias"),
+         "cls": g("embeddings.cls_token").reshape(-1), "ln_f.g": g("norm.weight"), "ln_f.b": g("norm.bias")}
+    D = w["cls"].shape[0]
+    if g("embeddings.register_tokens").size:
+        w["reg"] = g("embeddings.register_tokens").reshape(-1, D)
+    for l in range(depth):
+        p, q = f"model.layer.{l}.", f"l{l}."
+        w[q + "ln1.g"], w[q + "ln1.b"] = g(p + "norm1.weight"), g(p + "norm1.bias")
+        w[q + "ln2.g"], w[q + "ln2.b"] = g(p + "norm2.weight"), g(p + "norm2.bias")
+        for hf, mine in (("q_proj", "q"), ("k_proj", "k"), ("v_proj", "v"), ("o_proj", "o")):
+            w[q + mine + ".w"] = g(p + f"attention.{hf}.weight")
+            w[q + mine + ".b"] = g(p + f"attention.{hf}.bias") if p + f"attention.{hf}.bias" in sd else np.zeros(w[q + mine + ".w"].shape[0], np.float32)
+        w[q + "fc1.w"], w[q + "fc1.b"] = g(p + "mlp.up_proj.weight"), g(p + "mlp.up_proj.bias")
+        w[q + "fc2.w"], w[q + "fc2.b"] = g(p + "mlp.down_proj.weight"), g(p + "mlp.down_proj.bias")
+        w[q + "ls1"], w[q + "ls2"] = g(p + "layer_scale1.lambda1"), g(p + "layer_scale2.lambda1")
+    return w
+
+
+def check_dino_weights(w: dict, cfg: V.VitConfig) -> None:
+    """what load_encoder refuses for the DINO kinds before anything is uploaded: a head_dim other than 64, and a register count that is
+    not the configuration's"""
+    if cfg.dim != 64 * cfg.heads:
+        raise ValueError(f"{cfg.name}: head_dim {cfg.dim / cfg.heads:g} is not supported (the attention and rotation kernels run head_dim 64)")
+    have = int(np.shape(w["reg"])[0]) if "reg" in w else 0
+    if have != cfg.n_registers:
+        raise ValueError(f"the state dict holds {have} register tokens, the configuration {cfg.name} {cfg.n_registers}: pick the "
+                         "configuration of the checkpoint (dinov2_*_reg have 4, the plain DINOv2 ones none)")
 
 
 def hf_vit_to_weights(sd: dict, depth: int) -> dict:
@@ -166,6 +213,11 @@ def load_encoder(kind: str, state_dict, device="cuda", cfg: V.VitConfig = None):
     `weights_only=True`: a checkpoint is data) -> `ibloc_amd.dator.DatorEncoder` (`module.` prefix stripped, `classifier*` skipped, LoRA
     folded into the QKV weights).
 
+    "dino" also takes the register checkpoints (Dinov2WithRegistersModel) with cfg "dinov2_vits14_reg" / "dinov2_vitb14_reg" /
+    "dinov2_vitl14_reg" / "dinov2_vitb14_reg_518"; "dinov3" a transformers `DINOv3ViTModel` state dict, cfg "dinov3_vits16" /
+    "dinov3_vitb16" (default) / "dinov3_vitl16".  Gated-MLP checkpoints, head_dim != 64 and a register count that is not the
+    configuration's are refused (ValueError) before anything is uploaded.
+
     "siglip": a transformers `SiglipVisionModel` / `SiglipModel` state dict -> `ibloc_amd.siglip.SiglipEncoder` (trunk + attention-pooling
     head); cfg defaults to "siglip_b16_224", the other towers are "siglip_b16_256" / "_384" and "siglip_l16_256" / "_384"."""
     if kind == "dator":
@@ -186,8 +238,12 @@ def load_encoder(kind: str, state_dict, device="cuda", cfg: V.VitConfig = None):
         set_encoder(kind, enc)
         return enc
     cfg = cfg or V.CONFIGS[_KIND_TO_CONFIG[kind]]
-    conv = clip_converter(state_dict) if kind == "clip" else {"dino": hf_dinov2_to_weights, "vit": hf_vit_to_weights}[kind]
-    enc = V.VitEncoder(cfg, conv(state_dict, cfg.depth), device=device)
+    conv = clip_converter(state_dict) if kind == "clip" else {"dino": hf_dinov2_to_weights, "dinov3": hf_dinov3_to_weights,
+                                                              "vit": hf_vit_to_weights}[kind]
+    weights = conv(state_dict, cfg.depth)
+    if kind in ("dino", "dinov3"):
+        check_dino_weights(weights, cfg)
+    enc = V.VitEncoder(cfg, weights, device=device)
     set_encoder(kind, enc)
     return enc
 
@@ -215,6 +271,11 @@ def get_all_clip_embeddings(**kwargs) -> torch.Tensor:
 
 def get_all_dino_embeddings(**kwargs) -> torch.Tensor:
     return embed_batch("dino", [kwargs["current_obj_grounded_img"]])[0]
+
+
+def get_all_dinov3_embeddings(**kwargs) -> torch.Tensor:
+    """DINOv3 pooler_output of the crop (the class row after the final LayerNorm), un-normalised, as get_all_dino_embeddings returns it"""
+    return embed_batch("dinov3", [kwargs["current_obj_grounded_img"]])[0]
 
 
 def get_all_vit_embeddings(**kwargs) -> torch.Tensor:

@@ -4,6 +4,7 @@ preprocess + forward call.  Replaces the model objects utils/embeddings.py build
 (/root/reference/utils/embeddings.py:13-28) and the per-crop calls at :31-98.
 """
 import ctypes as C
+import dataclasses
 import math
 from dataclasses import dataclass
 
@@ -32,7 +33,7 @@ class VitDesc(C.Structure):
     _fields_ = [("dim", C.c_int32), ("depth", C.c_int32), ("heads", C.c_int32), ("mlp_dim", C.c_int32),
                 ("patch", C.c_int32), ("img_h", C.c_int32), ("img_w", C.c_int32), ("n_tokens", C.c_int32),
                 ("patch_k_pad", C.c_int32), ("flags", C.c_int32), ("n_blocks_run", C.c_int32),
-                ("out_dim", C.c_int32), ("ln_eps", C.c_float)]
+                ("out_dim", C.c_int32), ("ln_eps", C.c_float), ("n_registers", C.c_int32)]
 
 
 class VitLayer(C.Structure):
@@ -45,7 +46,8 @@ class VitLayer(C.Structure):
 
 class VitWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w_patch", "b_patch", "cls_pos", "pos_patch", "ln_pre_g", "ln_pre_b",
-                                          "ln_f_g", "ln_f_b", "w_proj", "w_patch_lo", "w_proj_x")] + [("layers", VitLayer * MAX_LAYERS)]
+                                          "ln_f_g", "ln_f_b", "w_proj", "w_patch_lo", "w_proj_x")] + [("layers", VitLayer * MAX_LAYERS)] + \
+               [("reg_tokens", C.c_void_p), ("rope_table", C.c_void_p)]
 
 
 SPLIT_SCALE = 64.0          # IBL_VIT_SPLIT_SCALE (include/ibloc.h)
@@ -69,7 +71,16 @@ MODEL_PRECISION = {"clip_b32": "p2;*:2222;0:3232",
                    # under the default (6.6e-4 / 7.7e-4): no entry.  L/14's 24 blocks spread the error over more of the depth (default 8.9e-4 / 1.04e-3):
                    # two-term weights in blocks 0-3 give 8.1e-4 / 9.2e-4 for 49.8 instead of 46.5 ms
                    "clip_b32_openai": "p2;0:3232;1:2222;2:2211",
-                   "clip_l14_openai": "p2;0:3232;1:2222;2:2222;3:2222;4:2211"}
+                   "clip_l14_openai": "p2;0:3232;1:2222;2:2222;3:2222;4:2211",
+                   # the register / rotary models on 224 u8 crops (32 at 518 px), mean / max (DESIGN (c) has the whole ladder).  The S and B register
+                   # models and dinov3_vits16 meet the gate under the default (5.7e-4 / 7.1e-4, 6.7e-4 / 7.7e-4, 6.0e-4 / 6.4e-4 at 518 px, 5.4e-4 /
+                   # 6.3e-4): no entry.  dinov3_vitb16 misses it there (7.9e-4 / 1.02e-3: the rotation rounds q and k to fp16 a second time);
+                   # two-term weights in blocks 0-6 give 7.1e-4 / 9.3e-4 for 17.0 instead of 13.8 ms per 224 crops.  dinov2_vitl14_reg (default
+                   # 9.9e-4 / 1.23e-3) passes under the last plan of the ladder only: 6.0e-4 / 7.5e-4, but 110 instead of 48 ms -- pass
+                   # precision="default" where the time matters more.  dinov3_vitl16 meets it under no plan (p2;*:3333: 1.21e-3 / 1.83e-3) and
+                   # runs the default
+                   "dinov3_vitb16": "p2;0:3232;1:2222;2:2222;3:2222;4:2222;5:2222;6:2211",
+                   "dinov2_vitl14_reg": "p2;*:3333"}
 
 
 def parse_precision(spec):
@@ -129,10 +140,12 @@ class VitConfig:
     n_blocks_run: int = -1
     out_all_tokens: bool = False
     recipe: str = "dinov2"
-    pos_interp: str = "hf-4.44"    # how stored position embeddings are resampled to the run grid
+    pos_interp: str = "hf-4.44"    # how stored position embeddings are resampled to the run grid ("hf-4.44" | "size" | "size-aa")
     quick_gelu: bool = False       # fc1 activation x * sigmoid(1.702 x) (OpenAI CLIP) instead of erf GELU: IBL_VIT_QUICK_GELU
     cls_token: bool = True         # False (SigLIP): no class token, `pos` is (gh * gw, D) and used as stored: IBL_VIT_NO_CLS
     tanh_gelu: bool = False        # fc1 activation 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) (SigLIP): IBL_VIT_TANH_GELU
+    n_registers: int = 0           # register tokens between the class token and the patches (DINOv2-reg, DINOv3): ibl_vit_desc.n_registers
+    rope_theta: float | None = None    # DINOv3: rotary position embedding of this base on q / k of the patch rows; no position table
 
     @property
     def grid(self):
@@ -140,7 +153,11 @@ class VitConfig:
 
     @property
     def n_tokens(self):
-        return int(self.cls_token) + self.grid[0] * self.grid[1]
+        return int(self.cls_token) + self.n_registers + self.grid[0] * self.grid[1]
+
+    @property
+    def n_prefix(self):
+        return int(self.cls_token) + self.n_registers
 
     @property
     def n_patches(self):
@@ -218,6 +235,36 @@ CONFIGS.update({
 })
 
 
+def _dino_reg(name, dim, heads, depth, px, recipe="dinov2"):
+    """DINOv2 with registers (dinov2_vit{s,b,l}14_reg, facebook/dinov2-with-registers-*): the DINOv2 trunk with four register rows after
+    the class row; transformers resamples its 37 x 37 position table with antialiasing ("size-aa")"""
+    return VitConfig(name, dim, depth, heads, 4 * dim, 14, px, px, (37, 37), layerscale=True, recipe=recipe, pos_interp="size-aa",
+                     n_registers=4)
+
+
+def _dinov3(name, dim, heads, depth, px=224):
+    """DINOv3 ViT-S / B / L at patch 16 (facebook/dinov3-vit*16-pretrain-*): four registers, rotary position embedding (theta 100) on q / k
+    of the patch rows in place of a position table, LayerScale, eps 1e-5.  The gated-MLP variants (S+, H+) are not supported"""
+    return VitConfig(name, dim, depth, heads, 4 * dim, 16, px, px, (px // 16, px // 16), layerscale=True, ln_eps=1e-5, recipe="dinov3",
+                     n_registers=4, rope_theta=100.0)
+
+
+CONFIGS.update({
+    # 261 tokens: the resident attention kernel's widest tier (272); 1 374 at 518 px: the streaming one, the table as stored
+    "dinov2_vits14_reg": _dino_reg("dinov2_vits14_reg", 384, 6, 12, 224),
+    "dinov2_vitb14_reg": _dino_reg("dinov2_vitb14_reg", 768, 12, 12, 224),
+    "dinov2_vitl14_reg": _dino_reg("dinov2_vitl14_reg", 1024, 16, 24, 224),
+    "dinov2_vitb14_reg_518": _dino_reg("dinov2_vitb14_reg_518", 768, 12, 12, 518, recipe="dinov2_518"),
+    "dinov3_vits16": _dinov3("dinov3_vits16", 384, 6, 12),            # 201 tokens
+    "dinov3_vitb16": _dinov3("dinov3_vitb16", 768, 12, 12),
+    "dinov3_vitl16": _dinov3("dinov3_vitl16", 1024, 16, 24),
+    "tiny_dino_reg": dataclasses.replace(_dino_reg("tiny_dino_reg", 128, 2, 2, 224), mlp_dim=256),
+    "tiny_dino_reg_518": dataclasses.replace(_dino_reg("tiny_dino_reg_518", 128, 2, 2, 518, recipe="dinov2_518"), mlp_dim=256),
+    "tiny_dinov3": dataclasses.replace(_dinov3("tiny_dinov3", 128, 2, 2), mlp_dim=256),
+    "tiny_dinov3_384": dataclasses.replace(_dinov3("tiny_dinov3_384", 128, 2, 2, px=384), mlp_dim=256),      # 581 tokens: rotation in front of the streaming attention
+})
+
+
 def random_weights(cfg: VitConfig, seed: int):
     """Seeded synthetic weights (no pretrained checkpoints exist offline): trunc-normal-ish N(0, 0.02)
     matrices, LayerNorm gains around 1, LayerScale around 1 -- numpy fp32, keyed like the oracle expects."""
@@ -234,6 +281,11 @@ def random_weights(cfg: VitConfig, seed: int):
         "ln_f.g": (1 + mat(cfg.dim, std=0.1)),
         "ln_f.b": mat(cfg.dim, std=0.1),
     }
+    if cfg.rope_theta is not None:
+        del w["pos"]                   # rotary models hold no position table
+    if cfg.n_registers:
+        # non-zero (transformers initialises DINOv2's registers to zero, which would hide a missing prefix row)
+        w["reg"] = mat(cfg.n_registers, cfg.dim)
     if cfg.pre_ln:
         w["ln_pre.g"] = 1 + mat(cfg.dim, std=0.1)
         w["ln_pre.b"] = mat(cfg.dim, std=0.1)
@@ -264,7 +316,9 @@ def interpolate_pos_embed(pos: np.ndarray, cfg: VitConfig) -> np.ndarray:
 
     "hf-4.44": transformers 4.44.0 Dinov2Embeddings.interpolate_pos_encoding (the version the reference
     pins, environment.yml:275): bicubic, align_corners=False, scale_factor = (grid + 0.1) / stored_grid.
-    "size": torch's size= form (transformers >= 4.46)."""
+    "size": torch's size= form (transformers >= 4.46).
+    "size-aa": the size= form with antialias=True, as Dinov2WithRegistersEmbeddings.interpolate_pos_encoding resamples (37 x 37 ->
+    16 x 16 at 224 px is a down-scale, so the antialiasing filter changes every row)."""
     gh, gw = cfg.pos_grid
     th, tw = cfg.grid
     if (gh, gw) == (th, tw):
@@ -276,10 +330,25 @@ def interpolate_pos_embed(pos: np.ndarray, cfg: VitConfig) -> np.ndarray:
         t = torch.nn.functional.interpolate(t, scale_factor=sf, mode="bicubic", align_corners=False)
         if tuple(t.shape[-2:]) != (th, tw):
             raise ValueError("pos-embed interpolation produced an unexpected grid")
+    elif cfg.pos_interp in ("size", "size-aa"):
+        t = torch.nn.functional.interpolate(t, size=(th, tw), mode="bicubic", align_corners=False, antialias=cfg.pos_interp == "size-aa")
     else:
-        t = torch.nn.functional.interpolate(t, size=(th, tw), mode="bicubic", align_corners=False)
+        raise ValueError(f"unknown pos_interp {cfg.pos_interp!r}")
     patch_new = t.permute(0, 2, 3, 1).reshape(th * tw, -1).numpy()
     return np.concatenate([cls_pos, patch_new], axis=0).astype(np.float32)
+
+
+def rope_table(grid_h: int, grid_w: int, theta: float) -> np.ndarray:
+    """-> fp32 (grid_h * grid_w, 64) = [cos(32) | sin(32)] per patch: transformers' DINOv3ViTRopePositionEmbedding in eval mode (no
+    shift / jitter / rescale) at head_dim 64, in its order of fp32 operations.  Patch-centre coordinates in [-1, 1], inv_freq =
+    theta^-(4 j / 64), j = 0..15, angles 2 pi coord inv_freq -- the 16 of y, then the 16 of x; the model tiles these 32 twice, which is
+    what `ibl_rope_kernel` does by pairing column i with i + 32."""
+    inv_freq = 1 / theta ** torch.arange(0, 1, 4 / 64, dtype=torch.float32)
+    ch = torch.arange(0.5, grid_h, dtype=torch.float32) / grid_h
+    cw = torch.arange(0.5, grid_w, dtype=torch.float32) / grid_w
+    coords = 2.0 * torch.stack(torch.meshgrid(ch, cw, indexing="ij"), dim=-1).flatten(0, 1) - 1.0
+    angles = (2 * math.pi * coords[:, :, None] * inv_freq[None, None, :]).flatten(1, 2)
+    return torch.cat([torch.cos(angles), torch.sin(angles)], dim=1).numpy().astype(np.float32)
 
 
 class PackedCrops:
@@ -337,7 +406,21 @@ class VitEncoder:
 
         if cfg.quick_gelu and cfg.tanh_gelu:
             raise ValueError("quick_gelu and tanh_gelu are both set")
-        if cfg.cls_token:
+        if cfg.dim != 64 * cfg.heads:
+            raise ValueError(f"head_dim {cfg.dim / cfg.heads:g} is not supported: the attention and rotation kernels run head_dim 64")
+        if cfg.n_registers and not cfg.cls_token:
+            raise ValueError("n_registers needs cls_token: registers follow the class row")
+        if cfg.n_registers and tuple(np.shape(weights.get("reg", ()))) != (cfg.n_registers, cfg.dim):
+            raise ValueError(f"the weights hold registers of shape {np.shape(weights.get('reg', ()))}, the configuration {cfg.name} "
+                             f"needs ({cfg.n_registers}, {cfg.dim})")
+        if not cfg.n_registers and np.size(weights.get("reg", ())):
+            raise ValueError(f"the weights hold {np.shape(weights['reg'])[0]} register tokens, the configuration {cfg.name} none")
+        if cfg.rope_theta is not None:
+            # rotary models: no position table.  The patch scatter still adds a row per patch, so it is handed zeros
+            if "pos" in weights:
+                raise ValueError("rope_theta and a position table are both given")
+            pos = np.zeros((int(cfg.cls_token) + cfg.n_patches, cfg.dim), dtype=np.float32)
+        elif cfg.cls_token:
             pos = interpolate_pos_embed(weights["pos"], cfg)
         else:
             # no class token: the table is (gh * gw, D) and used as stored (resampling it is not supported)
@@ -358,6 +441,10 @@ class VitEncoder:
             W.pos_patch = dev_f32(pos[1:])
         else:
             W.pos_patch = dev_f32(pos)
+        if cfg.n_registers:
+            W.reg_tokens = dev_f32(weights["reg"])
+        if cfg.rope_theta is not None:
+            W.rope_table = dev_f32(rope_table(cfg.grid[0], cfg.grid[1], cfg.rope_theta))
         if cfg.pre_ln:
             W.ln_pre_g, W.ln_pre_b = dev_f32(weights["ln_pre.g"]), dev_f32(weights["ln_pre.b"])
         if cfg.final_ln:
@@ -427,7 +514,7 @@ class VitEncoder:
         flags |= {1: 0, 2: FLAG_ACT_TERMS2, 3: FLAG_ACT_TERMS3}[getattr(self, "_act_terms", 1)]
         nrun = cfg.depth if cfg.n_blocks_run < 0 else cfg.n_blocks_run
         self.desc = VitDesc(cfg.dim, cfg.depth, cfg.heads, cfg.mlp_dim, cfg.patch, cfg.img_h, cfg.img_w, cfg.n_tokens,
-                            cfg.patch_k_pad, flags, nrun, cfg.out_dim, cfg.ln_eps)
+                            cfg.patch_k_pad, flags, nrun, cfg.out_dim, cfg.ln_eps, cfg.n_registers)
         self.recipe = pp.recipe_for(cfg.recipe, cfg.img_h, cfg.img_w)
         self._ws = None
         self._plan_cache = {}
@@ -671,6 +758,18 @@ def attention_stream_f16(qkv: torch.Tensor, heads: int, cls_only: bool = False, 
                                             torch.cuda.current_stream().cuda_stream)
     _lib.check(st, "ibl_attention_stream_f16")
     return out
+
+
+def rope_f16(qkv: torch.Tensor, table: torch.Tensor, heads: int, n_prefix: int, k_only: bool = False) -> torch.Tensor:
+    """Rotary position embedding in place on q and k of the patch rows of qkv (batch, n_tokens, 3 * dim) fp16 through `ibl_rope_f16` (the
+    encoder's kernel on its own); table (n_tokens - n_prefix, 64) fp32 = [cos | sin] (`rope_table`).  The first n_prefix rows of a crop
+    and the v columns stay; k_only leaves q alone too.  What the kernel cannot run is refused by the library: IblError."""
+    assert qkv.dtype == torch.float16 and qkv.is_cuda and qkv.dim() == 3 and qkv.is_contiguous() and qkv.shape[2] % 3 == 0
+    assert table.dtype == torch.float32 and table.is_cuda and table.is_contiguous() and table.shape == (qkv.shape[1] - n_prefix, 64)
+    st = _lib.lib.ibl_rope_f16(qkv.data_ptr(), table.data_ptr(), qkv.shape[0], qkv.shape[1], int(n_prefix), qkv.shape[2] // 3, heads,
+                               int(k_only), torch.cuda.current_stream().cuda_stream)
+    _lib.check(st, "ibl_rope_f16")
+    return qkv
 
 
 LN_F32, LN_F16, LN_F16_X2, LN_F16_X3 = 0, 1, 2, 3
