@@ -111,7 +111,9 @@ typedef struct {                   /* all [dev]; weights fp16 [N][K] row-major (
     /* round 4: the two residual GEMMs with K-extended operands as well -- ONE launch of K' = terms * K instead of one read-modify-write pass
      * over the residual per term: the attention kernel / the fc1 epilogue write the rows [a_hi | a_hi / S] (terms 2) or
      * [a_hi | a_lo * S | a_hi / S] (terms 3: + the second fp16 term of the attention output / of the GELU hidden layer); w_o_x / w_fc2_x are laid
-     * out like w_qkv_x.  Needs IBL_VIT_ACT_TERMS2 / 3 in the descriptor's flags.  With w_o_x / w_fc2_x NULL the older w_o_lo / w_fc2_lo launches run. */
+     * out like w_qkv_x.  Needs IBL_VIT_ACT_TERMS2 / 3 in the descriptor's flags.  With w_o_x / w_fc2_x NULL the older w_o_lo / w_fc2_lo launches run.
+     * The terms of every block to run are checked before the first launch: a count above 3, or o_terms / fc2_terms above what the flags allow,
+     * in ANY layer is refused (IBL_ERR_ARG) with the workspace and `out` untouched. */
     int32_t o_terms, fc2_terms;
     const void* w_o_x;                           /* fp16 [dim][o_terms*dim] or NULL                     */
     const void* w_fc2_x;                         /* fp16 [dim][fc2_terms*mlp_dim] or NULL               */

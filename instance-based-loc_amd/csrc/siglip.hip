@@ -173,7 +173,7 @@ static int probe_pool_check(const char* fn, int batch, int n_tokens, int dim, in
 
 static int launch_probe_pool(const float* x, int batch, int n_tokens, int dim, int heads, const float* u, float* pooled, float* probs,
                              hipStream_t s) {
-    // the dynamic-LDS limit is a per-device property of the function: set once per device of this process (see launch_gemm_cfg, vit.hip)
+    // the dynamic-LDS limit is a per-device property of the function: set once per device of this process (see launch_gemm_cfg, vit_gemm.hip)
     static std::atomic<unsigned long long> attr_set{0};
     int dev = 0;
     IBL_HIP_CHECK(hipGetDevice(&dev));

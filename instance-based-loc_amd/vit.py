@@ -460,7 +460,7 @@ class VitEncoder:
             L.w_qkv = dev_f16(np.concatenate([weights[p + "q.w"], weights[p + "k.w"], weights[p + "v.w"]], axis=0))
             L.b_qkv = dev_f32(np.concatenate([weights[p + "q.b"], weights[p + "k.b"], weights[p + "v.b"]], axis=0))
             # fold_layerscale (lab, off by default): x += ls * (a W^T + b) = a (diag(ls) W)^T + ls * b.  Without a scale vector in the
-            # epilogue the library can preload the residual tile into the accumulators (EPI_RESID_PRE_F32, csrc/vit.hip).
+            # epilogue the library can preload the residual tile into the accumulators (EPI_RESID_PRE_F32, csrc/vit_gemm.hip).
             w_o, b_o, w_fc2, b_fc2 = weights[p + "o.w"], weights[p + "o.b"], weights[p + "fc2.w"], weights[p + "fc2.b"]
             fold = self.fold_layerscale              # (without LayerScale: "folded" = no 1 / S vectors for the second terms either)
             if fold and cfg.layerscale:

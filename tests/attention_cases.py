@@ -1,4 +1,4 @@
-"""Inputs, fp64 reference, error bound and a CPU emulation of the arithmetic of `ibl_attention_kernel` (csrc/vit.hip), shared by
+"""Inputs, fp64 reference, error bound and a CPU emulation of the arithmetic of `ibl_attention_kernel` (csrc/vit_attention.hip), shared by
 tests/test_attention_model.py (CPU: the bound is reachable) and tests/test_gpu_attention.py (GPU: the kernel meets it).
 
 Arrays are (batch, heads, n_tokens, 64); `pack` lays them out as the kernel's qkv rows [q | k | v], each [heads][64]."""

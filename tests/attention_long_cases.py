@@ -1,4 +1,4 @@
-"""Case table of the streaming attention kernel `ibl_attention_stream_kernel` (csrc/vit.hip): the input families, fp64 reference and
+"""Case table of the streaming attention kernel `ibl_attention_stream_kernel` (csrc/vit_attention.hip): the input families, fp64 reference and
 error bound of tests/attention_cases.py at token counts beyond the resident kernel's 272, two families that force the online softmax
 to rescale at every key chunk, and a CPU emulation of the kernel's arithmetic.  Shared by tests/test_attention_long_model.py (CPU:
 the bound is reachable) and tests/test_gpu_attention_long.py (GPU: the kernel meets it)."""

@@ -1,7 +1,7 @@
 """QuickGELU (OpenAI CLIP: v * sigmoid(1.702 v)) -- what the tests of the QuickGELU epilogue of `ibl_gemm_f16_tn` and of the OpenAI CLIP
 configurations share:
 
-  * `emulate_qgelu`: `quick_gelu2` (csrc/vit.hip) in numpy fp32, operation for operation, and the fp64 reference `qgelu64`;
+  * `emulate_qgelu`: `quick_gelu2` (csrc/vit_gemm.hip) in numpy fp32, operation for operation, and the fp64 reference `qgelu64`;
   * the per-element bound of IBL_LINEAR_GELU_F16 / _X2 / _X3 with IBL_ACT_QUICK_GELU.  It is the bound of tests/gemm_cases.py with two
     constants exchanged:  LIP_Q e1 + C_QGELU max(|v|, TINY) + 2^-11 |ref| + 2^-25  (e1, TINY, SLACK: gemm_cases).
       LIP_Q = 1.10 >= max |q'| = 1.0998 (at v = 1.44) carries the accumulation error through the activation.
@@ -34,7 +34,7 @@ def qgelu64(v):
 
 
 def emulate_qgelu(v):
-    """quick_gelu2 (csrc/vit.hip) in numpy fp32, operation for operation; v fp32 -> value fp32"""
+    """quick_gelu2 (csrc/vit_gemm.hip) in numpy fp32, operation for operation; v fp32 -> value fp32"""
     f = np.float32
     v = np.asarray(v, f)
     with np.errstate(over="ignore"):

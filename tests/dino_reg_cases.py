@@ -1,7 +1,7 @@
 """DINOv2 with registers and DINOv3 (register tokens, rotary position embedding) -- what the tests of `ibl_rope_kernel`, of the prefix rows and
 of the new configurations share:
 
-  * `rope64` / `emulate_rope` / `rope_bound`: the rotation of `ibl_rope_kernel` (csrc/vit.hip) in float64, in numpy fp32 operation for
+  * `rope64` / `emulate_rope` / `rope_bound`: the rotation of `ibl_rope_kernel` (csrc/vit_attention.hip) in float64, in numpy fp32 operation for
     operation (one rounded product, then one fma, then f2h_pk's round-to-nearest-even and clamp), and its per-element bound
         2^-11 |ref| + 2^-22 (|a cos| + |b sin|) + 2^-25
     -- one fp16 rounding of the result, three fp32 roundings of the two terms (the kernel spends two: the product and the fma) and the

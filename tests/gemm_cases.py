@@ -1,4 +1,4 @@
-"""Inputs, fp64 reference, per-element error bounds and a CPU emulation of `gelu_erf2` for `ibl_gemm_f16_tn` (csrc/vit.hip), shared by
+"""Inputs, fp64 reference, per-element error bounds and a CPU emulation of `gelu_erf2` for `ibl_gemm_f16_tn` (csrc/vit_gemm.hip), shared by
 tests/test_gemm_model.py (CPU: the families are what they claim, C_GELU is chosen by rule) and tests/test_gpu_gemm.py (GPU: every element of
 every epilogue on both tile shapes meets the bound).
 
@@ -195,7 +195,7 @@ def _fma(a, b, c):
 
 
 def emulate_gelu(v):
-    """gelu_erf2 (csrc/vit.hip) in numpy fp32, operation for operation; v fp32 -> value fp32"""
+    """gelu_erf2 (csrc/vit_gemm.hip) in numpy fp32, operation for operation; v fp32 -> value fp32"""
     f = np.float32
     v = np.asarray(v, f)
     c = f(0.70710678118654752)

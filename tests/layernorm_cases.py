@@ -1,4 +1,4 @@
-"""Inputs, fp64 reference, error bound and a CPU emulation of the arithmetic of `ibl_layernorm_kernel` (csrc/vit.hip), shared by
+"""Inputs, fp64 reference, error bound and a CPU emulation of the arithmetic of `ibl_layernorm_kernel` (csrc/vit_layernorm.hip), shared by
 tests/test_layernorm_model.py (CPU: the bound is reachable) and tests/test_gpu_layernorm.py (GPU: the kernel meets it)."""
 import numpy as np
 

@@ -1,7 +1,7 @@
 """SigLIP (tanh GELU, no class token, attention-pooling head) -- what the tests of the tanh-GELU epilogue of `ibl_gemm_f16_tn`, of the pooling
 head (csrc/siglip.hip) and of the SigLIP configurations share:
 
-  * `emulate_tgelu`: `tanh_gelu2` (csrc/vit.hip) in numpy fp32, operation for operation, and the fp64 reference `tgelu64`;
+  * `emulate_tgelu`: `tanh_gelu2` (csrc/vit_gemm.hip) in numpy fp32, operation for operation, and the fp64 reference `tgelu64`;
   * the per-element bound of IBL_LINEAR_GELU_F16 / _X2 / _X3 with IBL_ACT_GELU_TANH (through ibl_linear_f16_act).  It is the bound of
     tests/gemm_cases.py with two constants exchanged:  LIP_T e1 + C_TGELU max(|v|, TINY) + 2^-11 |ref| + 2^-25  (e1, TINY, SLACK: gemm_cases).
       LIP_T = 1.13 >= max |g'| = 1.12899 (at v = 1.42) carries the accumulation error through the activation.
@@ -39,7 +39,7 @@ def tgelu64(v):
 
 
 def emulate_tgelu(v):
-    """tanh_gelu2 (csrc/vit.hip) in numpy fp32, operation for operation (the fma is the one -ffp-contract fuses); v fp32 -> value fp32"""
+    """tanh_gelu2 (csrc/vit_gemm.hip) in numpy fp32, operation for operation (the fma is the one -ffp-contract fuses); v fp32 -> value fp32"""
     f = np.float32
     v = np.asarray(v, f)
     with np.errstate(over="ignore", invalid="ignore"):

@@ -1,4 +1,4 @@
-"""-m gpu: `ibl_rope_f16` (ibl_rope_kernel, csrc/vit.hip) on its own -- every element inside the bound of tests/dino_reg_cases.py against the
+"""-m gpu: `ibl_rope_f16` (ibl_rope_kernel, csrc/vit_attention.hip) on its own -- every element inside the bound of tests/dino_reg_cases.py against the
 fp64 rotation of the same fp16 inputs and fp32 table, everything the kernel must leave alone bit for bit (prefix rows, v columns, a
 NaN-filled guard after the last row, q under k_only), the same bytes from two calls and for a crop alone or inside a batch, and every
 refusal without a launch."""

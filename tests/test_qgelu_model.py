@@ -1,5 +1,5 @@
 """CPU: what tests/test_gpu_qgelu.py rests on -- C_QGELU and LIP_Q of tests/clip_openai_cases.py are what their rules give, the emulated
-`quick_gelu2` behaves at the extremes as csrc/vit.hip says, and `ibl_linear_f16_ex` refuses a bad `activation` before it touches the
+`quick_gelu2` behaves at the extremes as csrc/vit_gemm.hip says, and `ibl_linear_f16_ex` refuses a bad `activation` before it touches the
 device."""
 import ctypes as C
 import math

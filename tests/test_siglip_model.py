@@ -1,5 +1,5 @@
 """CPU: what the SigLIP GPU tests rest on -- C_TGELU and LIP_T of tests/siglip_cases.py are what their rules give, the emulated `tanh_gelu2`
-behaves at the extremes as csrc/vit.hip says, the erf form breaks the tanh bound, the folded pooling head is the unfolded one, the seeded
+behaves at the extremes as csrc/vit_gemm.hip says, the erf form breaks the tanh bound, the folded pooling head is the unfolded one, the seeded
 head pools non-uniformly, the configurations are the checkpoints', and the new entries refuse bad arguments before they touch the device."""
 import ctypes as C
 import math
