@@ -19,7 +19,7 @@
 #include "reg_common.h"
 
 // Cells per search radius of the hybrid k-NN grids: the max_nn nearest neighbours of a dense cloud sit in a small fraction of the
-// radius, and hybrid_select (reg_knn.hip) only walks the cube of cells that provably holds them.  (Per-segment cell sizes never drop
+// radius, and hybrid_select (knn_select.h) only walks the cube of cells that provably holds them.  (Per-segment cell sizes never drop
 // below extent / 128, reg_grid.hip.)
 #ifndef KNN_CELLS_NORMAL
 #define KNN_CELLS_NORMAL 3.0        // r = 2 voxel, 30 neighbours
@@ -27,28 +27,6 @@
 #ifndef KNN_CELLS_FEATURE
 #define KNN_CELLS_FEATURE 5.0       // r = 5 voxel, 100 neighbours
 #endif
-
-#ifndef KNN_TILE_NORMAL
-#define KNN_TILE_NORMAL 4           // tile edge in cells of the 30-neighbour searches (normals, colour gradients)
-#endif
-#ifndef KNN_TILE_FEATURE
-#define KNN_TILE_FEATURE 2          // ... of the 100-neighbour SPFH search
-#endif
-
-int ibl_launch_normals(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* pts, const int* seg_off, int n, double radius, int max_nn, float4* normals,
-                       int* status, hipStream_t s);
-int ibl_launch_fpfh(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* pts, const float4* normals, const int* seg_off, int n, double radius, int max_nn,
-                    unsigned char* spfh, int* nbr_idx, float* nbr_d2, int* nbr_cnt, float* fpfh, int matching_order, int* status,
-                    hipStream_t s);
-int ibl_launch_radius_count(const BatchGrid& g, const float4* pts, const int* seg_off, int n, double radius, int nb_points,
-                            unsigned char* keep, hipStream_t s);
-
-bool ibl_normals_fpfh_fusable(const ibl_reg_ctx* ctx, double radius_normal, int max_nn_normal, double radius_feature, int max_nn_feature);
-int ibl_launch_normals_fpfh(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* pts, const int* seg_off, int n, double radius_normal,
-                            int max_nn_normal, double radius_feature, int max_nn_feature, float4* normals, unsigned char* spfh, int* nbr_idx,
-                            float* nbr_d2, int* nbr_cnt, float* fpfh, int matching_order, int* status, hipStream_t s);
-int ibl_launch_color_grad(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* pts, const float4* normals, const int* seg_off, int q0, int q1, double radius,
-                          int max_nn, float4* grad, int* status, hipStream_t s);
 
 // bounding boxes of the segments on the host (synchronises the stream)
 static int ibl_bbox_to_host(ibl_reg_ctx* ctx, const float4* P, const int* seg_off_dev, int n_seg, float* bbox_host, hipStream_t s) {

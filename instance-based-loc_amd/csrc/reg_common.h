@@ -22,7 +22,7 @@ struct BatchGrid {
     const float4* sorted_pts;  // [N] (x, y, z, intensity) in cell order
     const int* order;          // [N] sorted position -> original point index (batch-global)
     int n_seg;
-    // tiles (ibl_build_tile_grid only): cubes of ts^3 cells, one workgroup each in the LDS-staged k-NN kernels (reg_knn.hip)
+    // tiles (ibl_build_tile_grid only): cubes of ts^3 cells, one workgroup each in the LDS-staged k-NN kernels (knn_select.h)
     const int* tile_base;      // [S + 1] first tile of every segment, or null
     const int* tile_seg;       // [n_tiles] segment of every tile (a lookup instead of a binary search over tile_base), or null
     int n_tiles;
@@ -131,6 +131,25 @@ int ibl_build_tile_grid(ibl_reg_ctx* ctx, const float4* pts, const int* seg_off_
 
 // per-segment axis-aligned bounding boxes [S][6] = (min xyz, max xyz); empty segments read as zeros
 int ibl_launch_bbox(const float4* pts, const int* seg_off_dev, int n_seg, float* bbox_dev, hipStream_t s);
+
+// neighbourhood consumers on a tile grid (reg_normals.hip, reg_fpfh.hip, reg_colorgrad.hip) and radius counts on a batch grid (reg_radius.hip).
+// Tile edge in cells of the grid a search is handed: the `ts` its caller gives ibl_build_tile_grid AND the one tile kernel the consumer's
+// factory instantiates read it here, so the two cannot disagree (launch_knn, knn_select.h, refuses a grid of another edge).
+constexpr int KNN_TILE_NORMAL = 4;           // the 30-neighbour searches: ibl_launch_normals, ibl_launch_color_grad
+constexpr int KNN_TILE_FEATURE = 2;          // the 100-neighbour searches: ibl_launch_fpfh, ibl_launch_normals_fpfh
+int ibl_launch_normals(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* pts, const int* seg_off, int n, double radius, int max_nn, float4* normals,
+                       int* status, hipStream_t s);
+int ibl_launch_fpfh(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* pts, const float4* normals, const int* seg_off, int n, double radius, int max_nn,
+                    unsigned char* spfh, int* nbr_idx, float* nbr_d2, int* nbr_cnt, float* fpfh, int matching_order, int* status,
+                    hipStream_t s);
+bool ibl_normals_fpfh_fusable(const ibl_reg_ctx* ctx, double radius_normal, int max_nn_normal, double radius_feature, int max_nn_feature);
+int ibl_launch_normals_fpfh(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* pts, const int* seg_off, int n, double radius_normal,
+                            int max_nn_normal, double radius_feature, int max_nn_feature, float4* normals, unsigned char* spfh, int* nbr_idx,
+                            float* nbr_d2, int* nbr_cnt, float* fpfh, int matching_order, int* status, hipStream_t s);
+int ibl_launch_color_grad(ibl_reg_ctx* ctx, const BatchGrid& g, const float4* pts, const float4* normals, const int* seg_off, int q0, int q1, double radius,
+                          int max_nn, float4* grad, int* status, hipStream_t s);
+int ibl_launch_radius_count(const BatchGrid& g, const float4* pts, const int* seg_off, int n, double radius, int nb_points,
+                            unsigned char* keep, hipStream_t s);
 
 // feature arrays the registration driver reads in place: [0] detected-pool instance features, [1] memory-pool instance
 // features, [2] groups recomputed in the context of their job

@@ -254,10 +254,10 @@ __global__ __launch_bounds__(256) void ibl_tile_seg_kernel(const int* __restrict
 
 // The defaults of diag.knn_safety / diag.knn_rho come from sweeps on the detections of a bench step (tools/lab_knn_grid.sh, 1.04 M
 // points in 210 clouds, ms per feature call; the results do not depend on the knobs -- a tile proves its queries or hands them to the grid walk).  With the 100-neighbour search
-// on 1 600-candidate packed tiles, three workgroups per CU (reg_knn.hip):
+// on 1 600-candidate packed tiles, three workgroups per CU (SpfhFactory / ListNormalFactory, reg_fpfh.hip):
 //   rho 2: safety 0.6 7.64 | 0.7 7.41 | 0.8 7.44 | 1.0 7.80 (9.7 % of the queries overflow their cube)
 //   rho 3: safety 0.7 7.89 | 0.8 7.33 | 0.9 7.16 | 1.0 7.14 | 1.1 7.02 | 1.25 7.06 | 1.5 7.30      rho 4: 1.25 7.43
-// (on the 2 560-candidate tiles, two workgroups per CU, the best was rho 2 / 0.8: 8.53 against 9.05 at 3 / 1.0.)
+// (on the 2 560-candidate unpacked tiles these searches had before, two workgroups per CU, the best was rho 2 / 0.8: 8.53 against 9.05 at 3 / 1.0.)
 int ibl_build_tile_grid(ibl_reg_ctx* ctx, const float4* pts, const int* seg_off_dev, const int* seg_off_host, int n_seg,
                         const float* bbox_host, double radius, int max_nn, int ts, int64_t max_cells, BatchGrid* out, hipStream_t s) {
     const int n = seg_off_host[n_seg];

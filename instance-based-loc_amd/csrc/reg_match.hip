@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void ibl_feat_pair_nn_kernel(const FeatPair* _
         const int nt = min(FT_TILE, P.dcnt - t0);
         for (int t = 0; t < nt; ++t) {
             const float* __restrict__ row = tile + t * 36;
-            // Rows are stored in matching order (bins from the histogram centres outwards, FEAT_POS in reg_knn.hip), so the
+            // Rows are stored in matching order (bins from the histogram centres outwards, FEAT_POS in reg_fpfh.hip), so the
             // chain is k = 0..32 over contiguous memory.  Its partial sums are non-decreasing: a target is abandoned as soon
             // as no lane of the wave can still beat its running minimum (checked after 4, 8, 12, 16 and 24 terms); the
             // surviving distances are the complete chains, bit-identical to the unpruned form.

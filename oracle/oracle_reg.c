@@ -775,7 +775,7 @@ static void matmul4(const double A[16], const double B[16], double C[16]) {
 
 /* Symmetric 3x3 solve, LDL^T with diagonal pivoting: at each step the largest remaining diagonal entry is moved to the front by a
  * symmetric exchange, then eliminated.  x stays zero and 0 is returned when a pivot is zero or not finite (a singular system: coincident
- * or collinear neighbours).  Written on scalars, the same statements as solve3_sym of csrc/reg_knn.hip:
+ * or collinear neighbours).  Written on scalars, the same statements as solve3_sym of csrc/reg_colorgrad.hip:
  * the device's comparison with this oracle cannot see a slip made in both, so the FORMULA is held by tests/test_feature_model.py, which
  * compares this copy with the least-squares restatement of oracle/open3d_fp64.py. */
 static int solve3_sym(double M[3][3], const double B[3], double x[3]) {

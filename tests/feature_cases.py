@@ -1,5 +1,5 @@
-"""Deterministic clouds for the neighbourhood kernels and their consumers (csrc/reg_knn.hip: tile search, grid-walk fallback, normals,
-SPFH/FPFH, colour gradients, radius counts), shared by tests/test_feature_model.py (CPU: the two references alone show that every cloud
+"""Deterministic clouds for the neighbourhood kernels and their consumers (csrc/knn_select.h: tile search, grid-walk fallback;
+reg_normals.hip, reg_fpfh.hip, reg_colorgrad.hip, reg_radius.hip: normals, SPFH/FPFH, colour gradients, radius counts), shared by tests/test_feature_model.py (CPU: the two references alone show that every cloud
 is what it claims and that holding EVERY row is fair) and tests/test_gpu_features.py (GPU: every row of every output against the oracle,
 and which path served the queries).
 
@@ -24,7 +24,7 @@ NORMAL = (0.1, 30)           # (radius, max_nn) of the normal search
 FEATURE = (0.25, 100)        # ... of the SPFH / FPFH search
 GRAD = (0.15, 30)            # ... of the colour-gradient search (grad_radius=0.15)
 OUTLIER = (0.05, 8)          # radius, nb_points of the radius-outlier filter
-KNN_BINS = 256               # d2 bins over [0, r^2) of the selection (csrc/reg_knn.hip KNN_BINS)
+KNN_BINS = 256               # d2 bins over [0, r^2) of the selection (csrc/knn_select.h KNN_BINS)
 KNN_CAPB = 256               # entries the boundary-bin list holds (KNN_CAPB): more and the query takes the re-scanning slow path
 ST_KNN_SLOWPATH = 2          # status bit IBL_ST_KNN_SLOWPATH
 

@@ -1,4 +1,5 @@
-"""-m gpu: grids, hybrid neighbourhoods, normals, FPFH, colour gradients and radius-outlier masks vs the C oracle (csrc/reg_knn.hip).
+"""-m gpu: grids, hybrid neighbourhoods, normals, FPFH, colour gradients and radius-outlier masks vs the C oracle (csrc/knn_select.h and
+its consumers reg_normals.hip, reg_fpfh.hip, reg_colorgrad.hip; reg_radius.hip).
 
 EVERY ROW.  The clouds of tests/feature_cases.py (tests/test_feature_model.py shows with the references alone what each is there for,
 and that the two references agree on every row where their neighbour sets do) go through `normals_fpfh_batch` and
@@ -22,14 +23,15 @@ PATHS, observed with knn_debug=1 (`[knn] ... fallback=` per tile search) and ctx
                              whose cube cannot show their k nearest
     boundary-bin slow path   boundary alone: status bit 1 (IBL_ST_KNN_SLOWPATH) set, clear after status(clear=True)
 
-Which instantiations the public calls reach (read off reg_api.hip and launch_knn): every search of `normals_fpfh_batch`,
-`instance_features_batch` and the registration runs on a grid of ibl_build_tile_grid, so launch_knn always takes its tile branch:
-ibl_knn_tile_kernel + ibl_knn_list_kernel.  `ibl_knn_query_kernel` (grids without tiles) is launched only when n_tiles == 0, which needs
-n_seg == 0, and those calls return before any launch: NOT reachable.  Tiles of 2^3 cells are built for the 100-neighbour searches only,
-whose factories (SpfhFactory, ListNormalFactory) are both WIDE and take the PACKED 1 600-candidate tile; the unpacked
-`ibl_knn_tile_kernel<2, 2560, Factory>` is instantiated for NormalFactory and GradFactory, which only ever see tiles of 4^3 cells: NOT
-reachable.  Reached: <4, 1024, NormalFactory> (feat_unfused), <4, 1024, GradFactory>, <2, 1600, SpfhFactory, packed> (feat_unfused),
-<2, 1600, ListNormalFactory, packed> (default), ibl_knn_list_kernel of the four factories, ibl_radius_count_kernel.
+Which instantiations the public calls reach (read off reg_api.hip and launch_knn, knn_select.h): every search kernel that is built.
+Every search of `normals_fpfh_batch`, `instance_features_batch` and the registration runs on a grid of ibl_build_tile_grid, whose tile
+edge (KNN_TILE_NORMAL = 4, KNN_TILE_FEATURE = 2, reg_common.h) is the one the consumer's factory states, and launch_knn instantiates
+that factory's one tile kernel + ibl_knn_list_kernel: <4, 1024, NormalFactory> (feat_unfused), <4, 1024, GradFactory>,
+<2, 1600, SpfhFactory, packed> (feat_unfused), <2, 1600, ListNormalFactory, packed> (default), ibl_knn_list_kernel of the four factories,
+ibl_radius_count_kernel.  The per-query kernel for grids without tiles and the tiles no factory is searched on (<2, 2560, *>,
+<4, 1024> of the two packed factories) could not be launched and are no longer built.  If a call ever reached launch_knn with a grid of
+another edge or without tiles it would return IBL_ERR_INTERNAL ("k-NN tiles of %d^3 cells are not built", "k-NN search needs a tile
+grid") instead of launching: every test here that runs a search asserts, through _lib.check, that none did.
 
 Measured on an MI355X: on every cloud, under every switch and through both calls the worst row of normals, FPFH and gradients differs
 from the oracle by 0 (the fp32 outputs are equal bit for bit), and the radius-outlier masks are equal.  With Cramer's rule in the 3 x 3
@@ -297,7 +299,7 @@ def test_fused_normals_and_feature_search_equals_the_two_searches(ctx):
 
 
 def test_spfh_fp32_bins_with_fp64_for_undecided_pairs_equal_the_fp64_bins(ctx):
-    """round 4: the SPFH bins of a pair come from fp32 arithmetic when every decision clears a guard band (pair_bins_f32, csrc/reg_knn.hip)
+    """round 4: the SPFH bins of a pair come from fp32 arithmetic when every decision clears a guard band (pair_bins_f32, csrc/reg_fpfh.hip)
     and from the fp64 pair features otherwise (queue + second kernel).  the switch spfh_f64 evaluates every pair in fp64; spfh_qcap=8
     overflows the queue, which the gated fp64 launch repairs: all three must give the same bytes -- noisy surfaces, exact planes (equal
     normals, theta on a bin boundary for every pair), a cloud 200 m from the origin, tiny and empty clouds"""

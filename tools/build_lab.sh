@@ -1,6 +1,8 @@
 #!/bin/bash
 # Lab builds of libibloc_hip.so with other compile-time constants (not the product library): tools/_lab/libibloc_<tag>.so,
-# selected at run time with IBLOC_LIB=...   usage: tools/build_lab.sh <tag> <file.hip> "<-D flags>" [<file2.hip> ...]
+# selected at run time with IBLOC_LIB=...   usage: tools/build_lab.sh <tag> <file.hip> "<-D flags>" [<file2.hip> "<-D flags>" ...]
+# e.g. the tile search's phase clocks and selection counters (knn_select.h is compiled into each of its three consumers' objects):
+#   tools/build_lab.sh knnclk reg_normals.hip "-DKNN_LAB_CLK -DKNN_LAB_STATS" reg_fpfh.hip "-DKNN_LAB_CLK -DKNN_LAB_STATS" reg_colorgrad.hip "-DKNN_LAB_CLK -DKNN_LAB_STATS"
 set -e
 tag=$1; shift
 cd "$(dirname "$0")/../instance-based-loc_amd/csrc"

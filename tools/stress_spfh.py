@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU: randomised cross-check of the fp32-guard-band SPFH path (pair_bins_f32 + fp64 queue, csrc/reg_knn.hip) against the all-fp64 evaluation
+"""GPU: randomised cross-check of the fp32-guard-band SPFH path (pair_bins_f32 + fp64 queue, csrc/reg_fpfh.hip) against the all-fp64 evaluation
 (switch spfh_f64) on clouds of many shapes: the FPFH rows (and normals) must be identical, bit for bit.  python tools/stress_spfh.py [rounds]"""
 import os
 import sys
