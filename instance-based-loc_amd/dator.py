@@ -6,7 +6,6 @@ The reference's `dator_wrapper.get_model_input` is missing from its repository; 
 surviving record, dator/get_embeds.py:80-87 (RGB: resize to 256x128, ToTensor, mean = std = 0.5) and :129-136
 (depth: bilinear resize to 256x128, tiled to 3 channels, clipped to [0, 50], /50, (x - 0.5) / 0.5)."""
 import ctypes as C
-import dataclasses
 
 import numpy as np
 import torch
@@ -139,13 +138,14 @@ def fourdnet_state_dict_to_weights(state_dict: dict):
     return stream("base."), stream("base2."), hw
 
 
+# (field of ibl_dator_head_weights, key of the head-weights dict), in the struct's order
+_HEAD_FIELDS = [(f"{n}_{p}", f"{n}.{p}") for n in HEAD_LINEARS for p in "wb"] \
+    + [(f"{op}_{part}_{p}", f"{op}.{part}.{p}") for op in ATTN_OPS for part, ps in (("sel", "wb"), ("aw", "wb"), ("ffn", "wb"), ("norm", "gb")) for p in ps] \
+    + [(f"hyper{i}_{p}", f"hyper.{i}.{p}") for i in range(4) for p in "wb"]
+
+
 class DatorHeadWeights(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in
-                ["proj_local_rgb_w", "proj_local_rgb_b", "proj_global_rgb_w", "proj_global_rgb_b", "merge_rgb_w", "merge_rgb_b",
-                 "proj_local_depth_w", "proj_local_depth_b", "proj_global_depth_w", "proj_global_depth_b", "merge_depth_w",
-                 "merge_depth_b", "Q_r_w", "Q_r_b", "V_r_w", "V_r_b", "Q_d_w", "Q_d_b", "V_d_w", "V_d_b"]
-                + [f"{op}_{p}" for op in ATTN_OPS for p in ("sel_w", "sel_b", "aw_w", "aw_b", "ffn_w", "ffn_b", "norm_g", "norm_b")]
-                + [f"hyper{i}_{p}" for i in range(4) for p in ("w", "b")]]
+    _fields_ = [(field, C.c_void_p) for field, _ in _HEAD_FIELDS]
 
 
 # workspace buffers of ibl_dator_head_forward in the order of include/ibloc.h's IBL_DATOR_WS_* enum, with their row widths
@@ -162,16 +162,7 @@ class DatorHead:
         self.device = torch.device(device)
         self._keep = []
         H = DatorHeadWeights()
-        for name, _ in DatorHeadWeights._fields_:
-            key = name
-            for a, b in (("_w", ".w"), ("_b", ".b"), ("_g", ".g")):
-                if key.endswith(a):
-                    key = key[:-len(a)] + b
-                    break
-            for op in ATTN_OPS:
-                for part in ("sel", "aw", "ffn", "norm"):
-                    key = key.replace(f"{op}_{part}", f"{op}.{part}")
-            key = key.replace("hyper0", "hyper.0").replace("hyper1", "hyper.1").replace("hyper2", "hyper.2").replace("hyper3", "hyper.3")
+        for name, key in _HEAD_FIELDS:
             arr = np.ascontiguousarray(head_weights[key], dtype=np.float32)
             if key.startswith("hyper") and key.endswith(".w"):
                 # conv weights [co][ci][3][3] -> [tap][ci][co] (output channels contiguous: one per thread)
@@ -180,15 +171,12 @@ class DatorHead:
             self._keep.append(t)
             setattr(H, name, t.data_ptr())
         self.H = H
-        self._ws = {}
+        self._ws = V.Workspace(self.device)
 
     def forward(self, rgb_tokens: torch.Tensor, depth_tokens: torch.Tensor, lane: int = 0) -> torch.Tensor:
         """fp32 token tensors (B, 129, 768) of the two streams -> (B, 128).  lane: workspace index for concurrent forwards."""
         B = rgb_tokens.shape[0]
-        ws_bytes = _lib.lib.ibl_dator_head_workspace_bytes(B)
-        ws = self._ws.get(lane)
-        if ws is None or ws.numel() < ws_bytes:
-            ws = self._ws[lane] = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+        ws = self._ws.get(lane, _lib.lib.ibl_dator_head_workspace_bytes(B))
         out = torch.empty((B, 128), dtype=torch.float32, device=self.device)
         st = _lib.lib.ibl_dator_head_forward(C.byref(self.H), rgb_tokens.data_ptr(), depth_tokens.data_ptr(), B, out.data_ptr(),
                                              ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
@@ -198,25 +186,17 @@ class DatorHead:
     def taps(self, batch: int, lane: int = 0) -> dict:
         """Views of what the last `forward` of `batch` crops on `lane` left in its workspace (include/ibloc.h, IBL_DATOR_WS_*):
         name -> [B*128, C] tensor ("gl": [B, C]; the gates "rgb_f" / "depth_f": [B, 128]).  The next forward overwrites them."""
-        ws = self._ws[lane]
         offs = (C.c_int64 * len(HEAD_TAPS))()
         _lib.check(_lib.lib.ibl_dator_head_workspace_layout(batch, offs, len(HEAD_TAPS)), "ibl_dator_head_workspace_layout")
-        base = (-ws.data_ptr()) % 256
-        out = {}
-        for (name, width), off in zip(HEAD_TAPS, offs):
-            shape = (batch, 128) if width == 0 or name == "gl" else (batch * 128, width)
-            n = shape[0] * shape[1] * 4
-            assert base + off + n <= ws.numel()
-            out[name] = ws[base + off:base + off + n].view(torch.float32).view(shape)
-        return out
+        return self._ws.views(lane, offs, [(name, torch.float32, (batch, 128) if width == 0 or name == "gl" else (batch * 128, width))
+                                           for name, width in HEAD_TAPS])
 
 
 class DatorEncoder:
     def __init__(self, rgb_weights: dict, depth_weights: dict, head_weights: dict, device="cuda", precision=None):
         """precision: operand-term plan of the two streams (ibloc_amd.vit syntax; None = $IBL_VIT_PREC or DEFAULT_PRECISION below)"""
-        import os
         self.device = torch.device(device)
-        self.precision = precision if precision is not None else os.environ.get("IBL_VIT_PREC", DEFAULT_PRECISION)
+        self.precision = V.resolve_options(DEFAULT_PRECISION, precision)[0]
         self.rgb = V.VitEncoder(STREAM_CFG, fold_lora(rgb_weights), device=device, precision=self.precision)
         self.depth = V.VitEncoder(STREAM_CFG, fold_lora(depth_weights), device=device, precision=self.precision)
         self._head = DatorHead(head_weights, device=device)
@@ -258,10 +238,9 @@ class DatorEncoder:
         (its `crops` argument is handed through as is).  lane: workspace index for concurrent forwards on different streams."""
         if depth_crops is None:
             rgb_crops, depth_crops = rgb_crops
-        n = rgb_crops.shape[0] if isinstance(rgb_crops, torch.Tensor) else len(rgb_crops)
-        outs = []
-        for i in range(0, n, max_batch):
-            rt = self.rgb.forward_patches(self.rgb.preprocess(rgb_crops[i:i + max_batch]), lane=lane)
-            dt = self.depth.forward_patches(self.preprocess_depth(depth_crops[i:i + max_batch]), lane=lane)
-            outs.append(self.head(rt, dt, lane=lane))
-        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+        def run(sl):
+            rt = self.rgb.forward_patches(self.rgb.preprocess(rgb_crops[sl]), lane=lane)
+            dt = self.depth.forward_patches(self.preprocess_depth(depth_crops[sl]), lane=lane)
+            return self.head(rt, dt, lane=lane)
+        return V.embed_chunks(rgb_crops.shape[0] if isinstance(rgb_crops, torch.Tensor) else len(rgb_crops), max_batch, run)

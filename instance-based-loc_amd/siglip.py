@@ -86,22 +86,22 @@ class ProbeHead:
         self.device = torch.device(device)
         self._keep = {}
         D, M = cfg.dim, cfg.mlp_dim
-        arrays = {"u": fold_head(head_weights, cfg.heads), "w_v": head_weights["v.w"], "b_v": head_weights["v.b"], "w_o": head_weights["o.w"],
-                  "b_o": head_weights["o.b"], "ln_g": head_weights["ln.g"], "ln_b": head_weights["ln.b"], "w_fc1": head_weights["fc1.w"],
-                  "b_fc1": head_weights["fc1.b"], "w_fc2": head_weights["fc2.w"], "b_fc2": head_weights["fc2.b"]}
-        shapes = {"u": (cfg.heads, D), "w_v": (D, D), "b_v": (D,), "w_o": (D, D), "b_o": (D,), "ln_g": (D,), "ln_b": (D,), "w_fc1": (M, D),
-                  "b_fc1": (M,), "w_fc2": (D, M), "b_fc2": (D,)}
+        hw = head_weights
+        # struct field -> (array, shape it must have); `u` is folded from the probe, the query and the key projection
+        fields = {"u": (fold_head(hw, cfg.heads), (cfg.heads, D)), "w_v": (hw["v.w"], (D, D)), "b_v": (hw["v.b"], (D,)), "w_o": (hw["o.w"], (D, D)),
+                  "b_o": (hw["o.b"], (D,)), "ln_g": (hw["ln.g"], (D,)), "ln_b": (hw["ln.b"], (D,)), "w_fc1": (hw["fc1.w"], (M, D)),
+                  "b_fc1": (hw["fc1.b"], (M,)), "w_fc2": (hw["fc2.w"], (D, M)), "b_fc2": (hw["fc2.b"], (D,))}
         W = ProbeHeadWeights()
-        for name, a in arrays.items():
+        for name, (a, shape) in fields.items():
             a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.shape != shapes[name]:
-                raise ValueError(f"head weight {name}: shape {a.shape}, expected {shapes[name]}")
+            if a.shape != shape:
+                raise ValueError(f"head weight {name}: shape {a.shape}, expected {shape}")
             t = torch.from_numpy(a).to(self.device)
             self._keep[name] = t
             setattr(W, name, t.data_ptr())
         self.W = W
         self.desc = ProbeHeadDesc(D, cfg.heads, M, cfg.n_tokens, cfg.ln_eps)
-        self._ws = {}
+        self._ws = V.Workspace(self.device)
 
     @property
     def u(self) -> torch.Tensor:
@@ -115,9 +115,7 @@ class ProbeHead:
         ws_bytes = _lib.lib.ibl_probe_head_workspace_bytes(C.byref(self.desc), B)
         if ws_bytes < 0:
             _lib.check(-1, "ibl_probe_head_workspace_bytes")
-        ws = self._ws.get(lane)
-        if ws is None or ws.numel() < ws_bytes:
-            ws = self._ws[lane] = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+        ws = self._ws.get(lane, ws_bytes)
         out = torch.empty((B, self.cfg.dim), dtype=torch.float32, device=self.device)
         st = _lib.lib.ibl_probe_head_forward(C.byref(self.desc), C.byref(self.W), tokens.data_ptr(), B, out.data_ptr(), ws.data_ptr(),
                                              ws.numel(), torch.cuda.current_stream().cuda_stream)
@@ -127,19 +125,12 @@ class ProbeHead:
     def taps(self, batch: int, lane: int = 0) -> dict:
         """Views of what the last `forward` of `batch` crops on `lane` left in its workspace (include/ibloc.h, IBL_PROBE_WS_*):
         probs (B, heads, T), pooled (B, heads, dim), vcat / att / ln (B, dim), hid (B, mlp_dim).  The next forward overwrites them."""
-        ws = self._ws[lane]
         c = self.cfg
         offs = (C.c_int64 * len(HEAD_TAPS))()
         _lib.check(_lib.lib.ibl_probe_head_workspace_layout(C.byref(self.desc), batch, offs, len(HEAD_TAPS)), "ibl_probe_head_workspace_layout")
         shapes = {"probs": (batch, c.heads, c.n_tokens), "pooled": (batch, c.heads, c.dim), "vcat": (batch, c.dim), "att": (batch, c.dim),
                   "ln": (batch, c.dim), "hid": (batch, c.mlp_dim)}
-        base = (-ws.data_ptr()) % 256
-        out = {}
-        for name, off in zip(HEAD_TAPS, offs):
-            n = int(np.prod(shapes[name])) * 4
-            assert base + off + n <= ws.numel()
-            out[name] = ws[base + off:base + off + n].view(torch.float32).view(shapes[name])
-        return out
+        return self._ws.views(lane, offs, [(name, torch.float32, shapes[name]) for name in HEAD_TAPS])
 
 
 class SiglipEncoder:
@@ -170,5 +161,4 @@ class SiglipEncoder:
         n = crops.shape[0] if isinstance(crops, torch.Tensor) else len(crops)
         if n == 0:
             return torch.empty((0, self.cfg.dim), dtype=torch.float32, device=self.device)
-        outs = [self.forward_patches(self.preprocess(crops[i:i + max_batch]), lane=lane) for i in range(0, n, max_batch)]
-        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        return V.embed_chunks(n, max_batch, lambda sl: self.forward_patches(self.preprocess(crops[sl]), lane=lane))

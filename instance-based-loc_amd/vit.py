@@ -6,6 +6,7 @@ preprocess + forward call.  Replaces the model objects utils/embeddings.py build
 import ctypes as C
 import dataclasses
 import math
+import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -51,6 +52,7 @@ class VitWeights(C.Structure):
 
 
 SPLIT_SCALE = 64.0          # IBL_VIT_SPLIT_SCALE (include/ibloc.h)
+F16, F32 = "fp16", "fp32"   # what `pack_top` / `pack_layer` tag an array with: both leave the host as float32, F16 is rounded on the device
 
 # Which operands of which blocks get a second fp16 term ("p<terms>;<layer>:<qkv><o><fc1><fc2>;...", layer "*" = every other block; qkv / fc1: 1, 2 (weights) or 3
 # (weights + LayerNorm output), o / fc2: 1, 2 (weights) or 3 (weights + the attention output / the GELU hidden layer in two terms: one more
@@ -376,164 +378,229 @@ class PackedCrops:
                            _offs=self.offs[lo:hi + 1] - self.offs[lo])
 
 
+def resolve_options(default_plan, precision=None, fold_layerscale=None, resid_kext=None):
+    """constructor arguments + environment -> (precision, fold_layerscale, resid_kext); the one place that reads $IBL_VIT_PREC,
+    $IBL_VIT_FOLD_LS and $IBL_VIT_RESID_KEXT (0: second weight terms of o / fc2 as launches of their own, rounds 3-4a)"""
+    return (precision if precision is not None else os.environ.get("IBL_VIT_PREC", default_plan),
+            os.environ.get("IBL_VIT_FOLD_LS", "0") == "1" if fold_layerscale is None else bool(fold_layerscale),
+            os.environ.get("IBL_VIT_RESID_KEXT", "1") != "0" if resid_kext is None else bool(resid_kext))
+
+
+def validate(cfg: VitConfig, weights: dict):
+    """what the kernels cannot run, or the weights do not fit: ValueError"""
+    if cfg.depth > MAX_LAYERS:
+        raise ValueError("too many layers")
+    if cfg.quick_gelu and cfg.tanh_gelu:
+        raise ValueError("quick_gelu and tanh_gelu are both set")
+    if cfg.dim != 64 * cfg.heads:
+        raise ValueError(f"head_dim {cfg.dim / cfg.heads:g} is not supported: the attention and rotation kernels run head_dim 64")
+    if cfg.n_registers and not cfg.cls_token:
+        raise ValueError("n_registers needs cls_token: registers follow the class row")
+    if cfg.n_registers and tuple(np.shape(weights.get("reg", ()))) != (cfg.n_registers, cfg.dim):
+        raise ValueError(f"the weights hold registers of shape {np.shape(weights.get('reg', ()))}, the configuration {cfg.name} "
+                         f"needs ({cfg.n_registers}, {cfg.dim})")
+    if not cfg.n_registers and np.size(weights.get("reg", ())):
+        raise ValueError(f"the weights hold {np.shape(weights['reg'])[0]} register tokens, the configuration {cfg.name} none")
+    if cfg.rope_theta is not None and "pos" in weights:
+        raise ValueError("rope_theta and a position table are both given")
+    if not cfg.cls_token and cfg.rope_theta is None:
+        if not cfg.out_all_tokens:
+            raise ValueError("cls_token=False needs out_all_tokens: there is no class row to return")
+        if tuple(cfg.pos_grid) != tuple(cfg.grid) or np.shape(weights["pos"]) != (cfg.n_patches, cfg.dim):
+            raise ValueError(f"cls_token=False: the position table {np.shape(weights['pos'])} of grid {cfg.pos_grid} must be that of the run grid {cfg.grid}")
+
+
+def plan_terms(cfg: VitConfig, layer_terms: dict, resid_kext=True):
+    """parsed plan -> ([(qkv, o, fc1, fc2) the host packs block l for], [(o, fc2): the second weight term goes as a launch of its own],
+    act_terms: the widest rows a residual GEMM reads).  Without resid_kext o / fc2 are one-term rows (2 = the extra launch, 3 refused)."""
+    nrun = cfg.depth if cfg.n_blocks_run < 0 else cfg.n_blocks_run
+    terms, lo_launch = [], []
+    for l in range(cfg.depth):
+        t = layer_terms.get(l, layer_terms.get("*"))
+        if t is None or (l == nrun - 1 and not cfg.out_all_tokens):     # the CLS-only last block stays plain
+            t = (1, 1, 1, 1)
+        for name, v in (("o", t[1]), ("fc2", t[3])):
+            if not resid_kext and v > 2:
+                raise ValueError(f"{name} = 3 needs the K-extended form")
+        lo_launch.append((t[1] == 2, t[3] == 2) if not resid_kext else (False, False))
+        terms.append(t if resid_kext else (t[0], 1, t[2], 1))
+    return terms, lo_launch, max([1] + [max(t[1], t[3]) for t in terms])
+
+
+def pack_top(cfg: VitConfig, weights: dict, patch_terms=1, proj_x=False) -> dict:
+    """-> {ibl_vit_weights field: (F16 | F32, float32 array)} outside the layers; no device"""
+    validate(cfg, weights)
+    if cfg.rope_theta is not None:
+        # rotary models: no position table.  The patch scatter still adds a row per patch, so it is handed zeros
+        pos = np.zeros((int(cfg.cls_token) + cfg.n_patches, cfg.dim), dtype=np.float32)
+    elif cfg.cls_token:
+        pos = interpolate_pos_embed(weights["pos"], cfg)
+    else:
+        # no class token: the table is (gh * gw, D) and used as stored (resampling it is not supported)
+        pos = np.ascontiguousarray(weights["pos"], dtype=np.float32)
+    wp = np.zeros((cfg.dim, cfg.patch_k_pad), dtype=np.float32)
+    wp[:, :cfg.patch_k] = weights["patch.w"].reshape(cfg.dim, -1)
+    a = {"w_patch": (F16, wp)}
+    if patch_terms == 2:
+        a["w_patch_lo"] = (F16, weight_lo(wp))
+    if "patch.b" in weights:
+        a["b_patch"] = (F32, weights["patch.b"])
+    a["pos_patch"] = (F32, pos[1:] if cfg.cls_token else pos)
+    if cfg.cls_token:
+        a["cls_pos"] = (F32, weights["cls"].reshape(-1) + pos[0])
+    if cfg.n_registers:
+        a["reg_tokens"] = (F32, weights["reg"])
+    if cfg.rope_theta is not None:
+        a["rope_table"] = (F32, rope_table(cfg.grid[0], cfg.grid[1], cfg.rope_theta))
+    if cfg.pre_ln:
+        a["ln_pre_g"], a["ln_pre_b"] = (F32, weights["ln_pre.g"]), (F32, weights["ln_pre.b"])
+    if cfg.final_ln:
+        a["ln_f_g"], a["ln_f_b"] = (F32, weights["ln_f.g"]), (F32, weights["ln_f.b"])
+    if cfg.proj_dim:
+        a["w_proj"] = (F16, weights["proj.w"])
+        if proj_x:      # the last arithmetic before the output: three-term operands (free at batch x dim x out_dim)
+            a["w_proj_x"] = (F16, split_terms(weights["proj.w"], 3))
+    return a
+
+
+def _pack_resid(cfg, weights, p, name, i, terms, lo_launch, fold):
+    """one residual GEMM of a block (o: i = 1, fc2: i = 2), as `pack_layer` yields it.
+    fold (lab, off by default): x += ls * (a W^T + b) = a (diag(ls) W)^T + ls * b.  Without a scale vector in the epilogue the library
+    can preload the residual tile into the accumulators (EPI_RESID_PRE_F32, csrc/vit_gemm.hip).  (Without LayerScale: "folded" = no
+    1 / S vectors for the second terms either)"""
+    w, b = np.asarray(weights[p + name + ".w"], np.float32), np.asarray(weights[p + name + ".b"], np.float32)
+    ls = np.asarray(weights[p + f"ls{i}"], np.float32) if cfg.layerscale else None
+    if fold and ls is not None:
+        w, b = ls[:, None] * w, ls * b
+    elif ls is not None:
+        yield f"ls{i}", (F32, ls)
+    yield "w_" + name, (F16, w)
+    yield "b_" + name, (F32, b)
+    if terms > 1:
+        yield f"w_{name}_x", (F16, split_terms(w, terms))
+        yield name + "_terms", terms
+    elif lo_launch:
+        yield f"w_{name}_lo", (F16, weight_lo(w))
+        if not fold:                             # (no vector: the library adds the term with the factor 1 / S, residual preloaded)
+            yield f"ls{i}_lo", (F32, (ls if ls is not None else np.ones(cfg.dim, dtype=np.float32)) / SPLIT_SCALE)
+
+
+def pack_layer(cfg: VitConfig, weights: dict, l: int, terms, lo_launch=(False, False), fold=False):
+    """block l -> (ibl_vit_layer field, value) pairs, value = (F16 | F32, float32 array) or the int of a `*_terms` field; terms, lo_launch:
+    `plan_terms`' entries for the block.  A field the block does not use is not yielded.  No device.  A generator: a consumer that uploads
+    as it goes holds one operand's fp32 temporaries at a time, as the hot pages of one allocation (`dict(pack_layer(...))`: the layer's)"""
+    p = f"l{l}."
+    tq, to, t1, t2 = terms
+    for name in ("ln1", "ln2"):
+        yield name + "_g", (F32, weights[p + name + ".g"])
+        yield name + "_b", (F32, weights[p + name + ".b"])
+    wqkv = np.concatenate([weights[p + "q.w"], weights[p + "k.w"], weights[p + "v.w"]], axis=0)
+    yield "w_qkv", (F16, wqkv)
+    if tq > 1:
+        yield "w_qkv_x", (F16, split_terms(wqkv, tq))
+        yield "qkv_terms", tq
+    yield "b_qkv", (F32, np.concatenate([weights[p + "q.b"], weights[p + "k.b"], weights[p + "v.b"]], axis=0))
+    yield "w_fc1", (F16, weights[p + "fc1.w"])
+    yield "b_fc1", (F32, weights[p + "fc1.b"])
+    if t1 > 1:
+        yield "w_fc1_x", (F16, split_terms(weights[p + "fc1.w"], t1))
+        yield "fc1_terms", t1
+    yield from _pack_resid(cfg, weights, p, "o", 1, to, lo_launch[0], fold)
+    yield from _pack_resid(cfg, weights, p, "fc2", 2, t2, lo_launch[1], fold)
+
+
+# VitConfig attribute -> descriptor flag (IBL_VIT_NO_CLS is the absence of one: `make_desc`)
+CONFIG_FLAGS = (("layerscale", FLAG_LAYERSCALE), ("pre_ln", FLAG_PRE_LN), ("final_ln", FLAG_FINAL_LN), ("proj_dim", FLAG_PROJ),
+                ("quick_gelu", FLAG_QUICK_GELU), ("out_all_tokens", FLAG_OUT_ALL_TOKENS), ("tanh_gelu", FLAG_TANH_GELU))
+
+
+def make_desc(cfg: VitConfig, act_terms=1) -> VitDesc:
+    flags = sum(flag for attr, flag in CONFIG_FLAGS if getattr(cfg, attr))
+    flags |= (0 if cfg.cls_token else FLAG_NO_CLS) | {1: 0, 2: FLAG_ACT_TERMS2, 3: FLAG_ACT_TERMS3}[act_terms]
+    return VitDesc(cfg.dim, cfg.depth, cfg.heads, cfg.mlp_dim, cfg.patch, cfg.img_h, cfg.img_w, cfg.n_tokens, cfg.patch_k_pad, flags,
+                   cfg.depth if cfg.n_blocks_run < 0 else cfg.n_blocks_run, cfg.out_dim, cfg.ln_eps, cfg.n_registers)
+
+
+class Workspace:
+    """The byte buffers a C-ABI forward works in, one per lane, grown on demand; and typed views into one by the offsets of the library's
+    `*_workspace_layout` call, which count from the first 256-byte boundary of the buffer."""
+
+    def __init__(self, device):
+        self.device, self._lanes = device, {}
+
+    def get(self, lane, nbytes) -> torch.Tensor:
+        ws = self._lanes.get(lane)
+        if ws is None or ws.numel() < nbytes:
+            ws = self._lanes[lane] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def views(self, lane, offsets, specs) -> dict:
+        """offsets: what the layout call filled in; specs: [(name, dtype, shape)] in the same order -> {name: view}"""
+        ws = self._lanes[lane]
+        base = (-ws.data_ptr()) % 256
+        out = {}
+        for off, (name, dtype, shape) in zip(offsets, specs):
+            lo, n = base + off, math.prod(shape) * dtype.itemsize
+            assert lo + n <= ws.numel()
+            out[name] = ws[lo:lo + n].view(dtype).view(shape)
+        return out
+
+
+def embed_chunks(n, max_batch, run) -> torch.Tensor:
+    """run(slice) for every chunk of at most max_batch of n crops, the results as one tensor"""
+    outs = [run(slice(i, i + max_batch)) for i in range(0, n, max_batch)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+
 class VitEncoder:
     """Device-resident weights + batched forward through the C-ABI."""
 
-    def __init__(self, cfg: VitConfig, weights: dict, device="cuda", precision=None, fold_layerscale=None):
+    def __init__(self, cfg: VitConfig, weights: dict, device="cuda", precision=None, fold_layerscale=None, resid_kext=None):
         """precision: operand-term plan (see DEFAULT_PRECISION; None = $IBL_VIT_PREC or the default, "plain" = fp16 operands only);
         fold_layerscale: LayerScale multiplied into the output-projection weights at load, so that the library may run the residual GEMMs
         with the residual tile preloaded (lab: with IBL_GEMM_RESID_PRE=1; measured 2 % slower than the read-modify-write epilogue, so the
-        default -- also with $IBL_VIT_FOLD_LS unset -- keeps the LayerScale vectors and round 3's arithmetic)"""
-        if cfg.depth > MAX_LAYERS:
-            raise ValueError("too many layers")
-        import os
-        self.precision = precision if precision is not None else os.environ.get("IBL_VIT_PREC", MODEL_PRECISION.get(cfg.name, DEFAULT_PRECISION))
-        patch_terms, layer_terms = parse_precision(self.precision)
-        self.fold_layerscale = (os.environ.get("IBL_VIT_FOLD_LS", "0") == "1") if fold_layerscale is None else bool(fold_layerscale)
+        default -- also with $IBL_VIT_FOLD_LS unset -- keeps the LayerScale vectors and round 3's arithmetic);
+        resid_kext: the second and third terms of o / fc2 as K-extended rows (None = on unless $IBL_VIT_RESID_KEXT is 0)"""
+        self.precision, self.fold_layerscale, resid_kext = resolve_options(MODEL_PRECISION.get(cfg.name, DEFAULT_PRECISION), precision,
+                                                                           fold_layerscale, resid_kext)
         self.cfg = cfg
         self.device = torch.device(device)
+        patch_terms, layer_terms = parse_precision(self.precision)
+        terms, lo_launch, self.act_terms = plan_terms(cfg, layer_terms, resid_kext)
+        top = pack_top(cfg, weights, patch_terms, proj_x=self.precision != "plain")
         self._keep = []                     # device tensors referenced by the structs
-
-        def dev_f32(a):
-            t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
-            self._keep.append(t)
-            return t.data_ptr()
-
-        def dev_f16(a):
-            t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device).to(torch.float16).contiguous()
-            self._keep.append(t)
-            return t.data_ptr()
-
-        if cfg.quick_gelu and cfg.tanh_gelu:
-            raise ValueError("quick_gelu and tanh_gelu are both set")
-        if cfg.dim != 64 * cfg.heads:
-            raise ValueError(f"head_dim {cfg.dim / cfg.heads:g} is not supported: the attention and rotation kernels run head_dim 64")
-        if cfg.n_registers and not cfg.cls_token:
-            raise ValueError("n_registers needs cls_token: registers follow the class row")
-        if cfg.n_registers and tuple(np.shape(weights.get("reg", ()))) != (cfg.n_registers, cfg.dim):
-            raise ValueError(f"the weights hold registers of shape {np.shape(weights.get('reg', ()))}, the configuration {cfg.name} "
-                             f"needs ({cfg.n_registers}, {cfg.dim})")
-        if not cfg.n_registers and np.size(weights.get("reg", ())):
-            raise ValueError(f"the weights hold {np.shape(weights['reg'])[0]} register tokens, the configuration {cfg.name} none")
-        if cfg.rope_theta is not None:
-            # rotary models: no position table.  The patch scatter still adds a row per patch, so it is handed zeros
-            if "pos" in weights:
-                raise ValueError("rope_theta and a position table are both given")
-            pos = np.zeros((int(cfg.cls_token) + cfg.n_patches, cfg.dim), dtype=np.float32)
-        elif cfg.cls_token:
-            pos = interpolate_pos_embed(weights["pos"], cfg)
-        else:
-            # no class token: the table is (gh * gw, D) and used as stored (resampling it is not supported)
-            if not cfg.out_all_tokens:
-                raise ValueError("cls_token=False needs out_all_tokens: there is no class row to return")
-            pos = np.ascontiguousarray(weights["pos"], dtype=np.float32)
-            if tuple(cfg.pos_grid) != tuple(cfg.grid) or pos.shape != (cfg.n_patches, cfg.dim):
-                raise ValueError(f"cls_token=False: the position table {pos.shape} of grid {cfg.pos_grid} must be that of the run grid {cfg.grid}")
-        wp = np.zeros((cfg.dim, cfg.patch_k_pad), dtype=np.float32)
-        wp[:, :cfg.patch_k] = weights["patch.w"].reshape(cfg.dim, -1)
-        W = VitWeights()
-        W.w_patch = dev_f16(wp)
-        if patch_terms == 2:
-            W.w_patch_lo = dev_f16(weight_lo(wp))
-        W.b_patch = dev_f32(weights["patch.b"]) if "patch.b" in weights else None
-        if cfg.cls_token:
-            W.cls_pos = dev_f32(weights["cls"].reshape(-1) + pos[0])
-            W.pos_patch = dev_f32(pos[1:])
-        else:
-            W.pos_patch = dev_f32(pos)
-        if cfg.n_registers:
-            W.reg_tokens = dev_f32(weights["reg"])
-        if cfg.rope_theta is not None:
-            W.rope_table = dev_f32(rope_table(cfg.grid[0], cfg.grid[1], cfg.rope_theta))
-        if cfg.pre_ln:
-            W.ln_pre_g, W.ln_pre_b = dev_f32(weights["ln_pre.g"]), dev_f32(weights["ln_pre.b"])
-        if cfg.final_ln:
-            W.ln_f_g, W.ln_f_b = dev_f32(weights["ln_f.g"]), dev_f32(weights["ln_f.b"])
-        if cfg.proj_dim:
-            W.w_proj = dev_f16(weights["proj.w"])
-            if self.precision != "plain":      # the last arithmetic before the output: three-term operands (free at batch x dim x out_dim)
-                W.w_proj_x = dev_f16(split_terms(weights["proj.w"], 3))
-        for l in range(cfg.depth):
-            p = f"l{l}."
-            L = W.layers[l]
-            L.ln1_g, L.ln1_b = dev_f32(weights[p + "ln1.g"]), dev_f32(weights[p + "ln1.b"])
-            L.w_qkv = dev_f16(np.concatenate([weights[p + "q.w"], weights[p + "k.w"], weights[p + "v.w"]], axis=0))
-            L.b_qkv = dev_f32(np.concatenate([weights[p + "q.b"], weights[p + "k.b"], weights[p + "v.b"]], axis=0))
-            # fold_layerscale (lab, off by default): x += ls * (a W^T + b) = a (diag(ls) W)^T + ls * b.  Without a scale vector in the
-            # epilogue the library can preload the residual tile into the accumulators (EPI_RESID_PRE_F32, csrc/vit_gemm.hip).
-            w_o, b_o, w_fc2, b_fc2 = weights[p + "o.w"], weights[p + "o.b"], weights[p + "fc2.w"], weights[p + "fc2.b"]
-            fold = self.fold_layerscale              # (without LayerScale: "folded" = no 1 / S vectors for the second terms either)
-            if fold and cfg.layerscale:
-                ls1, ls2 = np.asarray(weights[p + "ls1"], np.float32), np.asarray(weights[p + "ls2"], np.float32)
-                w_o, b_o = ls1[:, None] * np.asarray(w_o, np.float32), ls1 * np.asarray(b_o, np.float32)
-                w_fc2, b_fc2 = ls2[:, None] * np.asarray(w_fc2, np.float32), ls2 * np.asarray(b_fc2, np.float32)
-            L.w_o, L.b_o = dev_f16(w_o), dev_f32(b_o)
-            L.ln2_g, L.ln2_b = dev_f32(weights[p + "ln2.g"]), dev_f32(weights[p + "ln2.b"])
-            L.w_fc1, L.b_fc1 = dev_f16(weights[p + "fc1.w"]), dev_f32(weights[p + "fc1.b"])
-            L.w_fc2, L.b_fc2 = dev_f16(w_fc2), dev_f32(b_fc2)
-            if cfg.layerscale and not fold:
-                L.ls1, L.ls2 = dev_f32(weights[p + "ls1"]), dev_f32(weights[p + "ls2"])
-            nrun_ = cfg.depth if cfg.n_blocks_run < 0 else cfg.n_blocks_run
-            if (l in layer_terms or "*" in layer_terms) and not (l == nrun_ - 1 and not cfg.out_all_tokens):     # the CLS-only last block stays plain
-                tq, to, t1, t2 = layer_terms[l] if l in layer_terms else layer_terms["*"]
-                ones = np.ones(cfg.dim, dtype=np.float32)
-                if tq > 1:
-                    L.w_qkv_x = dev_f16(split_terms(np.concatenate([weights[p + "q.w"], weights[p + "k.w"], weights[p + "v.w"]], axis=0), tq))
-                    L.qkv_terms = tq
-                kext = os.environ.get("IBL_VIT_RESID_KEXT", "1") != "0"       # 0: second weight terms of o / fc2 as launches of their own (rounds 3-4a)
-                self._act_terms = max(getattr(self, "_act_terms", 1), to if kext else 1, t2 if kext else 1)
-                if to > 1 and kext:
-                    L.w_o_x, L.o_terms = dev_f16(split_terms(w_o, to)), to
-                elif to > 1:
-                    if to > 2:
-                        raise ValueError("o = 3 needs the K-extended form")
-                    L.w_o_lo = dev_f16(weight_lo(w_o))
-                    if not fold:                             # (no vector: the library adds the term with the factor 1 / S, residual preloaded)
-                        L.ls1_lo = dev_f32((weights[p + "ls1"] if cfg.layerscale else ones) / SPLIT_SCALE)
-                if t1 > 1:
-                    L.w_fc1_x = dev_f16(split_terms(weights[p + "fc1.w"], t1))
-                    L.fc1_terms = t1
-                if t2 > 1 and kext:
-                    L.w_fc2_x, L.fc2_terms = dev_f16(split_terms(w_fc2, t2)), t2
-                elif t2 > 1:
-                    if t2 > 2:
-                        raise ValueError("fc2 = 3 needs the K-extended form")
-                    L.w_fc2_lo = dev_f16(weight_lo(w_fc2))
-                    if not fold:
-                        L.ls2_lo = dev_f32((weights[p + "ls2"] if cfg.layerscale else ones) / SPLIT_SCALE)
-        self.W = W
-        flags = 0
-        flags |= FLAG_LAYERSCALE if cfg.layerscale else 0
-        flags |= FLAG_PRE_LN if cfg.pre_ln else 0
-        flags |= FLAG_FINAL_LN if cfg.final_ln else 0
-        flags |= FLAG_PROJ if cfg.proj_dim else 0
-        flags |= FLAG_QUICK_GELU if cfg.quick_gelu else 0
-        flags |= FLAG_OUT_ALL_TOKENS if cfg.out_all_tokens else 0
-        flags |= FLAG_TANH_GELU if cfg.tanh_gelu else 0
-        flags |= 0 if cfg.cls_token else FLAG_NO_CLS
-        flags |= {1: 0, 2: FLAG_ACT_TERMS2, 3: FLAG_ACT_TERMS3}[getattr(self, "_act_terms", 1)]
-        nrun = cfg.depth if cfg.n_blocks_run < 0 else cfg.n_blocks_run
-        self.desc = VitDesc(cfg.dim, cfg.depth, cfg.heads, cfg.mlp_dim, cfg.patch, cfg.img_h, cfg.img_w, cfg.n_tokens,
-                            cfg.patch_k_pad, flags, nrun, cfg.out_dim, cfg.ln_eps, cfg.n_registers)
+        self.W = VitWeights()
+        self._upload(self.W, top.items())
+        for l in range(cfg.depth):          # packed and uploaded operand by operand: the host never holds more than one's fp32 temporaries
+            self._upload(self.W.layers[l], pack_layer(cfg, weights, l, terms[l], lo_launch[l], self.fold_layerscale))
+        self._act_terms = self.act_terms    # the attribute's earlier name, which callers still read
+        self.desc = make_desc(cfg, self.act_terms)
         self.recipe = pp.recipe_for(cfg.recipe, cfg.img_h, cfg.img_w)
-        self._ws = None
+        self._ws = Workspace(self.device)
+        self._streams = []
         self._plan_cache = {}
+
+    def _upload(self, struct, fields):
+        for name, v in fields:
+            if not isinstance(v, int):
+                t = torch.from_numpy(np.ascontiguousarray(v[1], dtype=np.float32)).to(self.device)
+                self._keep.append(t.to(torch.float16).contiguous() if v[0] == F16 else t)
+                v = self._keep[-1].data_ptr()
+            setattr(struct, name, v)
 
     # ---- preprocessing -------------------------------------------------------------------------
     def preprocess(self, crops, want_u8=False):
         """crops: list of HxWx3 uint8 numpy arrays (RGB as the detector hands them over), or a single
         uint8 device/host tensor (N, H, W, 3) of equally sized crops.  Returns fp16 patch matrix (device)."""
         r = self.recipe
-        if isinstance(crops, PackedCrops):
-            shapes, src = crops.shapes, crops.src.to(self.device)
-        elif isinstance(crops, torch.Tensor):
+        if isinstance(crops, torch.Tensor):
             n, h, w, _ = crops.shape
             shapes = [(h, w)] * n
             src = crops.to(self.device).contiguous().view(-1)
         else:
-            shapes = [c.shape[:2] for c in crops]
-            src = torch.from_numpy(np.concatenate([np.ascontiguousarray(c, dtype=np.uint8).reshape(-1) for c in crops]))
-            src = src.to(self.device)
+            if not isinstance(crops, PackedCrops):
+                crops = PackedCrops(crops, self.device)
+            shapes, src = crops.shapes, crops.src.to(self.device)
         key = tuple(shapes) if len(set(shapes)) > 1 else (shapes[0], len(shapes))
         plan = self._plan_cache.get(key)
         if plan is None:
@@ -567,16 +634,9 @@ class VitEncoder:
         P = self.cfg.n_patches
         assert patches.dtype == torch.float16 and patches.is_cuda and patches.shape[1] == self.cfg.patch_k_pad
         batch = patches.shape[0] // P
-        ws_bytes = _lib.lib.ibl_vit_workspace_bytes(C.byref(self.desc), batch)
-        if not hasattr(self, "_ws_lanes"):
-            self._ws_lanes = {}
-        ws = self._ws_lanes.get(lane)
-        if ws is None or ws.numel() < ws_bytes:
-            ws = self._ws_lanes[lane] = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-        if self.cfg.out_all_tokens:
-            out = torch.empty((batch, self.cfg.n_tokens, self.cfg.dim), dtype=torch.float32, device=self.device)
-        else:
-            out = torch.empty((batch, self.cfg.out_dim), dtype=torch.float32, device=self.device)
+        ws = self._ws.get(lane, _lib.lib.ibl_vit_workspace_bytes(C.byref(self.desc), batch))
+        shape = (batch, self.cfg.n_tokens, self.cfg.dim) if self.cfg.out_all_tokens else (batch, self.cfg.out_dim)
+        out = torch.empty(shape, dtype=torch.float32, device=self.device)
         st = _lib.lib.ibl_vit_forward(C.byref(self.desc), C.byref(self.W), patches.data_ptr(), batch, out.data_ptr(),
                                       ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
         _lib.check(st, "ibl_vit_forward")
@@ -588,23 +648,13 @@ class VitEncoder:
         of `terms` column blocks is at [i * terms * dim, (i + 1) * terms * dim) of the flattened view; qkv fp16 (B, T, 3 * dim); att fp16
         (B * T, at * dim) and hid fp16 (B * T, at * mlp_dim), flat in the same way, at = the workspace's term flag; fin fp16 (B, dim).
         The next forward on the lane overwrites them."""
-        ws = self._ws_lanes[lane]
         c = self.cfg
         offs = (C.c_int64 * len(WS_TAPS))()
         _lib.check(_lib.lib.ibl_vit_workspace_layout(C.byref(self.desc), batch, offs, len(WS_TAPS)), "ibl_vit_workspace_layout")
-        at = getattr(self, "_act_terms", 1)
-        R = batch * c.n_tokens
-        shapes = {"x": (torch.float32, (batch, c.n_tokens, c.dim)), "xn": (torch.float16, (R, 3 * c.dim)),
-                  "qkv": (torch.float16, (batch, c.n_tokens, 3 * c.dim)), "att": (torch.float16, (R, at * c.dim)),
-                  "hid": (torch.float16, (R, at * c.mlp_dim)), "fin": (torch.float16, (batch, c.dim))}
-        base = (-ws.data_ptr()) % 256
-        out = {}
-        for name, off in zip(WS_TAPS, offs):
-            dtype, shape = shapes[name]
-            n = int(np.prod(shape)) * (4 if dtype == torch.float32 else 2)
-            assert base + off + n <= ws.numel()
-            out[name] = ws[base + off:base + off + n].view(dtype).view(shape)
-        return out
+        at, R, f16, f32 = self.act_terms, batch * c.n_tokens, torch.float16, torch.float32
+        return self._ws.views(lane, offs, [("x", f32, (batch, c.n_tokens, c.dim)), ("xn", f16, (R, 3 * c.dim)),
+                                           ("qkv", f16, (batch, c.n_tokens, 3 * c.dim)), ("att", f16, (R, at * c.dim)),
+                                           ("hid", f16, (R, at * c.mlp_dim)), ("fin", f16, (batch, c.dim))])
 
     def patches_from_pixels(self, x: torch.Tensor) -> torch.Tensor:
         """(B, 3, H, W) float model input (already normalised) -> fp16 patch matrix.  Data-layout plumbing
@@ -631,7 +681,7 @@ class VitEncoder:
         if n == 0:
             return torch.empty((0, self.cfg.out_dim), dtype=torch.float32, device=self.device)
         if streams > 1 and min_split <= n <= max_batch:
-            if not hasattr(self, "_streams") or len(self._streams) != streams:
+            if len(self._streams) != streams:
                 self._streams = [torch.cuda.Stream(device=self.device) for _ in range(streams)]
             cur = torch.cuda.current_stream(self.device)
             bounds = [n * k // streams for k in range(streams + 1)]
@@ -645,10 +695,7 @@ class VitEncoder:
             for o in outs:
                 o.record_stream(cur)
             return torch.cat(outs, dim=0)
-        outs = []
-        for i in range(0, n, max_batch):
-            outs.append(self.forward_patches(self.preprocess(crops[i:i + max_batch]), lane=lane))
-        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        return embed_chunks(n, max_batch, lambda sl: self.forward_patches(self.preprocess(crops[sl]), lane=lane))
 
 
 LINEAR_F16, LINEAR_GELU_F16, LINEAR_RESID_F32, LINEAR_F32 = 0, 1, 2, 4
@@ -692,11 +739,12 @@ def linear_f16(x: torch.Tensor, W: torch.Tensor, bias=None, epilogue=LINEAR_F16,
 
 
 def linear_f16_ex(x: torch.Tensor, W: torch.Tensor, out: torch.Tensor, epilogue, bias=None, scale=None, pos=None, alpha=1.0,
-                  accumulate=False, tokens_per_crop=0, patches_per_crop=0, activation=ACT_GELU_ERF) -> torch.Tensor:
+                  accumulate=False, tokens_per_crop=0, patches_per_crop=0, activation=ACT_GELU_ERF, _call_activation=None) -> torch.Tensor:
     """`ibl_linear_f16_ex`: the encoder's GEMM with any of its eight epilogues, written into `out` (include/ibloc.h says what each one
     computes; `activation` = ACT_QUICK_GELU makes the three GELU epilogues apply x * sigmoid(1.702 x)).  x (rows, n_in) fp16, W (n_out, n_in) fp16, `out` fp16 (rows, terms * n_out) for LINEAR_F16 / _GELU_F16 / _GELU_F16_X2 /
     _X3, else fp32 (rows, n_out) -- for LINEAR_PATCH_F32 fp32 (rows / patches_per_crop * tokens_per_crop, n_out), the token rows.  All
-    three may be row-strided views.  Only the dtypes and the devices are checked here: what the library cannot run it refuses (IblError)."""
+    three may be row-strided views.  Only the dtypes and the devices are checked here: what the library cannot run it refuses (IblError).
+    (_call_activation: `linear_f16_act`'s form of the call, which shares this body)"""
     for t in (x, W, out):
         assert t.is_cuda and t.dim() == 2 and t.stride(1) == 1
     assert x.dtype == torch.float16 and W.dtype == torch.float16
@@ -707,7 +755,11 @@ def linear_f16_ex(x: torch.Tensor, W: torch.Tensor, out: torch.Tensor, epilogue,
                    scale.data_ptr() if scale is not None else None, pos.data_ptr() if pos is not None else None, out.data_ptr(),
                    out.stride(0), x.shape[0], W.shape[0], x.shape[1], int(epilogue), int(accumulate), int(tokens_per_crop),
                    int(patches_per_crop), float(alpha), int(activation))
-    _lib.check(_lib.lib.ibl_linear_f16_ex(C.byref(d), torch.cuda.current_stream().cuda_stream), "ibl_linear_f16_ex")
+    stream = torch.cuda.current_stream().cuda_stream
+    if _call_activation is None:
+        _lib.check(_lib.lib.ibl_linear_f16_ex(C.byref(d), stream), "ibl_linear_f16_ex")
+    else:
+        _lib.check(_lib.lib.ibl_linear_f16_act(C.byref(d), int(_call_activation), stream), "ibl_linear_f16_act")
     return out
 
 
@@ -715,33 +767,23 @@ def linear_f16_act(x: torch.Tensor, W: torch.Tensor, out: torch.Tensor, epilogue
                    accumulate=False, tokens_per_crop=0, patches_per_crop=0) -> torch.Tensor:
     """`ibl_linear_f16_act`: `linear_f16_ex` with the activation as an argument of the call -- ACT_GELU_ERF, ACT_QUICK_GELU or
     ACT_GELU_TANH (the tanh form of GELU, SigLIP's); the descriptor's own activation field stays 0.  Everything else as `linear_f16_ex`."""
-    for t in (x, W, out):
-        assert t.is_cuda and t.dim() == 2 and t.stride(1) == 1
-    assert x.dtype == torch.float16 and W.dtype == torch.float16
-    assert out.dtype == (torch.float16 if epilogue in (LINEAR_F16, LINEAR_GELU_F16, LINEAR_GELU_F16_X2, LINEAR_GELU_F16_X3) else torch.float32)
-    for t in (bias, scale, pos):
-        assert t is None or (t.dtype == torch.float32 and t.is_cuda and t.is_contiguous())
-    d = LinearDesc(x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), bias.data_ptr() if bias is not None else None,
-                   scale.data_ptr() if scale is not None else None, pos.data_ptr() if pos is not None else None, out.data_ptr(),
-                   out.stride(0), x.shape[0], W.shape[0], x.shape[1], int(epilogue), int(accumulate), int(tokens_per_crop),
-                   int(patches_per_crop), float(alpha), 0)
-    _lib.check(_lib.lib.ibl_linear_f16_act(C.byref(d), int(activation), torch.cuda.current_stream().cuda_stream), "ibl_linear_f16_act")
-    return out
+    return linear_f16_ex(x, W, out, epilogue, bias, scale, pos, alpha, accumulate, tokens_per_crop, patches_per_crop, 0, activation)
 
 
-def attention_f16(qkv: torch.Tensor, heads: int, cls_only: bool = False, terms: int = 1, out=None) -> torch.Tensor:
+def attention_f16(qkv: torch.Tensor, heads: int, cls_only: bool = False, terms: int = 1, out=None, _symbol="ibl_attention_f16") -> torch.Tensor:
     """softmax(q k^T / 8) v per (crop, head) through `ibl_attention_f16` (the encoder's attention kernel on its own).
     qkv (batch, n_tokens, 3 * dim) fp16 = [q | k | v]; returns (batch, n_tokens, terms * dim) fp16.  With `cls_only` only row 0 of
     every crop is written, so pass `out` unless the other rows may stay uninitialised.  Shapes the kernel cannot run
-    (dim != 64 * heads, n_tokens > 272, terms outside 1..3) are refused by the library: IblError."""
+    (dim != 64 * heads, n_tokens > 272, terms outside 1..3) are refused by the library: IblError.
+    (_symbol: `attention_stream_f16` shares this body)"""
     assert qkv.dtype == torch.float16 and qkv.is_cuda and qkv.dim() == 3 and qkv.is_contiguous() and qkv.shape[2] % 3 == 0
     batch, n_tokens, dim = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
     if out is None:
         out = torch.empty((batch, n_tokens, max(int(terms), 0) * dim), device=qkv.device, dtype=torch.float16)
     assert out.dtype == torch.float16 and out.is_cuda and out.is_contiguous() and out.shape == (batch, n_tokens, terms * dim)
-    st = _lib.lib.ibl_attention_f16(qkv.data_ptr(), out.data_ptr(), batch, n_tokens, dim, heads, int(cls_only), terms,
-                                     torch.cuda.current_stream().cuda_stream)
-    _lib.check(st, "ibl_attention_f16")
+    st = getattr(_lib.lib, _symbol)(qkv.data_ptr(), out.data_ptr(), batch, n_tokens, dim, heads, int(cls_only), terms,
+                                    torch.cuda.current_stream().cuda_stream)
+    _lib.check(st, _symbol)
     return out
 
 
@@ -749,15 +791,7 @@ def attention_stream_f16(qkv: torch.Tensor, heads: int, cls_only: bool = False, 
     """softmax(q k^T / 8) v per (crop, head) through `ibl_attention_stream_f16`: the kernel the encoder runs beyond 272 tokens (keys and
     values stream through LDS under an fp32 online softmax), on its own.  Arguments and result as for `attention_f16`; n_tokens may be
     anything up to 8192, short rows included.  Shapes the kernel cannot run are refused by the library: IblError."""
-    assert qkv.dtype == torch.float16 and qkv.is_cuda and qkv.dim() == 3 and qkv.is_contiguous() and qkv.shape[2] % 3 == 0
-    batch, n_tokens, dim = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
-    if out is None:
-        out = torch.empty((batch, n_tokens, max(int(terms), 0) * dim), device=qkv.device, dtype=torch.float16)
-    assert out.dtype == torch.float16 and out.is_cuda and out.is_contiguous() and out.shape == (batch, n_tokens, terms * dim)
-    st = _lib.lib.ibl_attention_stream_f16(qkv.data_ptr(), out.data_ptr(), batch, n_tokens, dim, heads, int(cls_only), terms,
-                                            torch.cuda.current_stream().cuda_stream)
-    _lib.check(st, "ibl_attention_stream_f16")
-    return out
+    return attention_f16(qkv, heads, cls_only, terms, out, _symbol="ibl_attention_stream_f16")
 
 
 def rope_f16(qkv: torch.Tensor, table: torch.Tensor, heads: int, n_prefix: int, k_only: bool = False) -> torch.Tensor:
