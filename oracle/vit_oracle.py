@@ -65,21 +65,34 @@ def interpolate_pos(pos: torch.Tensor, stored_grid, grid, mode: str) -> torch.Te
 
 
 @torch.no_grad()
-def vit_forward(weights: dict, cfg, pixel_values: np.ndarray, all_tokens=False, device="cpu") -> np.ndarray:
-    """pixel_values (B, 3, H, W) float32 -> (B, out_dim) float32 (or (B, T, D) when all_tokens).
+def vit_forward(weights: dict, cfg, pixel_values: np.ndarray, all_tokens=False, device="cpu", dtype=torch.float32) -> np.ndarray:
+    """pixel_values (B, 3, H, W) float32 -> (B, out_dim) `dtype` (or (B, T, D) when all_tokens).
     cfg is an ibloc_amd.vit.VitConfig (plain data).  device: where torch evaluates this fp32 restatement ("cuda" lets the parity
-    tests embed tens of thousands of crops; gfx950 has no reduced-precision fp32 matmul mode, the arithmetic stays fp32)."""
+    tests embed tens of thousands of crops; gfx950 has no reduced-precision fp32 matmul mode, the arithmetic stays fp32).
+    dtype: torch.float64 evaluates the same arithmetic on the fp32 weights and pixels in double (the reference of the precision tests).
+    Without a class token (cfg.cls_token False) the position table is used as stored and there is no class row to return: all_tokens."""
     F = torch.nn.functional
-    w = {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v, dtype=np.float32))).to(device) for k, v in weights.items()}
+    w = {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v, dtype=np.float32))).to(device=device, dtype=dtype)
+         for k, v in weights.items()}
     if isinstance(pixel_values, torch.Tensor):       # already a float32 tensor (the parity tests normalise u8 crops on the device)
-        x = pixel_values.to(device=device, dtype=torch.float32)
+        x = pixel_values.to(device=device, dtype=dtype)
     else:
-        x = torch.from_numpy(np.asarray(pixel_values, dtype=np.float32)).to(device)
+        x = torch.from_numpy(np.asarray(pixel_values, dtype=np.float32)).to(device=device, dtype=dtype)
+    if cfg.quick_gelu:                               # x * sigmoid(1.702 x) (OpenAI CLIP)
+        act = lambda t: t * torch.sigmoid(1.702 * t)
+    elif cfg.tanh_gelu:                              # gelu_pytorch_tanh (SigLIP)
+        act = lambda t: F.gelu(t, approximate="tanh")
+    else:
+        act = F.gelu
     B = x.shape[0]
     x = F.conv2d(x, w["patch.w"], w.get("patch.b"), stride=cfg.patch)           # (B, D, gh, gw)
     x = x.flatten(2).transpose(1, 2)
-    x = torch.cat([w["cls"].reshape(1, 1, -1).expand(B, -1, -1), x], dim=1)
-    x = x + interpolate_pos(w["pos"], cfg.pos_grid, cfg.grid, cfg.pos_interp).unsqueeze(0)
+    if cfg.cls_token:
+        x = torch.cat([w["cls"].reshape(1, 1, -1).expand(B, -1, -1), x], dim=1)
+        x = x + interpolate_pos(w["pos"], cfg.pos_grid, cfg.grid, cfg.pos_interp).unsqueeze(0)
+    else:
+        assert all_tokens and tuple(cfg.pos_grid) == tuple(cfg.grid), "no class token: every token is returned, the table is the run grid's"
+        x = x + w["pos"].unsqueeze(0)
     if cfg.pre_ln:
         x = F.layer_norm(x, (cfg.dim,), w["ln_pre.g"], w["ln_pre.b"], cfg.ln_eps)
     hd = cfg.dim // cfg.heads
@@ -96,7 +109,7 @@ def vit_forward(weights: dict, cfg, pixel_values: np.ndarray, all_tokens=False, 
             a = a * w[p + "ls1"]
         x = x + a
         h = F.layer_norm(x, (cfg.dim,), w[p + "ln2.g"], w[p + "ln2.b"], cfg.ln_eps)
-        h = F.linear(F.gelu(F.linear(h, w[p + "fc1.w"], w[p + "fc1.b"])), w[p + "fc2.w"], w[p + "fc2.b"])
+        h = F.linear(act(F.linear(h, w[p + "fc1.w"], w[p + "fc1.b"])), w[p + "fc2.w"], w[p + "fc2.b"])
         if cfg.layerscale:
             h = h * w[p + "ls2"]
         x = x + h

@@ -5,11 +5,13 @@ tests/test_vit_stream_model.py shows on the CPU that they refuse a chain with on
 
 Worst error / bound and worst share of fp16 elements not bit-equal to the emulation per stage, over the whole file, on an MI355X
 (`test_zz_worst_ratios`, run with -s; "cls_" = the stages of a CLS-only block):
-    patch 0.044            qkv 0.930 / 1.74 %     att 0.564 / 0.35 %     ln2 0.988 / 0.11 %     hid 0.908 / 0.09 %     resid 0.073
+    patch 0.044            qkv 0.930 / 1.74 %     att 0.564 / 0.07 %     ln2 0.988 / 0.11 %     hid 0.908 / 0.09 %     resid 0.073
     out_ln 0.095           cls_ln1 0.995 / 0.04 % cls_qkv 0.934 / 0.26 % cls_att 0.564 / 0.26 % cls_ln2 0.977 / 0.52 % cls_hid 0.889 / 0.13 %
     cls_resid 0.044        cls_out_ln 0.070       cls_proj_ln 0.991 / 0 % cls_out_proj 0.021
 The class rows of a CLS-only block are bit-identical to row 0 of an all-token run whose block is plain, in every family, plan and
-block: the comment in ibl_vit_forward holds.  Every stage of every plan met its bound and the cap: no operand term is dead.
+block: the comment in ibl_vit_forward holds.  (att: 0.35 % before `att_undetermined` of vit_stream_cases took the outputs that one
+softmax weight on an fp16 rounding boundary decides out of the share.)  Every stage of every plan met its bound and the cap: no operand
+term is dead.
 qkv is the one stage whose share is not a few tenths of a percent (dino, default plan, block 1: 1.74 %; dino plain, block 2: 1.34 %;
 every other case under 0.8 %), and the cause is known: its operand, LayerNorm 1, is not kept by the device and is emulated here, so where
 the device's LayerNorm (v_rsq_f32, the compiler's choice of fused multiply-adds) rounds ONE element of a one-term row to the other fp16
@@ -42,7 +44,7 @@ def model(cfg):
 
 def run(cfg, n_run, all_tokens, final_ln=False, proj=False, plan=None):
     """one forward -> (encoder's model, out numpy, taps as torch views)"""
-    family, plan0, kext, fold = cfg
+    family, plan0, kext, fold = cfg[:4]       # (a fifth entry is the weights' kind: tests/test_gpu_vit_trained.py)
     m = model(cfg)
     c = SCS.run_cfg(family, n_run, all_tokens, final_ln=final_ln, proj=proj)
     with pytest.MonkeyPatch.context() as mp:

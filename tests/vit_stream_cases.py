@@ -21,6 +21,17 @@ Two allowances that the kernel tests do not need, both first order and derived, 
   * `flip_allowance`: where a stage's GEMM operand is itself emulated here (LayerNorm 1 is not kept by the device), an element of it whose
     fp32 value lies within the LayerNorm's own fp32 bound of an fp16 rounding boundary may have been rounded the other way by the device;
     the GEMM bound grows by |W'| times one fp16 step of exactly those elements.
+  * `att_undetermined`: the attention kernel rounds every softmax weight p to fp16 before the PV product.  A p whose fp32 value lies
+    within what a correct fp32 implementation may differ by -- one ulp of exp2, the order of the 64-term score sums of p and of the
+    row's maximum, in the root mean square as in `check32` -- of an fp16 rounding boundary may be rounded the other way by the device;
+    the 64 outputs of that (crop, head, query) row then move by one fp16 step of that p times |v| / sum p, and those of them that lie
+    within that distance of their own rounding boundary need not EQUAL the emulation.  They stay out of the unequal share (the bound
+    holds them as it holds every element).  The score sums of numpy in three orders measure 0.2 .. 0.5 of 2^-24 sum |q_i k_i| in the
+    root mean square and 3.9 of it at most, against the sqrt(66) assumed.  1 .. 7 % of an all-token buffer are excused on these cases
+    (up to 25 % of one CLS-only buffer of 384), so the cap asks what it asked of the other 93 % and more.  Why it is needed: ONE dominant
+    p rounded the other way moves its row's 64 outputs by a third of a step, and among the 3 x 2 x 17 weights of a CLS-only block that
+    is 6 % of its 384 outputs (met on the MI355X: clip, heavy-tailed matrices, block 1; within 0.28 of the bound), which a cap of 2 % of
+    so small a buffer cannot hold.
   * `ln_lipschitz`: where a LayerNorm's input is itself a reference value with a bound d (the residual after the output projection is
     overwritten before the call returns), the output moves by at most rstd |g_i| (d_i + mean d + |xhat_i| sqrt(mean d^2)).
 
@@ -63,12 +74,16 @@ EXTRA = [(f, "p2;*:2222", kext, fold) for f in ("dino", "vit") for kext, fold in
 
 
 @functools.lru_cache(maxsize=None)
-def inputs(family):
-    """-> (cfg, weights, pixels (BATCH, 3, H, W) fp32)"""
+def inputs(family, kind="random"):
+    """-> (cfg, weights, pixels (BATCH, 3, H, W) fp32).  kind: "random" = `random_weights` as they are, else those weights with the
+    trained-like statistics of that name (tests/vit_trained_cases.py)"""
     cfg = FAMILIES[family]
     w = V.random_weights(cfg, WSEED + list(FAMILIES).index(family))
     if family == "clip":
         del w["patch.b"]                 # the null-bias path of the patch GEMM
+    if kind != "random":
+        from tests import vit_trained_cases as TC
+        w = TC.trained_like(cfg, w, TC.SEED + list(FAMILIES).index(family), kind)
     px = np.random.default_rng(ISEED + list(FAMILIES).index(family)).normal(size=(BATCH, 3, cfg.img_h, cfg.img_w)).astype(np.float32)
     return cfg, w, px
 
@@ -125,9 +140,9 @@ def a_terms(a16, value32, terms, split):
 class Model:
     """What one encoder (family, plan, kext, fold) should hand its kernels.  mutant: a name of MUTANTS, applied where it says."""
 
-    def __init__(self, family, plan, kext=True, fold=False):
-        self.family, self.plan, self.kext, self.fold = family, plan, kext, fold
-        self.cfg, self.w, self.px = inputs(family)
+    def __init__(self, family, plan, kext=True, fold=False, kind="random"):
+        self.family, self.plan, self.kext, self.fold, self.kind = family, plan, kext, fold, kind
+        self.cfg, self.w, self.px = inputs(family, kind)
         c = self.cfg
         self.patch_terms, self.layer_terms = V.parse_precision(plan)
         self.D, self.T, self.P, self.H, self.MLP = c.dim, c.n_tokens, c.n_patches, c.heads, c.mlp_dim
@@ -252,6 +267,27 @@ def flip_allowance(value32, ln_bnd, w16):
     dist = step / 2 - np.abs(v - a)                       # distance of the value from the nearest rounding boundary
     may = (dist <= 2 * ln_bnd) * step
     return may @ np.abs(w16.astype(np.float64)).T
+
+
+def att_undetermined(q, k, v, value32):
+    """see the module docstring: q (B, H, Tq, 64), k, v (B, H, T, 64) fp16, value32 (B, H, Tq, 64) the emulation's fp32 outputs ->
+    bool (B, H, Tq, 64), True where the device's fp16 output need not equal the emulation's"""
+    q64, k64, v64 = (a.astype(np.float64) for a in (q, k, v))
+    c2 = 0.125 * 1.4426950408889634
+    s = np.einsum("bhqd,bhkd->bhqk", q64, k64)
+    s_abs = np.einsum("bhqd,bhkd->bhqk", np.abs(q64), np.abs(k64))
+    top = np.take_along_axis(s_abs, s.argmax(axis=-1)[..., None], axis=-1)             # the sum of |products| of the row's maximum
+    ds = np.sqrt(AC.HD + 2.0) * 2.0 ** -24 * (s_abs + top)
+    p = np.exp2((s - s.max(axis=-1, keepdims=True)) * c2)
+    dp = p * (2.0 ** -23 + np.log(2.0) * c2 * ds)
+    p16 = f16(p.astype(np.float32)).astype(np.float64)
+    step = LC.ulp16(p)
+    flag = (step / 2 - np.abs(p - p16) <= dp) * step                                   # one fp16 step of exactly those p
+    move = np.einsum("bhqk,bhkd->bhqd", flag, np.abs(v64)) / p.sum(axis=-1, keepdims=True)
+    val = value32.astype(np.float64)
+    ostep = LC.ulp16(val)
+    dist = ostep / 2 - np.abs(val - f16(value32).astype(np.float64))
+    return (move > 0) & (dist <= move + 4 * 2.0 ** -24 * np.abs(val))
 
 
 def ln_lipschitz(x64, g, eps, d):
@@ -420,11 +456,12 @@ def stage_att(m, l, qkv, acc=np.float64, mutant=None, cls_only=False):
     else:
         a16, value = AC.emulate(q, k, v)
     rows = lambda x: np.ascontiguousarray(x.transpose(0, 2, 1, 3)).reshape(-1, D)
+    may = rows(att_undetermined(q, k, v, value))
     a16, value = rows(a16), rows(value)
     emu = a_terms(a16, value, ot, AC.split_terms)
     if mutant == "swap23":
         emu = swap23(emu, ot, D)
-    return dict(emu=emu, ref=rows(ref), bnd=rows(bnd), terms=ot, lo_bnd=rows(AC.bound(ref, A, v, out_rel=2.0 ** -21)))
+    return dict(emu=emu, ref=rows(ref), bnd=rows(bnd), terms=ot, lo_bnd=rows(AC.bound(ref, A, v, out_rel=2.0 ** -21)), may=may)
 
 
 def resid_o(m, l, x_prev, att, acc, mutant=None, cls_only=False):
@@ -579,31 +616,31 @@ def block_checks(m, l, x_prev, dev, mutant=None, cls_only=False, acc=np.float64,
     return out
 
 
-def stand_in(m, l, x_prev, cls_only=False):
+def stand_in(m, l, x_prev, cls_only=False, acc=np.float32):
     """What a device that accumulates in fp32, in numpy's order, would leave of block l: the `dev` of `block_checks`, each stage from the
-    stand-in's own previous one"""
-    f32, D, T = np.float32, m.D, m.T
+    stand-in's own previous one.  (acc = np.float64: the emulation itself chained, what the design gives without accumulation error)"""
+    D, T = m.D, m.T
     dev = {}
     if not cls_only:
-        dev["qkv"] = stage_qkv(m, l, x_prev, f32)["emu"].reshape(BATCH, T, 3 * D)
-        dev["att"] = stage_att(m, l, dev["qkv"], f32)["emu"]
-        dev["xn"] = stage_ln2(m, l, x_prev, dev["att"], f32)["emu"]
-        dev["hid"] = stage_hid(m, l, dev["xn"], f32)["emu"]
-        dev["x"] = stage_resid(m, l, x_prev, dev["att"], dev["hid"], f32)["emu"]
+        dev["qkv"] = stage_qkv(m, l, x_prev, acc)["emu"].reshape(BATCH, T, 3 * D)
+        dev["att"] = stage_att(m, l, dev["qkv"], acc)["emu"]
+        dev["xn"] = stage_ln2(m, l, x_prev, dev["att"], acc)["emu"]
+        dev["hid"] = stage_hid(m, l, dev["xn"], acc)["emu"]
+        dev["x"] = stage_resid(m, l, x_prev, dev["att"], dev["hid"], acc)["emu"]
         return dev
     dev["xn"] = stage_ln1_cls(m, l, x_prev)["emu"]
-    kv, q = stage_qkv_cls(m, l, dev["xn"], f32)
+    kv, q = stage_qkv_cls(m, l, dev["xn"], acc)
     qkv = np.zeros((BATCH * T, 3 * D), np.float16)
     qkv[:, D:], qkv[::T, :D] = kv["emu"], q["emu"]
     dev["qkv"] = qkv.reshape(BATCH, T, 3 * D)
     att = np.zeros((BATCH * T, D), np.float16)
-    att[::T] = stage_att(m, l, dev["qkv"], f32, cls_only=True)["emu"]
+    att[::T] = stage_att(m, l, dev["qkv"], acc, cls_only=True)["emu"]
     dev["att"] = att
     xc = np.ascontiguousarray(x_prev[::T])
-    dev["fin"] = stage_ln2(m, l, xc, att[::T], f32, cls_only=True)["emu"]
-    dev["hid"] = stage_hid(m, l, dev["fin"], f32, cls_only=True)["emu"]
+    dev["fin"] = stage_ln2(m, l, xc, att[::T], acc, cls_only=True)["emu"]
+    dev["hid"] = stage_hid(m, l, dev["fin"], acc, cls_only=True)["emu"]
     x = x_prev.copy()
-    x[::T] = stage_resid(m, l, xc, att[::T], dev["hid"], f32, cls_only=True)["emu"]
+    x[::T] = stage_resid(m, l, xc, att[::T], dev["hid"], acc, cls_only=True)["emu"]
     dev["x"] = x
     return dev
 
@@ -629,7 +666,10 @@ def check16(stage, got, st, K):
     cols = np.ones(got.shape[1], bool)
     if terms == 3:
         cols[K:2 * K] = False
-    share = float((got.view(np.uint16) != emu.view(np.uint16))[:, cols].mean())
+    neq = got.view(np.uint16) != emu.view(np.uint16)
+    if "may" in st:                         # `att_undetermined`: elements that need not equal the emulation (and their a / S)
+        neq &= ~np.tile(st["may"], (1, got.shape[1] // K))
+    share = float(neq[:, cols].mean())
     g64 = got.astype(np.float64)
     ok = bool(np.isfinite(g64).all())
     ratio = float((np.abs(g64[:, :K] - st["ref"]) / st["bnd"]).max())
