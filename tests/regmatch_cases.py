@@ -108,7 +108,8 @@ def operand_rows(stored, norm):
 # ------------------------------------------------------------------------------------------------
 def inject(feat, rows_list):
     """overwrites fpfh (rows in matching order), fpfh_norm and, for the resident form, fpfh_split of an InstanceFeatures object made by
-    instance_features_batch; its normals, gradients and bbox stay the real ones (ICP runs behind RANSAC, the planner reads bbox)"""
+    instance_features_batch; its normals, gradients and bbox stay the computed ones unless `inject_geometry` overwrites them too (the
+    coloured ICP behind RANSAC reads normals and gradients, the planner reads bbox)"""
     import torch
     rows = np.concatenate([np.asarray(r, np.float32).reshape(-1, 33) for r in rows_list]) if rows_list else np.zeros((0, 33), np.float32)
     assert len(rows) == feat.n
@@ -121,6 +122,20 @@ def inject(feat, rows_list):
     feat.fpfh_norm[:feat.n].copy_(torch.from_numpy(norm).to(dev))
     if feat.fpfh_split is not None:
         feat.fpfh_split[:feat.n].copy_(torch.from_numpy(operand_rows(st, norm).view(np.int16)).to(dev).view(torch.float16))
+    return feat
+
+
+def inject_geometry(feat, nrm_list, grad_list):
+    """overwrites the x, y, z lanes of the normals and colour gradients of an InstanceFeatures object made by instance_features_batch
+    with grad_radius > 0 (one (n, 3) array per instance): what the coloured ICP reads of its target side (tests/icp_colour_cases.py).
+    The w lanes stay as computed."""
+    import torch
+    if feat.n == 0:
+        return feat
+    for dst, rows_list in ((feat.normals, nrm_list), (feat.grad, grad_list)):
+        rows = np.concatenate([np.asarray(r, np.float32).reshape(-1, 3) for r in rows_list])
+        assert len(rows) == feat.n
+        dst[:feat.n, :3].copy_(torch.from_numpy(rows).to(dst.device))
     return feat
 
 

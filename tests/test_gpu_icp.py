@@ -22,6 +22,8 @@ centred     center=True: the means and the centred clouds                       
 coloured    the coloured estimator (geometric + photometric rows, 6 x 6 solve), wrong assignments that run
             all 30 iterations in the grouped search (the correct jobs stop after 4 to 8 iterations: only the
             three wrong assignments take this estimator past iteration 8)                                        5.6e-16, 0, 0
+            (its edges -- strides of the moments loop, the strided active list, pieces, photometric rows,
+            refused singular systems, ties, few points -- on injected fields: tests/test_gpu_icp_colour.py)
 """
 import numpy as np
 import pytest
