@@ -174,6 +174,25 @@ int ibl_preprocess_crops(const uint8_t* src, const ibl_crop_desc* descs, int n_c
                          uint8_t* tmp, int out_h, int out_w, int patch, int patch_k_pad, int swap_rb,
                          const float* mean, const float* stdv, void* patches, uint8_t* out_u8, void* stream);
 
+/* Native-aspect crops: the same preprocessing with a target size and a destination per crop.  Crop b (descs[b]: its tables are those of
+ * an exact resize in_w -> out_w, in_h -> out_h, its scratch [in_h][out_w][3]) is resized to out_h x out_w, normalised and written as
+ * (out_h / patch) * (out_w / patch) rows of the patch matrix from row row0 on -- for ibl_vit_forward_ragged row0 = seq_off[b] +
+ * 1 + n_registers.  The whole matrix, fp16 [patch_rows][patch_k_pad], is cleared first: rows no crop writes (the prefix rows) and the K
+ * padding are zero.  out_u8 (optional): crop b's out_h x out_w x 3 image at byte u8_offset.  The arithmetic per pixel is that of
+ * ibl_preprocess_crops.  rdescs is given twice, [dev] for the kernels and [HOST] for the checks; the caller keeps them equal.
+ * Enqueues on `stream` and synchronises nothing.  Refused (IBL_ERR_ARG) before anything is launched or cleared: null pointers (out_u8
+ * may be NULL), sizes that are not positive multiples of `patch`, row0 (or, with out_u8, u8_offset) that does not ascend past the
+ * previous crop's rows, rows beyond patch_rows, n_crops outside 1..65535. */
+typedef struct {
+    int32_t out_h, out_w;          /* target size in pixels: multiples of the patch size                */
+    int64_t row0;                  /* first row of this crop's patches in the patch matrix              */
+    int64_t u8_offset;             /* byte offset of this crop's image in out_u8                        */
+} ibl_crop_ragged_desc;
+int ibl_preprocess_crops_ragged(const uint8_t* src, const ibl_crop_desc* descs, const ibl_crop_ragged_desc* rdescs_dev,
+                                const ibl_crop_ragged_desc* rdescs_host, int n_crops, int max_in_h, const int32_t* tables,
+                                uint8_t* tmp, int patch, int patch_k_pad, int swap_rb, const float* mean, const float* stdv,
+                                void* patches, int64_t patch_rows, uint8_t* out_u8, void* stream);
+
 /* ViT forward over a batch of crops.  Replaces the batch-1 torch forward of
  * utils/embeddings.py:46,69,93 and dator/model/backbones/vit_pytorch.py:422-443.
  *   patches [dev] fp16 [batch*P][patch_k_pad], P = n_tokens - 1 - n_registers (from ibl_preprocess_crops; P = n_tokens with IBL_VIT_NO_CLS)
@@ -199,6 +218,24 @@ enum { IBL_VIT_WS_X = 0, IBL_VIT_WS_XN, IBL_VIT_WS_QKV, IBL_VIT_WS_ATT, IBL_VIT_
 int ibl_vit_workspace_layout(const ibl_vit_desc* desc, int batch, int64_t* offsets, int n);
 int ibl_vit_forward(const ibl_vit_desc* desc, const ibl_vit_weights* weights, const void* patches, int batch,
                     float* out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The forward over crops with different patch grids (native-aspect crops).  Crop b owns rows seq_off[b] .. seq_off[b + 1] - 1 of every
+ * per-token buffer: 1 + n_registers prefix rows, then its gh * gw patches in row-major order; seq_off int32 [batch + 1] from 0, given
+ * [dev] and [HOST] (kept equal by the caller), total = seq_off[batch].  desc->n_tokens, img_h and img_w are not read.
+ *   patches  [dev] fp16 [total][patch_k_pad]: one row per TOKEN, the prefix rows zero (ibl_preprocess_crops_ragged)
+ *   pos_rows [dev] fp32 [total][dim]: the position row of every token (a crop's table resampled to its grid; the prefix rows are not used)
+ *   out      [dev] fp32 [batch][dim] (class rows), or fp32 [total][dim], packed like the input, with IBL_VIT_OUT_ALL_TOKENS
+ * The launches are those of ibl_vit_forward with Rn = total and the attention of ibl_attention_ragged_f16; the class rows of the last
+ * block are gathered to compact buffers.  A crop's result does not depend on the batch it runs in; a batch of equal grids gives
+ * ibl_vit_forward's bits where that runs the streaming attention (n_tokens > 272).  Enqueues on `stream`, synchronises nothing.
+ * Refused before anything is launched: IBL_ERR_UNSUPPORTED for weights->rope_table (DINOv3), IBL_VIT_NO_CLS (SigLIP), IBL_VIT_PROJ /
+ * IBL_VIT_PRE_LN (CLIP) and the shapes ibl_vit_forward refuses; IBL_ERR_ARG for null or misaligned pointers, batch <= 0 or > 65535,
+ * seq_off[0] != 0, a segment that is descending, has no patch row or exceeds IBL_ATT_STREAM_MAX_TOKENS, term counts the descriptor has
+ * no room for, a workspace below ibl_vit_ragged_workspace_bytes(desc, total, batch) (-1 for arguments it cannot size). */
+int64_t ibl_vit_ragged_workspace_bytes(const ibl_vit_desc* desc, int64_t total_tokens, int batch);
+int ibl_vit_forward_ragged(const ibl_vit_desc* desc, const ibl_vit_weights* weights, const void* patches, const float* pos_rows,
+                           const int32_t* seq_off_dev, const int32_t* seq_off_host, int batch, float* out, void* workspace,
+                           int64_t workspace_bytes, void* stream);
 
 /* One linear layer of the encoder on its own: out = epilogue(x W^T + bias).  The nn.Linear of the reference's
  * encoders (transformers' ViTSelfAttention / ViTIntermediate / ViTOutput called from utils/embeddings.py:46,69,93).
@@ -292,6 +329,17 @@ int ibl_rope_f16(void* qkv, const float* table, int batch, int n_tokens, int n_p
 #define IBL_ATT_STREAM_MAX_TOKENS 8192
 int ibl_attention_stream_f16(const void* qkv, void* out, int batch, int n_tokens, int dim, int heads, int cls_only, int terms,
                              void* stream);
+
+/* The streaming attention over crops of different lengths, packed back to back: crop b owns rows seq_off[b] .. seq_off[b + 1] - 1 of
+ * qkv fp16 [total][3 * dim] and out fp16 [total][terms * dim] (seq_off int32 [batch + 1], given twice: [dev] for the kernel, [HOST] for
+ * the checks and the launch size; the caller keeps them equal).  The arithmetic per crop is ibl_attention_stream_f16's in its order, so
+ * a crop's rows are those of that entry run on the crop alone, bit for bit, whatever its neighbours hold; cls_only 1 writes row
+ * seq_off[b] of every crop only.  Rows outside every segment are neither read nor written.  Enqueues on `stream`, synchronises nothing.
+ * batch 0 returns IBL_OK without a launch.  Refused with a status, nothing launched and out untouched: null or misaligned pointers
+ * (qkv 16, out 8, seq_off 4 bytes), dim != 64 * heads, terms outside 1..3, cls_only outside 0 / 1, batch < 0 or > 65535, seq_off[0] < 0,
+ * an empty or descending segment, a segment longer than IBL_ATT_STREAM_MAX_TOKENS. */
+int ibl_attention_ragged_f16(const void* qkv, void* out, const int32_t* seq_off_dev, const int32_t* seq_off_host, int batch, int dim,
+                             int heads, int cls_only, int terms, void* stream);
 
 /* The encoder's LayerNorm on its own: out[r] = (x[r] - mean) / sqrt(var + eps) * gamma + beta over `dim` columns, biased variance
  * from a second pass over the centred row (torch.nn.LayerNorm as the reference's encoders call it).  The kernel and the launch are

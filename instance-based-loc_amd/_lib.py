@@ -53,6 +53,12 @@ _SIGS = {
     "ibl_attention_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ibl_rope_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "ibl_attention_stream_f16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    # native-aspect crops: per-crop target sizes and ragged row offsets (the offset arrays are given twice, device and host)
+    "ibl_preprocess_crops_ragged": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int64,
+                                              vp, vp]),
+    "ibl_attention_ragged_f16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "ibl_vit_ragged_workspace_bytes": (C.c_int64, [vp, C.c_int64, C.c_int]),
+    "ibl_vit_forward_ragged": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp]),
     "ibl_layernorm_f32": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_float, vp, C.c_int64, C.c_int, vp]),
     "ibl_reg_ctx_create": (C.c_int, [C.POINTER(vp), C.c_int64]),
     "ibl_reg_ctx_destroy": (C.c_int, [vp]),

@@ -1,6 +1,7 @@
 // vit_attention.hip -- the ViT encoder's attention on gfx950 (vit.hip says where it sits in the forward): the rotation of q and k, the
-// resident kernel (up to 272 tokens, K and V^T of a head in LDS) and the streaming one beyond, their launchers, and the entries
-// ibl_attention_f16, ibl_attention_stream_f16 and ibl_rope_f16.
+// resident kernel (up to 272 tokens, K and V^T of a head in LDS), the streaming one beyond and its ragged twin (crops of different
+// lengths packed back to back), their launchers, and the entries ibl_attention_f16, ibl_attention_stream_f16, ibl_attention_ragged_f16
+// and ibl_rope_f16.
 #include <type_traits>
 
 #include "vit_kernels.h"
@@ -237,9 +238,10 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void ibl_attention_kernel(const u16
 #define ATT_S_THREADS 256
 #define ATT_S_KV 128         // keys per chunk
 #define ATT_S_QB 64          // queries per workgroup (16 per wave)
+// The body both streaming kernels share: query block qb of head h of the crop whose T rows start at row tok0 of qkv and out.
 template <int TERMS>
-__global__ __launch_bounds__(ATT_S_THREADS, 3) void ibl_attention_stream_kernel(const u16* __restrict__ qkv, u16* __restrict__ out, int T,
-                                                                                  int D, int heads, float scale, int cls_only) {
+__device__ __forceinline__ void attention_stream_body(const u16* __restrict__ qkv, u16* __restrict__ out, int T, int64_t tok0, int h, int qb,
+                                                      int D, float scale, int cls_only) {
     constexpr int KV = ATT_S_KV, NT = KV / 16, NS = NT / 2;
     constexpr int KROW = 144;               // bytes per K row (64 fp16 + 16 B pad)
     constexpr int VROW = KV * 2 + 16;       // bytes per V^T row
@@ -250,10 +252,6 @@ __global__ __launch_bounds__(ATT_S_THREADS, 3) void ibl_attention_stream_kernel(
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nq = cls_only ? 1 : T;                    // rows that are queries
-    const int nqb = (nq + ATT_S_QB - 1) / ATT_S_QB;     // the query blocks of a (crop, head) are neighbours in the grid: they share K and V in L2
-    const int bh = blockIdx.x / nqb, qb = blockIdx.x % nqb;
-    const int b = bh / heads, h = bh % heads;
-    const int64_t tok0 = (int64_t)b * T;
     const int64_t ld = 3 * (int64_t)D;
     const u16* qbase = qkv + tok0 * ld + h * 64;
     const u16* kbase = qbase + D;
@@ -422,6 +420,29 @@ __global__ __launch_bounds__(ATT_S_THREADS, 3) void ibl_attention_stream_kernel(
     }
 }
 
+// equal rows: crop b's T rows start at row b * T
+template <int TERMS>
+__global__ __launch_bounds__(ATT_S_THREADS, 3) void ibl_attention_stream_kernel(const u16* __restrict__ qkv, u16* __restrict__ out, int T,
+                                                                                  int D, int heads, float scale, int cls_only) {
+    const int nq = cls_only ? 1 : T;
+    const int nqb = (nq + ATT_S_QB - 1) / ATT_S_QB;     // the query blocks of a (crop, head) are neighbours in the grid: they share K and V in L2
+    const int bh = blockIdx.x / nqb, qb = blockIdx.x % nqb;
+    attention_stream_body<TERMS>(qkv, out, T, (int64_t)(bh / heads) * T, bh % heads, qb, D, scale, cls_only);
+}
+
+// ragged rows: crop b's rows are seq_off[b] .. seq_off[b + 1] - 1 of the packed qkv and out.  Grid (query blocks of the longest crop,
+// heads, batch): the query blocks of a (crop, head) stay neighbours.  A workgroup whose query block lies beyond its crop returns before
+// the first barrier -- the whole workgroup does, and the key loop's trip count is the crop's, so every barrier is met by all or by none.
+template <int TERMS>
+__global__ __launch_bounds__(ATT_S_THREADS, 3) void ibl_attention_ragged_kernel(const u16* __restrict__ qkv, u16* __restrict__ out,
+                                                                                  const int* __restrict__ seq_off, int D, float scale,
+                                                                                  int cls_only) {
+    const int b = blockIdx.z, qb = blockIdx.x;
+    const int tok0 = seq_off[b], T = seq_off[b + 1] - tok0;
+    if (qb * ATT_S_QB >= (cls_only ? 1 : T)) return;
+    attention_stream_body<TERMS>(qkv, out, T, tok0, blockIdx.y, qb, D, scale, cls_only);
+}
+
 // terms (1..3; the entries and ibl_vit_forward validate it) -> the kernels' TERMS: f is called with std::integral_constant<int, TERMS>
 template <class F>
 static void with_terms(int terms, F f) {
@@ -442,6 +463,54 @@ static int run_attention_stream(const u16* qkv, u16* out, int B, int T, int D, i
     });
     IBL_LAUNCH_CHECK();
     return IBL_OK;
+}
+
+// seq_off [dev] as ibl_attention_ragged_f16 takes it, max_tokens the longest segment (from the host copy); batch <= 65535 (grid.z)
+int run_attention_ragged(const u16* qkv, u16* out, const int* seq_off, int B, int max_tokens, int D, int heads, int cls_only, hipStream_t s,
+                         int terms) {
+    const float scale = 0.125f;   // 1/sqrt(64)
+    const int nqb = ((cls_only ? 1 : max_tokens) + ATT_S_QB - 1) / ATT_S_QB;
+    dim3 grid((unsigned)nqb, (unsigned)heads, (unsigned)B), block(ATT_S_THREADS);
+    with_terms(terms, [&](auto t) {
+        hipLaunchKernelGGL((ibl_attention_ragged_kernel<decltype(t)::value>), grid, block, 0, s, qkv, out, seq_off, D, scale, cls_only);
+    });
+    IBL_LAUNCH_CHECK();
+    return IBL_OK;
+}
+
+// the row offsets of a ragged batch, on the host: ascending from >= 0, every segment 1 .. IBL_ATT_STREAM_MAX_TOKENS rows, at most 65535
+// segments (grid.z).  *max_tokens: the longest segment
+int ragged_offsets_check(const char* fn, const int32_t* seq_off, int batch, int* max_tokens) {
+    *max_tokens = 0;
+    if (batch > 65535) return ibl_set_error(IBL_ERR_ARG, "%s: batch %d exceeds the grid (65535)", fn, batch);
+    if (seq_off[0] < 0) return ibl_set_error(IBL_ERR_ARG, "%s: seq_off[0] = %d is negative", fn, seq_off[0]);
+    for (int b = 0; b < batch; ++b) {
+        const int64_t n = (int64_t)seq_off[b + 1] - seq_off[b];
+        if (n < 1) return ibl_set_error(IBL_ERR_ARG, "%s: segment %d is empty or descending (%d .. %d)", fn, b, seq_off[b], seq_off[b + 1]);
+        if (n > IBL_ATT_STREAM_MAX_TOKENS)
+            return ibl_set_error(IBL_ERR_UNSUPPORTED, "%s: segment %d has %lld rows > %d", fn, b, (long long)n, IBL_ATT_STREAM_MAX_TOKENS);
+        if (n > *max_tokens) *max_tokens = (int)n;
+    }
+    return IBL_OK;
+}
+
+extern "C" int ibl_attention_ragged_f16(const void* qkv, void* out, const int32_t* seq_off_dev, const int32_t* seq_off_host, int batch,
+                                        int dim, int heads, int cls_only, int terms, void* stream) {
+    const char* fn = "ibl_attention_ragged_f16";
+    if (batch < 0) return ibl_set_error(IBL_ERR_ARG, "%s: negative batch (%d)", fn, batch);
+    if (terms < 1 || terms > 3) return ibl_set_error(IBL_ERR_ARG, "%s: terms %d outside 1..3", fn, terms);
+    if (cls_only != 0 && cls_only != 1) return ibl_set_error(IBL_ERR_ARG, "%s: cls_only must be 0 or 1", fn);
+    if (heads <= 0 || heads > 65535 || dim != heads * 64)
+        return ibl_set_error(IBL_ERR_UNSUPPORTED, "%s: dim (%d) must be 64 * heads (%d): head_dim is 64", fn, dim, heads);
+    if (batch == 0) return IBL_OK;
+    if (!qkv || !out || !seq_off_dev || !seq_off_host) return ibl_set_error(IBL_ERR_ARG, "%s: null pointer", fn);
+    if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 7) || (reinterpret_cast<uintptr_t>(seq_off_dev) & 3))
+        return ibl_set_error(IBL_ERR_ARG, "%s: qkv must be 16-byte, out 8-byte and seq_off 4-byte aligned", fn);
+    int max_tokens;
+    const int st = ragged_offsets_check(fn, seq_off_host, batch, &max_tokens);
+    if (st) return st;
+    return run_attention_ragged(reinterpret_cast<const u16*>(qkv), reinterpret_cast<u16*>(out), seq_off_dev, batch, max_tokens, dim, heads,
+                                cls_only, reinterpret_cast<hipStream_t>(stream), terms);
 }
 
 int run_attention(const u16* qkv, u16* out, int B, int T, int D, int heads, int cls_only, hipStream_t s, int terms) {

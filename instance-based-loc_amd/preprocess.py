@@ -281,3 +281,35 @@ def plan_batch(recipe: PreprocessRecipe, shapes):
         tmp_off += h * recipe.out_w * 3
         max_h = max(max_h, h)
     return descs, cache.packed(), src_off, tmp_off, max_h
+
+
+class CropRaggedDesc(C.Structure):          # ibl_crop_ragged_desc (include/ibloc.h)
+    _fields_ = [("out_h", C.c_int32), ("out_w", C.c_int32), ("row0", C.c_int64), ("u8_offset", C.c_int64)]
+
+
+def plan_batch_ragged(recipe: PreprocessRecipe, shapes, sizes, row0s):
+    """Native-aspect crops: crop i of shape (H, W) is resized WHOLE to sizes[i] = (out_h, out_w) with the recipe's filter -- one exact
+    resize, no shortest-edge step, no centre crop -- and its patches go to the rows from row0s[i] on.
+    Returns (descs of CropDesc, rdescs of CropRaggedDesc, tables int32, src_bytes, tmp_bytes, u8_bytes, max_h)."""
+    cache = TableCache()
+    keys = lambda h, w, oh, ow: ((w, ow, recipe.filt, 0, ow), (h, oh, recipe.filt, 0, oh))
+    want = {k for (h, w), (oh, ow) in zip(shapes, sizes) for k in keys(h, w, oh, ow) if k[0] != k[1] and k not in _TABLES}
+    if want:
+        built = resample_tables_native(sorted(want))
+        if len(_TABLES) + len(built) > 8192:
+            _TABLES.clear()
+        _TABLES.update(built)
+    descs, rdescs = (CropDesc * len(shapes))(), (CropRaggedDesc * len(shapes))()
+    src_off = tmp_off = u8_off = max_h = 0
+    for i, ((h, w), (oh, ow)) in enumerate(zip(shapes, sizes)):
+        kh, kv = keys(h, w, oh, ow)
+        d, r = descs[i], rdescs[i]
+        d.src_offset, d.in_h, d.in_w, d.tmp_offset = src_off, h, w, tmp_off
+        d.h_table, d.h_ksize = cache.get(*kh)
+        d.v_table, d.v_ksize = cache.get(*kv)
+        r.out_h, r.out_w, r.row0, r.u8_offset = oh, ow, int(row0s[i]), u8_off
+        src_off += h * w * 3
+        tmp_off += h * ow * 3
+        u8_off += oh * ow * 3
+        max_h = max(max_h, h)
+    return descs, rdescs, cache.packed(), src_off, tmp_off, u8_off, max_h

@@ -197,7 +197,7 @@ def clip_converter(state_dict):
     raise KeyError("neither a transformers CLIP state dict (vision_model.*) nor an open_clip / OpenAI visual one (conv1.weight)")
 
 
-def load_encoder(kind: str, state_dict, device="cuda", cfg: V.VitConfig = None):
+def load_encoder(kind: str, state_dict, device="cuda", cfg: V.VitConfig = None, native_aspect=False, max_patches=None, upscale=True):
     """Build + register the encoder of `kind` ("dino" | "vit" | "clip" | "dator") from a checkpoint state dict.  cfg: another
     architecture / position-embedding rule than the checkpoint the reference loads (default: V.CONFIGS of the kind).
 
@@ -219,7 +219,18 @@ def load_encoder(kind: str, state_dict, device="cuda", cfg: V.VitConfig = None):
     configuration's are refused (ValueError) before anything is uploaded.
 
     "siglip": a transformers `SiglipVisionModel` / `SiglipModel` state dict -> `ibloc_amd.siglip.SiglipEncoder` (trunk + attention-pooling
-    head); cfg defaults to "siglip_b16_224", the other towers are "siglip_b16_256" / "_384" and "siglip_l16_256" / "_384"."""
+    head); cfg defaults to "siglip_b16_224", the other towers are "siglip_b16_256" / "_384" and "siglip_l16_256" / "_384".
+
+    native_aspect=True ("dino" only, plain or with registers): the registered and returned encoder is a `V.NativeAspectEncoder` -- every
+    crop runs at the patch grid of its own aspect ratio (`V.native_grid` with `max_patches`, default the configuration's, and `upscale`)
+    instead of the recipe's centre-cropped square, so `embed_batch` / `get_all_dino_embeddings` take the ragged forward.  Such
+    embeddings differ from the reference's by design: embed a memory and its queries the same way.  Any other kind, and a configuration
+    without a resampled position table, is refused (ValueError) before anything is uploaded.  False: today's objects, unchanged."""
+    if native_aspect:
+        c = V.CONFIGS[cfg] if isinstance(cfg, str) else (cfg or V.CONFIGS.get(_KIND_TO_CONFIG.get(kind)))
+        if kind != "dino" or c.rope_theta is not None or not c.cls_token or c.proj_dim or c.pre_ln:
+            raise ValueError(f"native_aspect: kind {kind!r} is not supported: per-crop patch grids need a DINOv2 encoder (plain or with "
+                             "registers), whose position table is defined for every grid")
     if kind == "dator":
         from ibloc_amd import dator as D
         if isinstance(state_dict, (str, bytes)) or hasattr(state_dict, "__fspath__"):
@@ -244,6 +255,8 @@ def load_encoder(kind: str, state_dict, device="cuda", cfg: V.VitConfig = None):
     if kind in ("dino", "dinov3"):
         check_dino_weights(weights, cfg)
     enc = V.VitEncoder(cfg, weights, device=device)
+    if native_aspect:
+        enc = V.NativeAspectEncoder(enc, max_patches, upscale)
     set_encoder(kind, enc)
     return enc
 

@@ -340,6 +340,49 @@ def interpolate_pos_embed(pos: np.ndarray, cfg: VitConfig) -> np.ndarray:
     return np.concatenate([cls_pos, patch_new], axis=0).astype(np.float32)
 
 
+ATT_STREAM_MAX_TOKENS = 8192       # IBL_ATT_STREAM_MAX_TOKENS (include/ibloc.h): the longest sequence of the ragged forward, prefix rows included
+
+
+def native_grid(h: int, w: int, patch: int, max_patches: int, upscale: bool = True):
+    """The patch grid (gh, gw) a crop of h x w pixels runs at when it keeps its aspect ratio: the grid of (nearly) the crop's shape
+    that fills a budget of max_patches patches.  Deterministic, float64:
+
+        s  = sqrt(max_patches * patch^2 / (h * w));  if not upscale: s = min(s, 1)
+        gh = min(max(1, floor(h * s / patch + 1e-9)), max_patches);  gw likewise from w
+        while gh * gw > max_patches: decrement the larger of the two (gh on a tie)
+
+    So 1 <= gh, gw and gh * gw <= max_patches always; a square crop gets the square grid of a square budget (16 x 16 of 256); with
+    upscale=False a crop smaller than the budget is not blown up: gh <= max(1, h // patch), gw likewise.  The crop is then resized
+    whole to (gh * patch, gw * patch): the aspect ratio is kept up to the rounding to whole patches."""
+    if h < 1 or w < 1 or patch < 1 or max_patches < 1:
+        raise ValueError(f"native_grid: h, w, patch and max_patches must be positive, got {h} x {w}, {patch}, {max_patches}")
+    s = math.sqrt(float(max_patches) * float(patch) * float(patch) / (float(h) * float(w)))
+    if not upscale:
+        s = min(s, 1.0)
+    gh = min(max(1, int(math.floor(h * s / patch + 1e-9))), max_patches)
+    gw = min(max(1, int(math.floor(w * s / patch + 1e-9))), max_patches)
+    while gh * gw > max_patches:
+        if gh >= gw:
+            gh -= 1
+        else:
+            gw -= 1
+    return gh, gw
+
+
+def token_chunks(tokens, max_tokens):
+    """[slice] over a batch whose crop i has tokens[i] rows: consecutive crops, in order, each chunk within max_tokens rows -- except
+    that a crop which alone exceeds the budget runs as a chunk of its own"""
+    out, lo, acc = [], 0, 0
+    for i, t in enumerate(tokens):
+        if i > lo and acc + t > max_tokens:
+            out.append(slice(lo, i))
+            lo, acc = i, 0
+        acc += t
+    if len(tokens) > lo:
+        out.append(slice(lo, len(tokens)))
+    return out
+
+
 def rope_table(grid_h: int, grid_w: int, theta: float) -> np.ndarray:
     """-> fp32 (grid_h * grid_w, 64) = [cos(32) | sin(32)] per patch: transformers' DINOv3ViTRopePositionEmbedding in eval mode (no
     shift / jitter / rescale) at head_dim 64, in its order of fp32 operations.  Patch-centre coordinates in [-1, 1], inv_freq =
@@ -579,6 +622,8 @@ class VitEncoder:
         self._ws = Workspace(self.device)
         self._streams = []
         self._plan_cache = {}
+        self._pos_stored = weights.get("pos")   # the stored table: `forward_ragged` resamples it once per distinct grid
+        self._grid_pos = {}                     # (gh, gw) -> fp32 device (n_prefix + gh * gw, dim), the prefix rows zero
 
     def _upload(self, struct, fields):
         for name, v in fields:
@@ -697,6 +742,130 @@ class VitEncoder:
             return torch.cat(outs, dim=0)
         return embed_chunks(n, max_batch, lambda sl: self.forward_patches(self.preprocess(crops[sl]), lane=lane))
 
+    # ---- native-aspect crops: every crop at a patch grid of its own ----------------------------
+    def check_ragged(self):
+        """ValueError for what `ibl_vit_forward_ragged` refuses: only class-token models with a learned position table have one for every grid"""
+        c = self.cfg
+        if c.rope_theta is not None or not c.cls_token or c.proj_dim or c.pre_ln or self._pos_stored is None:
+            raise ValueError(f"{c.name}: per-crop patch grids need a class-token model with a learned, resampled position table (DINOv2, "
+                             "plain or with registers); rotary tables (DINOv3), SigLIP and CLIP are not supported")
+
+    def seq_offsets(self, grids) -> np.ndarray:
+        """int32 [n + 1]: crop i owns rows seq[i] .. seq[i + 1] - 1 of every per-token buffer: n_prefix rows, then gh * gw patches"""
+        tokens = [self.cfg.n_prefix + gh * gw for gh, gw in grids]
+        if any(gh < 1 or gw < 1 for gh, gw in grids) or max(tokens) > ATT_STREAM_MAX_TOKENS:
+            raise ValueError(f"a grid is empty or has more than {ATT_STREAM_MAX_TOKENS} tokens with its prefix rows")
+        return np.concatenate([[0], np.cumsum(tokens)]).astype(np.int32)
+
+    def grid_pos_rows(self, grid) -> torch.Tensor:
+        """the position rows of a crop at `grid`: the stored table resampled with the configuration's pos_interp (once per grid, kept on
+        the device), under zero rows for the prefix -- the class row's position is in cls_pos, registers have none"""
+        t = self._grid_pos.get(grid)
+        if t is None:
+            p = self.cfg.patch
+            pos = interpolate_pos_embed(self._pos_stored, dataclasses.replace(self.cfg, img_h=grid[0] * p, img_w=grid[1] * p))[1:]
+            t = torch.from_numpy(np.concatenate([np.zeros((self.cfg.n_prefix, self.cfg.dim), np.float32), pos])).to(self.device)
+            if len(self._grid_pos) < 4096:
+                self._grid_pos[grid] = t
+        return t
+
+    def preprocess_ragged(self, crops, grids, want_u8=False):
+        """crops (a list of HxWx3 uint8 arrays or PackedCrops), grids [(gh, gw)] -> fp16 patch matrix (total_tokens, patch_k_pad): crop
+        i resized WHOLE to (gh * patch, gw * patch) with the recipe's filter, channel swap and mean / std -- no shortest-edge step, no
+        centre crop -- its patches at rows seq[i] + n_prefix + p, the prefix rows zero.  want_u8: -> (patches, [the resized u8 image
+        of every crop, (gh * patch, gw * patch, 3), model channel order])."""
+        r, cfg = self.recipe, self.cfg
+        if not isinstance(crops, PackedCrops):
+            crops = PackedCrops(crops, self.device)
+        shapes, src = crops.shapes, crops.src.to(self.device)
+        assert len(shapes) == len(grids) and len(shapes) > 0
+        seq = self.seq_offsets(grids)
+        sizes = [(gh * cfg.patch, gw * cfg.patch) for gh, gw in grids]
+        descs, rdescs, tables, src_bytes, tmp_bytes, u8_bytes, max_h = pp.plan_batch_ragged(r, shapes, sizes, seq[:-1] + cfg.n_prefix)
+        assert src.numel() == src_bytes
+        to_dev = lambda s: torch.frombuffer(bytearray(bytes(s)), dtype=torch.uint8).to(self.device)
+        d_descs, d_rdescs, d_tables = to_dev(descs), to_dev(rdescs), torch.from_numpy(tables).to(self.device)
+        tmp = torch.empty(max(tmp_bytes, 16), dtype=torch.uint8, device=self.device)
+        patches = torch.empty((int(seq[-1]), cfg.patch_k_pad), dtype=torch.float16, device=self.device)
+        out_u8 = torch.empty(u8_bytes, dtype=torch.uint8, device=self.device) if want_u8 else None
+        st = _lib.lib.ibl_preprocess_crops_ragged(src.data_ptr(), d_descs.data_ptr(), d_rdescs.data_ptr(), C.addressof(rdescs), len(shapes),
+                                                  max_h, d_tables.data_ptr(), tmp.data_ptr(), cfg.patch, cfg.patch_k_pad,
+                                                  1 if r.swap_rb else 0, (C.c_float * 3)(*r.mean), (C.c_float * 3)(*r.std),
+                                                  patches.data_ptr(), patches.shape[0], out_u8.data_ptr() if want_u8 else None,
+                                                  torch.cuda.current_stream().cuda_stream)
+        _lib.check(st, "ibl_preprocess_crops_ragged")
+        if not want_u8:
+            return patches
+        return patches, [out_u8[rd.u8_offset:rd.u8_offset + rd.out_h * rd.out_w * 3].view(rd.out_h, rd.out_w, 3) for rd in rdescs]
+
+    def forward_ragged(self, patches: torch.Tensor, grids, lane: int = 0) -> torch.Tensor:
+        """The forward of crops at their own grids through `ibl_vit_forward_ragged`.  patches fp16 (total_tokens, patch_k_pad), one row
+        per token as `preprocess_ragged` lays them out (`patches_from_pixels_ragged` for pre-normalised pixels); grids [(gh, gw)].
+        -> fp32 (n, dim) class rows, or with out_all_tokens (total_tokens, dim): the crops' rows packed back to back (`seq_offsets`).
+        What the library cannot run -- DINOv3, SigLIP, CLIP -- it refuses: IblError."""
+        cfg = self.cfg
+        seq = self.seq_offsets(grids)
+        n, total = len(grids), int(seq[-1])
+        assert patches.dtype == torch.float16 and patches.is_cuda and patches.is_contiguous() and patches.shape == (total, cfg.patch_k_pad)
+        if self._pos_stored is None or not cfg.cls_token or cfg.proj_dim or cfg.pre_ln:
+            pos = torch.zeros((total, cfg.dim), dtype=torch.float32, device=self.device)     # no table for every grid: the library refuses below
+        else:
+            pos = torch.cat([self.grid_pos_rows(tuple(g)) for g in grids], dim=0)
+        d_seq = torch.from_numpy(seq).to(self.device)
+        ws = self._ws.get(lane, _lib.lib.ibl_vit_ragged_workspace_bytes(C.byref(self.desc), total, n))
+        out = torch.empty((total, cfg.dim) if cfg.out_all_tokens else (n, cfg.out_dim), dtype=torch.float32, device=self.device)
+        st = _lib.lib.ibl_vit_forward_ragged(C.byref(self.desc), C.byref(self.W), patches.data_ptr(), pos.data_ptr(), d_seq.data_ptr(),
+                                             seq.ctypes.data, n, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             torch.cuda.current_stream().cuda_stream)
+        _lib.check(st, "ibl_vit_forward_ragged")
+        return out
+
+    def patches_from_pixels_ragged(self, xs) -> torch.Tensor:
+        """[(3, gh * patch, gw * patch) float model input, already normalised] -> the fp16 patch matrix `forward_ragged` takes (zero
+        prefix rows).  Data-layout plumbing only, as `patches_from_pixels`."""
+        cfg, p = self.cfg, self.cfg.patch
+        rows = []
+        for x in xs:
+            gh, gw = x.shape[1] // p, x.shape[2] // p
+            t = x.to(self.device, torch.float32).reshape(3, gh, p, gw, p).permute(1, 3, 0, 2, 4).reshape(gh * gw, 3 * p * p)
+            m = torch.zeros((cfg.n_prefix + gh * gw, cfg.patch_k_pad), dtype=torch.float16, device=self.device)
+            m[cfg.n_prefix:, :cfg.patch_k] = t.to(torch.float16)
+            rows.append(m)
+        return torch.cat(rows, dim=0)
+
+    def embed_native(self, crops, max_patches=None, upscale=True, max_tokens=65536, lane=0) -> torch.Tensor:
+        """crops -> (N, out_dim) fp32 class embeddings, every crop at `native_grid` of its own shape (max_patches: the budget, default
+        the configuration's n_patches) instead of the recipe's square window.  A batch is cut into chunks of at most max_tokens rows
+        (`token_chunks`); the caller's order is kept.  These embeddings differ from `embed`'s by design: a memory and its queries must be
+        embedded the same way."""
+        self.check_ragged()
+        if not isinstance(crops, PackedCrops):
+            crops = PackedCrops(list(crops), self.device)
+        if len(crops) == 0:
+            return torch.empty((0, self.cfg.out_dim), dtype=torch.float32, device=self.device)
+        budget = self.cfg.n_patches if max_patches is None else int(max_patches)
+        grids = [native_grid(h, w, self.cfg.patch, budget, upscale) for h, w in crops.shapes]
+        outs = [self.forward_ragged(self.preprocess_ragged(crops[sl], grids[sl]), grids[sl], lane=lane)
+                for sl in token_chunks([self.cfg.n_prefix + gh * gw for gh, gw in grids], max_tokens)]
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+
+class NativeAspectEncoder:
+    """A VitEncoder whose `embed` runs every crop at the patch grid of its own aspect ratio (`VitEncoder.embed_native`): what
+    `LocaliseEngine(encoder=...)` and `utils.embeddings` take in place of the encoder itself."""
+
+    def __init__(self, encoder: VitEncoder, max_patches=None, upscale=True):
+        encoder.check_ragged()
+        self.encoder, self.max_patches, self.upscale = encoder, max_patches, upscale
+        self.cfg, self.device = encoder.cfg, encoder.device
+
+    def embed(self, crops, max_batch=512, streams=1, min_split=128, lane=0) -> torch.Tensor:
+        """`VitEncoder.embed`'s signature; max_batch crops at the model's own token count bound a chunk's rows (streams / min_split: one
+        stream runs the ragged forward)"""
+        if isinstance(crops, torch.Tensor):
+            crops = list(crops.cpu().numpy())
+        return self.encoder.embed_native(crops, self.max_patches, self.upscale, max_tokens=max_batch * self.cfg.n_tokens, lane=lane)
+
 
 LINEAR_F16, LINEAR_GELU_F16, LINEAR_RESID_F32, LINEAR_F32 = 0, 1, 2, 4
 LINEAR_PATCH_F32, LINEAR_RESID_PRE_F32, LINEAR_GELU_F16_X2, LINEAR_GELU_F16_X3 = 3, 5, 6, 7
@@ -792,6 +961,27 @@ def attention_stream_f16(qkv: torch.Tensor, heads: int, cls_only: bool = False, 
     values stream through LDS under an fp32 online softmax), on its own.  Arguments and result as for `attention_f16`; n_tokens may be
     anything up to 8192, short rows included.  Shapes the kernel cannot run are refused by the library: IblError."""
     return attention_f16(qkv, heads, cls_only, terms, out, _symbol="ibl_attention_stream_f16")
+
+
+def attention_ragged_f16(qkv: torch.Tensor, seq_off, heads: int, cls_only: bool = False, terms: int = 1, out=None) -> torch.Tensor:
+    """softmax(q k^T / 8) v per (crop, head) over crops of different lengths through `ibl_attention_ragged_f16`: qkv (total, 3 * dim)
+    fp16, crop b in rows seq_off[b] .. seq_off[b + 1] - 1 (seq_off: int32 array of batch + 1 ascending offsets; rows outside every
+    segment are left alone).  Returns (total, terms * dim) fp16; with `cls_only` only row seq_off[b] of every crop is written, so pass
+    `out` unless the rest may stay uninitialised.  A crop's rows are `attention_stream_f16`'s of that crop alone, bit for bit.  What
+    the kernel cannot run is refused by the library: IblError."""
+    assert qkv.dtype == torch.float16 and qkv.is_cuda and qkv.dim() == 2 and qkv.is_contiguous() and qkv.shape[1] % 3 == 0
+    seq = np.ascontiguousarray(seq_off, dtype=np.int32)
+    assert seq.ndim == 1 and seq.size >= 1
+    dim = qkv.shape[1] // 3
+    if out is None:
+        out = torch.empty((qkv.shape[0], max(int(terms), 0) * dim), device=qkv.device, dtype=torch.float16)
+    assert out.dtype == torch.float16 and out.is_cuda and out.is_contiguous() and out.shape == (qkv.shape[0], terms * dim)
+    assert int(seq.max()) <= qkv.shape[0], "a segment ends beyond the buffers"
+    d_seq =torch.from_numpy(seq).to(qkv.device)
+    st = _lib.lib.ibl_attention_ragged_f16(qkv.data_ptr(), out.data_ptr(), d_seq.data_ptr(), seq.ctypes.data, seq.size - 1, dim, heads,
+                                           int(cls_only), terms, torch.cuda.current_stream().cuda_stream)
+    _lib.check(st, "ibl_attention_ragged_f16")
+    return out
 
 
 def rope_f16(qkv: torch.Tensor, table: torch.Tensor, heads: int, n_prefix: int, k_only: bool = False) -> torch.Tensor:
