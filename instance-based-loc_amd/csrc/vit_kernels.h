@@ -70,36 +70,3 @@ VIT_INTERNAL int run_attention(const u16* qkv, u16* out, int B, int T, int D, in
 VIT_INTERNAL int ragged_offsets_check(const char* fn, const int32_t* seq_off, int batch, int* max_tokens);
 VIT_INTERNAL int run_attention_ragged(const u16* qkv, u16* out, const int* seq_off, int B, int max_tokens, int D, int heads, int cls_only,
                                       hipStream_t s, int terms);
-
-// ---- what vit.hip and vit_ragged.hip decide alike
-// What block l runs with: the one place that decides it.
-// cls_only: only the CLS row leaves the encoder (unless all tokens are asked for), so in the LAST block the other rows are dead
-// after they have served as keys / values: its query projection, attention, output projection and MLP run on the CLS
-// rows alone (M = batch instead of batch * T; every row of a GEMM is computed independently, so the CLS rows come out
-// bit-identical).
-// qkv / fc1: two-term operands (ibloc.h): only in blocks that run on every row (the CLS-only last block stays plain).
-// o / fc2: K-extended inputs of the two residual GEMMs (w_o_x / w_fc2_x; round 4): ONE launch of K' = terms * K instead of one
-// read-modify-write pass over the residual per term
-struct BlockTerms {
-    bool cls_only;
-    int qkv, o, fc1, fc2;
-};
-
-static inline BlockTerms block_terms(const ibl_vit_desc* d, const ibl_vit_weights* w, int l) {
-    const ibl_vit_layer* L = &w->layers[l];
-    BlockTerms t;
-    t.cls_only = (l == d->n_blocks_run - 1) && !(d->flags & IBL_VIT_OUT_ALL_TOKENS);
-    t.qkv = (!t.cls_only && L->w_qkv_x && L->qkv_terms > 1) ? L->qkv_terms : 1;
-    t.o = (!t.cls_only && L->w_o_x && L->o_terms > 1) ? L->o_terms : 1;
-    t.fc1 = (!t.cls_only && L->w_fc1_x && L->fc1_terms > 1) ? L->fc1_terms : 1;
-    t.fc2 = (!t.cls_only && L->w_fc2_x && L->fc2_terms > 1) ? L->fc2_terms : 1;
-    return t;
-}
-
-// refused before anything is launched: a descriptor that is wrong in layer l must not leave blocks 0 .. l - 1 in the caller's workspace
-static inline int check_block_terms(const char* fn, int l, const BlockTerms& t, int at) {
-    if (t.qkv > 3 || t.fc1 > 3) return ibl_set_error(IBL_ERR_ARG, "%s: layer %d: at most three operand terms", fn, l);
-    if (t.o > at || t.fc2 > at || t.o > 3 || t.fc2 > 3)
-        return ibl_set_error(IBL_ERR_ARG, "%s: layer %d: o_terms / fc2_terms %d / %d need IBL_VIT_ACT_TERMS%d in the descriptor", fn, l, t.o, t.fc2, t.o > t.fc2 ? t.o : t.fc2);
-    return IBL_OK;
-}

@@ -634,6 +634,14 @@ class VitEncoder:
             setattr(struct, name, v)
 
     # ---- preprocessing -------------------------------------------------------------------------
+    def _bytes_to_device(self, s) -> torch.Tensor:
+        """a ctypes array of descriptors (anything `bytes` takes) -> uint8 device tensor"""
+        return torch.frombuffer(bytearray(bytes(s)), dtype=torch.uint8).to(self.device)
+
+    def _mean_std(self):
+        """the recipe's per-channel mean and std as the float[3] arguments of the preprocessing calls"""
+        return (C.c_float * 3)(*self.recipe.mean), (C.c_float * 3)(*self.recipe.std)
+
     def preprocess(self, crops, want_u8=False):
         """crops: list of HxWx3 uint8 numpy arrays (RGB as the detector hands them over), or a single
         uint8 device/host tensor (N, H, W, 3) of equally sized crops.  Returns fp16 patch matrix (device)."""
@@ -650,7 +658,7 @@ class VitEncoder:
         plan = self._plan_cache.get(key)
         if plan is None:
             descs, tables, src_bytes, tmp_bytes, max_h = pp.plan_batch(r, shapes)
-            d_descs = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(self.device)
+            d_descs = self._bytes_to_device(descs)
             d_tables = torch.from_numpy(tables).to(self.device)
             plan = (d_descs, d_tables, src_bytes, tmp_bytes, max_h)
             if len(self._plan_cache) < 64:
@@ -662,8 +670,7 @@ class VitEncoder:
         tmp = torch.empty(max(tmp_bytes, 16), dtype=torch.uint8, device=self.device)
         patches = torch.empty((n * P, self.cfg.patch_k_pad), dtype=torch.float16, device=self.device)
         out_u8 = torch.empty((n, r.out_h, r.out_w, 3), dtype=torch.uint8, device=self.device) if want_u8 else None
-        mean = (C.c_float * 3)(*r.mean)
-        std = (C.c_float * 3)(*r.std)
+        mean, std = self._mean_std()
         st = _lib.lib.ibl_preprocess_crops(src.data_ptr(), d_descs.data_ptr(), n, max_h, d_tables.data_ptr(),
                                            tmp.data_ptr(), r.out_h, r.out_w, self.cfg.patch, self.cfg.patch_k_pad,
                                            1 if r.swap_rb else 0, mean, std, patches.data_ptr(),
@@ -704,15 +711,15 @@ class VitEncoder:
     def patches_from_pixels(self, x: torch.Tensor) -> torch.Tensor:
         """(B, 3, H, W) float model input (already normalised) -> fp16 patch matrix.  Data-layout plumbing
         only (used by tests and by callers that hold pre-normalised tensors)."""
-        cfg = self.cfg
-        B = x.shape[0]
-        gh, gw = cfg.grid
-        p = cfg.patch
-        t = x.to(self.device, torch.float32).reshape(B, 3, gh, p, gw, p).permute(0, 2, 4, 1, 3, 5)
-        t = t.reshape(B * gh * gw, 3 * p * p)
-        out = torch.zeros((B * gh * gw, cfg.patch_k_pad), dtype=torch.float16, device=self.device)
-        out[:, :cfg.patch_k] = t.to(torch.float16)
-        return out
+        return self._patch_rows(x, self.cfg.grid, 0)
+
+    def _patch_rows(self, x: torch.Tensor, grid, n_prefix: int) -> torch.Tensor:
+        """(B, 3, gh * patch, gw * patch) at one grid -> fp16 (B * (n_prefix + gh * gw), patch_k_pad): n_prefix zero rows, then the crop's patches"""
+        cfg, p, B, (gh, gw) = self.cfg, self.cfg.patch, x.shape[0], grid
+        t = x.to(self.device, torch.float32).reshape(B, 3, gh, p, gw, p).permute(0, 2, 4, 1, 3, 5).reshape(B, gh * gw, 3 * p * p)
+        out = torch.zeros((B, n_prefix + gh * gw, cfg.patch_k_pad), dtype=torch.float16, device=self.device)
+        out[:, n_prefix:, :cfg.patch_k] = t.to(torch.float16)
+        return out.reshape(-1, cfg.patch_k_pad)
 
     def embed(self, crops, max_batch=512, streams=1, min_split=128, lane=0) -> torch.Tensor:
         """crops -> (N, out_dim) fp32 device tensor (un-normalised CLS embedding, as the reference returns).
@@ -743,10 +750,15 @@ class VitEncoder:
         return embed_chunks(n, max_batch, lambda sl: self.forward_patches(self.preprocess(crops[sl]), lane=lane))
 
     # ---- native-aspect crops: every crop at a patch grid of its own ----------------------------
-    def check_ragged(self):
-        """ValueError for what `ibl_vit_forward_ragged` refuses: only class-token models with a learned position table have one for every grid"""
+    def has_grid_tables(self) -> bool:
+        """whether the model has a position table for every grid: a class token and a learned table that is resampled, nothing of CLIP's"""
         c = self.cfg
-        if c.rope_theta is not None or not c.cls_token or c.proj_dim or c.pre_ln or self._pos_stored is None:
+        return c.rope_theta is None and c.cls_token and not c.proj_dim and not c.pre_ln and self._pos_stored is not None
+
+    def check_ragged(self):
+        """ValueError for what `ibl_vit_forward_ragged` refuses: the models without `has_grid_tables`"""
+        c = self.cfg
+        if not self.has_grid_tables():
             raise ValueError(f"{c.name}: per-crop patch grids need a class-token model with a learned, resampled position table (DINOv2, "
                              "plain or with registers); rotary tables (DINOv3), SigLIP and CLIP are not supported")
 
@@ -783,14 +795,13 @@ class VitEncoder:
         sizes = [(gh * cfg.patch, gw * cfg.patch) for gh, gw in grids]
         descs, rdescs, tables, src_bytes, tmp_bytes, u8_bytes, max_h = pp.plan_batch_ragged(r, shapes, sizes, seq[:-1] + cfg.n_prefix)
         assert src.numel() == src_bytes
-        to_dev = lambda s: torch.frombuffer(bytearray(bytes(s)), dtype=torch.uint8).to(self.device)
-        d_descs, d_rdescs, d_tables = to_dev(descs), to_dev(rdescs), torch.from_numpy(tables).to(self.device)
+        d_descs, d_rdescs, d_tables = self._bytes_to_device(descs), self._bytes_to_device(rdescs), torch.from_numpy(tables).to(self.device)
         tmp = torch.empty(max(tmp_bytes, 16), dtype=torch.uint8, device=self.device)
         patches = torch.empty((int(seq[-1]), cfg.patch_k_pad), dtype=torch.float16, device=self.device)
         out_u8 = torch.empty(u8_bytes, dtype=torch.uint8, device=self.device) if want_u8 else None
         st = _lib.lib.ibl_preprocess_crops_ragged(src.data_ptr(), d_descs.data_ptr(), d_rdescs.data_ptr(), C.addressof(rdescs), len(shapes),
                                                   max_h, d_tables.data_ptr(), tmp.data_ptr(), cfg.patch, cfg.patch_k_pad,
-                                                  1 if r.swap_rb else 0, (C.c_float * 3)(*r.mean), (C.c_float * 3)(*r.std),
+                                                  1 if r.swap_rb else 0, *self._mean_std(),
                                                   patches.data_ptr(), patches.shape[0], out_u8.data_ptr() if want_u8 else None,
                                                   torch.cuda.current_stream().cuda_stream)
         _lib.check(st, "ibl_preprocess_crops_ragged")
@@ -807,10 +818,10 @@ class VitEncoder:
         seq = self.seq_offsets(grids)
         n, total = len(grids), int(seq[-1])
         assert patches.dtype == torch.float16 and patches.is_cuda and patches.is_contiguous() and patches.shape == (total, cfg.patch_k_pad)
-        if self._pos_stored is None or not cfg.cls_token or cfg.proj_dim or cfg.pre_ln:
-            pos = torch.zeros((total, cfg.dim), dtype=torch.float32, device=self.device)     # no table for every grid: the library refuses below
-        else:
+        if self.has_grid_tables():
             pos = torch.cat([self.grid_pos_rows(tuple(g)) for g in grids], dim=0)
+        else:
+            pos = torch.zeros((total, cfg.dim), dtype=torch.float32, device=self.device)     # the library refuses below, in its own words
         d_seq = torch.from_numpy(seq).to(self.device)
         ws = self._ws.get(lane, _lib.lib.ibl_vit_ragged_workspace_bytes(C.byref(self.desc), total, n))
         out = torch.empty((total, cfg.dim) if cfg.out_all_tokens else (n, cfg.out_dim), dtype=torch.float32, device=self.device)
@@ -823,15 +834,8 @@ class VitEncoder:
     def patches_from_pixels_ragged(self, xs) -> torch.Tensor:
         """[(3, gh * patch, gw * patch) float model input, already normalised] -> the fp16 patch matrix `forward_ragged` takes (zero
         prefix rows).  Data-layout plumbing only, as `patches_from_pixels`."""
-        cfg, p = self.cfg, self.cfg.patch
-        rows = []
-        for x in xs:
-            gh, gw = x.shape[1] // p, x.shape[2] // p
-            t = x.to(self.device, torch.float32).reshape(3, gh, p, gw, p).permute(1, 3, 0, 2, 4).reshape(gh * gw, 3 * p * p)
-            m = torch.zeros((cfg.n_prefix + gh * gw, cfg.patch_k_pad), dtype=torch.float16, device=self.device)
-            m[cfg.n_prefix:, :cfg.patch_k] = t.to(torch.float16)
-            rows.append(m)
-        return torch.cat(rows, dim=0)
+        p = self.cfg.patch
+        return torch.cat([self._patch_rows(x[None], (x.shape[1] // p, x.shape[2] // p), self.cfg.n_prefix) for x in xs], dim=0)
 
     def embed_native(self, crops, max_patches=None, upscale=True, max_tokens=65536, lane=0) -> torch.Tensor:
         """crops -> (N, out_dim) fp32 class embeddings, every crop at `native_grid` of its own shape (max_patches: the budget, default
